@@ -8,7 +8,11 @@ One "step" = one full CC training step (train.py:445-568: DispResNet6 + PoseNetB
 forward, 6-scale losses, backward, gradient all-reduce, Adam) on a synthetic per-GPU mini-batch of 4 five-frame
 832x256 samples already resident in HBM.  value = N * 4 * K / time (whole-job images/sec, weak scaling).
 
-Extra objects on the JSON line:
+A plain run sets up, warms up, times the K steps and prints the line.  --dump-outputs DIR also writes what the last timed step
+computed (dump_outputs below).  Everything that takes runs of its own -- the objects below, the bench-time parity gate against
+the CPU baseline, and at N > 1 the standalone and exposed communication figures -- runs only with --full.
+
+Extra objects on the JSON line (--full):
   roofline      the dominant DEVICE kernel (the fp32 MFMA implicit-GEMM convolution with the largest share of the step):
                 algorithmic FLOPs of its launches in one instrumented step / their durations -- HIP events recorded by the
                 library around the kernel launch itself (cc_timing_*) -- against the 157.3 TFLOP/s fp32 MFMA peak; traffic =
@@ -60,8 +64,16 @@ def parse():
     ap.add_argument("--freeze", action="store_true",
                     help="README.md:59-65 training variant --fix-masknet --fix-flownet (train.py:332-346): all four nets run "
                          "forward, only DispResNet6 + PoseNetB6 are trained (227 MB gradient bucket); reported beside the metric")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-kernel-timing", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need: CPU baseline + parity gate, per-kernel "
+                         "timing and roofline, and at N > 1 the standalone / exposed communication figures")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the losses, a seeded sample of the parameters and gradients, and the module buffers after the "
+                         "last timed step as DIR/<name>.npy (float32 / float64).  In the library's default config.deterministic "
+                         "mode the same arguments give the same arrays bit for bit -- at N > 1 only with an explicit --pipeline: "
+                         "'auto' chooses the form by timing")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline and the parity gate")
+    ap.add_argument("--no-kernel-timing", action="store_true", help="(--full) skip the per-kernel timing and the roofline")
     ap.add_argument("--pipeline", choices=("auto", "per_network", "post", "staged"), default="auto",
                     help="per_network: every network's gradient all-reduce -> Adam segment -> weight images at the end of ITS "
                          "backward pass, on its own stream inside the one hipGraph; post: round 5 (one graph, two process-group "
@@ -263,6 +275,36 @@ class CallTimer:
 
 def log(*a):
     print("[bench]", *a, file=sys.stderr, flush=True)
+
+
+DUMP_SAMPLE = 1 << 22      # elements drawn from each of the parameter and gradient vectors: 2 x 16 MB of float32
+
+
+def output_snapshot(tr, losses):
+    """What a caller of the timed step holds after its last step, as host arrays: the loss terms (float64), the networks'
+    trainable parameters and their gradients in chain order (float32; where there are more than DUMP_SAMPLE elements, the same
+    fixed sample of both, drawn with seed 0 and sorted), and the module buffers (BatchNorm running statistics, float64).
+    Taken right after the timed region, before any other step moves the weights.  -> {name: numpy array}"""
+    import numpy as np
+    torch.cuda.synchronize()
+    out = {k: np.array(float(v), dtype=np.float64) for k, v in losses.items()}
+    p, g = tr.opt.gather(tr.opt.flat_p), tr.opt.gather(tr.opt.flat_g)
+    if p.numel() > DUMP_SAMPLE:
+        idx = torch.unique(torch.randint(0, p.numel(), (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(0)))
+        p, g = p[idx.to(p.device)], g[idx.to(g.device)]
+    out["params"], out["grads"] = p.cpu().numpy(), g.cpu().numpy()
+    bufs = [b.detach().reshape(-1).double() for n_ in tr.nets if n_ is not None for b in n_.buffers()]
+    if bufs:
+        out["buffers"] = torch.cat(bufs).cpu().numpy()
+    return out
+
+
+def dump_outputs(d, arrays):
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(d, k + ".npy"), v)
+    log("wrote %d arrays (%.1f MB) to %s" % (len(arrays), sum(v.nbytes for v in arrays.values()) / 1e6, d))
 
 
 def pmc_traffic(kernel):
@@ -467,7 +509,7 @@ def main():
     from tools import ab_env
     ab_switches = ab_env.apply()            # CC_* A/B variables -> cc_amd.config.debug, BEFORE the first engine() call (library path);
     #                                         explicit: the package itself reads no environment variable
-    from cc_amd import synthetic as syn, trainer as T, _lib
+    from cc_amd import synthetic as syn, trainer as T, _lib, config as cc_config
     eng = _lib.engine()
 
     torch.manual_seed(0)                                             # train.py:152
@@ -480,7 +522,7 @@ def main():
             if n_ is not None:
                 for p_ in n_.parameters():
                     p_.requires_grad = False                             # train.py:332-339
-    want_cpu = rank == 0 and world == 1 and not args.no_cpu_baseline
+    want_cpu = args.full and rank == 0 and world == 1 and not args.no_cpu_baseline
     init_sd = [({k: v.detach().cpu().clone() for k, v in n_.state_dict().items()} if n_ is not None else None)
                for n_ in nets] if want_cpu else None
     B, H, W = args.batch, args.height, args.width
@@ -527,7 +569,8 @@ def main():
             log("warm-up step %d done at %.1f s" % (i, time.perf_counter() - t_w))
     def timed_region():
         """EXACTLY args.steps steps between barrier + synchronize; per-step device time stamps: an event after every step on the
-        compute stream (no host synchronisation inside the region).  -> (wall seconds of this rank, sorted per-step ms, last losses)"""
+        compute stream (no host synchronisation inside the region).  -> (wall seconds of this rank, sorted per-step ms, last losses,
+        output_snapshot of the last step or None)"""
         sync()
         marks = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
         t0_ = time.perf_counter()
@@ -537,7 +580,8 @@ def main():
             marks[i + 1].record()
         sync()
         dt_ = time.perf_counter() - t0_
-        return dt_, sorted(marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps)), ls_
+        snap_ = output_snapshot(tr, ls_) if args.dump_outputs and rank == 0 else None
+        return dt_, sorted(marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps)), ls_, snap_
 
     def max_over_ranks(x):
         if not use_dist:
@@ -567,7 +611,7 @@ def main():
         # machine this code has never seen), every rank's watchdog ends its process after rank 0 has printed the line of the "post"
         # region -- the run keeps its number and says what happened.
         import threading
-        dt_post, steps_post, losses_post = timed_region()
+        dt_post, steps_post, losses_post, snap_post = timed_region()
         dt_post_max = max_over_ranks(dt_post)
         ms_post = 1e3 * dt_post_max / args.steps
         limit = float(os.environ.get("CC_FORM_WATCHDOG_S", "240"))
@@ -645,9 +689,12 @@ def main():
             % (ms_post, ("%.2f ms" % ms_pn) if ms_pn is not None else "failed", ("%.2f ms" % ms_ch) if ms_ch is not None else "-", chosen_full))
         if chosen == "post":
             disarm.set()
-            first_region = (dt_post, steps_post, losses_post)
-    comm_cal = tr.calibrate_comm() if use_dist else None            # each segment's all-reduce alone (outside the timed region)
-    dt, per_step, losses = first_region if first_region is not None else timed_region()
+            first_region = (dt_post, steps_post, losses_post, snap_post)
+    if use_dist and args.full:
+        tr.calibrate_comm()                 # each segment's all-reduce alone (outside the timed region)
+    dt, per_step, losses, snap = first_region if first_region is not None else timed_region()
+    if snap is not None:
+        dump_outputs(args.dump_outputs, snap)
     if select and form_selection is not None and form_selection["chosen"] != "post":
         disarm.set()
 
@@ -679,7 +726,7 @@ def main():
     if rank == 0:
         log("timed %d steps: %.2f ms/step, loss %.6f" % (args.steps, 1e3 * dt / args.steps, loss_val))
     tr.check_finite()
-    if use_dist and comm is not None and tr.graph_b is not None and not tr.opt.comm_probe:
+    if args.full and use_dist and comm is not None and tr.graph_b is not None and not tr.opt.comm_probe:
         # backward stage B with the collectives skipped (see comm.stage_b_ms above): a few untimed steps
         tr.opt.comm_probe, tr.stage_b_events = "skip", []
         for _ in range(6):
@@ -688,7 +735,7 @@ def main():
         comm["stage_b_ms"]["collectives_skipped"] = tr.stage_b_ms()
         tr.opt.comm_probe = ""
 
-    if use_dist and comm is not None and tr.pipeline == "per_network" and not tr.opt.comm_probe and not args.no_graph:
+    if args.full and use_dist and comm is not None and tr.pipeline == "per_network" and not tr.opt.comm_probe and not args.no_graph:
         # EXPOSED communication of the per-network form: its collectives are nodes of the replayed graph (no event can bracket them),
         # so the same step is captured once more with the collectives skipped and timed over a few steps AFTER the timed region and the
         # parity gate (the ranks' weights diverge in those steps; nothing else is reported from them).  exposed = with - without.
@@ -716,7 +763,7 @@ def main():
                                "them skipped (re-captured; measured back to back after the timed region)" % n_ab)
 
     kernels, roof = None, None
-    if not args.no_kernel_timing:
+    if args.full and not args.no_kernel_timing:
         tr_e = tr
         tr_e.use_graph = False
         # Per-kernel and per-call durations are taken with the networks' side streams OFF: a kernel that shares the chip with another
@@ -844,7 +891,7 @@ def main():
                        "hip_runtime": {"AMD_DIRECT_DISPATCH": os.environ.get("AMD_DIRECT_DISPATCH", "default (1)")},
                        "dead_occlusion_decoders_elided": bool(args.elide_occ), "ab_switches": ab_switches or None,
                        "net_streams": (len(tr.net_streams) if tr.net_streams else 0), "pipeline": tr.pipeline,
-                       "grad_chunks": bool(getattr(tr, "grad_chunks", False))},
+                       "grad_chunks": bool(getattr(tr, "grad_chunks", False)), "deterministic": bool(cc_config.deterministic)},
             "step_ms": step_ms, "comm": comm,
             "roofline": roof, "kernels": kernels,
         }

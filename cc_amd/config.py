@@ -10,10 +10,12 @@ align_corners = False
 # reference's behaviour, loss_functions.py:60,105,115).  False: device flag, see loss_functions.check_finite().
 strict_nan_checks = False
 
-# True: run-to-run bit-reproducible training steps.  The one order-dependent reduction of the step -- the feature-gradient
-# scatter of Back2Future's warps (float atomics, as in the reference's grid_sample backward) -- then accumulates 64-bit
-# fixed-point integers instead (cc_feature_warp_bwd_det: four launches per warp instead of two, ~+0.3 ms per step).
-deterministic = False
+# True (default): run-to-run bit-reproducible training steps.  The one order-dependent reduction of the step -- the feature-gradient
+# scatter of Back2Future's warps -- accumulates 64-bit fixed-point integers (cc_feature_warp_bwd_det: four launches per warp instead
+# of two).  With Back2Future's backward pass on a side stream of the hipGraph that costs +0.12 ms of a 15.8 ms step
+# (profiles/ab_deterministic.txt; it was ~0.3 ms when the step ran on one stream).  False: float atomics, as in the reference's
+# grid_sample backward -- last-bit differences from run to run, which Adam's updates grow over the steps of a run.
+deterministic = True
 
 # True: the four networks of a CCTrainer step run on HIP streams of their own (DispResNet6 and Back2Future on one side stream
 # each, PoseNetB6 and MaskNet6 on the step's stream; forward and backward), joined before the losses / the optimizer.  Their layer

@@ -27,6 +27,8 @@ def apply(env=None):
         config.net_streams = got["net_streams"] = int(env["CC_NET_STREAMS"])           # 0 / 1 (= 2 side streams) / 3
     if env.get("CC_NET_STREAM_PRIORITY"):              # e.g. "0,-1": Back2Future's stream high
         config.debug.net_stream_priority = got["net_stream_priority"] = tuple(int(v) for v in env["CC_NET_STREAM_PRIORITY"].replace(":", ",").split(","))
+    if env.get("CC_DETERMINISTIC") is not None:        # product switch cc_amd.config.deterministic (A/B: 0 = float-atomic scatter)
+        config.deterministic = got["deterministic"] = bool(int(env["CC_DETERMINISTIC"]))
     if env.get("CC_GRAD_CHUNKS") is not None:          # product switch cc_amd.config.grad_chunks
         config.grad_chunks = got["grad_chunks"] = bool(int(env["CC_GRAD_CHUNKS"]))
     if env.get("CC_BIAS_TABLE") is not None:           # product switch cc_amd.config.bias_table

@@ -52,13 +52,13 @@ for STEP in "$@"; do
   smoke)
     ( timeout 300 python -c "import __graft_entry__ as g; g.smoke()" ) > $O/smoke_$TAG.log 2>&1; echo "smoke rc=$?"; tail -3 $O/smoke_$TAG.log ;;
   bench)
-    ( timeout 700 python bench.py ) > $O/bench_$TAG.log 2> $O/bench_$TAG.err; echo "bench rc=$?"
+    ( timeout 700 python bench.py --full ) > $O/bench_$TAG.log 2> $O/bench_$TAG.err; echo "bench rc=$?"
     grep -E "cpu baseline|timed" $O/bench_$TAG.err | tail -4; line $O/bench_$TAG.log ;;
   quick)
     ( timeout 300 python bench.py $NOCPU --steps 30 ) > $O/bench_${TAG}_quick.log 2> $O/bench_${TAG}_quick.err; echo "quick rc=$?"
     grep timed $O/bench_${TAG}_quick.err ;;
   comm)
-    ( CC_FORCE_COMM=1 timeout 300 python bench.py $NOCPU --steps 20 --warmup 5 ) > $O/bench_${TAG}_comm.log 2> $O/bench_${TAG}_comm.err; echo "comm rc=$?"
+    ( CC_FORCE_COMM=1 timeout 300 python bench.py --full $NOCPU --steps 20 --warmup 5 ) > $O/bench_${TAG}_comm.log 2> $O/bench_${TAG}_comm.err; echo "comm rc=$?"
     line $O/bench_${TAG}_comm.log ;;
   cfg)
     for C in "--freeze" "--config c2" "--height 512 --width 1664 --batch 2" "--batch 8"; do
@@ -107,7 +107,7 @@ for STEP in "$@"; do
     python tools/pmc_mfma.py "$F" $O/rocprof_kernel_stats_${TAG}_serial.csv > $O/pmc_mfma_$TAG.txt 2>&1; head -26 $O/pmc_mfma_$TAG.txt | cut -c1-120 ;;
   layers)
     # (the table comes from bench.py's isolated pass: side streams off)
-    ( CC_TIMING_DETAIL=1 CC_TIMING_DUMP=$O/layers_$TAG.tsv timeout 400 python bench.py --steps 5 --warmup 3 --no-cpu-baseline ) > $O/bench_${TAG}_layers.log 2> $O/bench_${TAG}_layers.err
+    ( CC_TIMING_DETAIL=1 CC_TIMING_DUMP=$O/layers_$TAG.tsv timeout 400 python bench.py --full --steps 5 --warmup 3 --no-cpu-baseline ) > $O/bench_${TAG}_layers.log 2> $O/bench_${TAG}_layers.err
     python tools/layer_rates.py $O/layers_$TAG.tsv > $O/layer_rates_$TAG.txt; head -${LAYER_ROWS:-40} $O/layer_rates_$TAG.txt | cut -c1-170 ;;
   ab)
     export CC_LIB_PATH=${CC_LIB_PATH:-$TOOLS_LIB}

@@ -1,12 +1,14 @@
 #!/bin/bash
-mkdir -p gpurun_out
+# usage: bash tools/gpu_conv.sh OUTDIR
+O=${1:?usage: bash tools/gpu_conv.sh OUTDIR}
+mkdir -p "$O"
 export TMPDIR=/tmp
-( timeout 400 python tools/conv_bench.py ) > gpurun_out/conv_bench.log 2>&1; echo "conv_bench rc=$?"
-( timeout 900 python -m pytest tests -m gpu -q -s ) > gpurun_out/pytest_gpu.log 2>&1; echo "pytest rc=$?"
-( timeout 300 python bench.py --steps 10 --warmup 2 --no-cpu-baseline ) > gpurun_out/bench_graph.log 2>&1; echo "bench graph rc=$?"
-grep -E "passed|failed|FAILED|^E  " gpurun_out/pytest_gpu.log | tail -12
-grep -E "bench\]" gpurun_out/bench_graph.log; tail -c 2500 gpurun_out/bench_graph.log | head -c 2400; echo
-cat gpurun_out/conv_bench.log | python -c "
+( timeout 400 python tools/conv_bench.py ) > $O/conv_bench.log 2>&1; echo "conv_bench rc=$?"
+( timeout 900 python -m pytest tests -m gpu -q -s ) > $O/pytest_gpu.log 2>&1; echo "pytest rc=$?"
+( timeout 300 python bench.py --full --steps 10 --warmup 2 --no-cpu-baseline ) > $O/bench_graph.log 2>&1; echo "bench graph rc=$?"
+grep -E "passed|failed|FAILED|^E  " $O/pytest_gpu.log | tail -12
+grep -E "bench\]" $O/bench_graph.log; tail -c 2500 $O/bench_graph.log | head -c 2400; echo
+cat $O/conv_bench.log | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

@@ -1,8 +1,8 @@
 #!/usr/bin/env python
 """Per-layer-shape device-kernel rates of one eager step.
 
-    CC_TIMING_DETAIL=1 CC_TIMING_DUMP=gpurun_out/layers.tsv python bench.py --steps 5 --warmup 3
-    python tools/layer_rates.py gpurun_out/layers.tsv
+    CC_TIMING_DETAIL=1 CC_TIMING_DUMP=layers.tsv python bench.py --full --steps 5 --warmup 3
+    python tools/layer_rates.py layers.tsv
 
 The tools build of the library (tools/_bin/libccengine_tools.so) brackets the main device kernel of every conv / data-gradient /
 weight-gradient call with HIP events; with CC_TIMING_DETAIL=1 the record name carries the layer geometry, the split-K factor (k)
