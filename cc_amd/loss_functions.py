@@ -20,6 +20,7 @@ import torch
 from torch import nn
 
 from . import config
+from . import metrics as _metrics
 from ._lib import engine, STREAM
 from .inverse_warp import projection_matrix, pose2flow, _ac
 from .ssim import gauss13_ptr
@@ -1248,10 +1249,11 @@ def weighted_binary_cross_entropy(output, target, weights=None):
 
 
 # ----------------------------------------------------------------------------- validation metrics
-# loss_functions.py:355-467, consumed by train.py's validate_* loops (train.py:588-777).  Device-side torch arithmetic
-# on whatever device the inputs live on (they run once per validation batch, far off the training hot path), same
-# values as the reference.  The reference returns Python floats through .item() (a host sync per metric); sync=False
-# returns 0-dim device tensors instead so that a validation loop can stay asynchronous.
+# loss_functions.py:355-467, consumed by train.py's validate_* loops (train.py:588-777).  On HIP tensors every function is
+# one cc_amd.metrics call (cc_amd/csrc/metrics.hip: no host sync, capturable, deterministic); on CPU tensors the reference's
+# expressions on ATen (the `_*_aten` bodies, also callable on HIP tensors as a timing baseline).  The reference returns
+# Python floats through .item() (a host sync per metric); sync=False returns 0-dim device tensors instead so that a
+# validation loop can stay asynchronous.
 def _upsample_to(pred, size):
     """nn.functional.upsample(pred, size=size, mode='bilinear') (loss_functions.py:359,373,394,414-415): align_corners
     has defaulted to False for upsample since torch 0.4, i.e. for the authors' torch 1.0 as well as today's -- it does
@@ -1266,13 +1268,13 @@ def _scaled_uv(gt, pred):
     return gt[:, 0], gt[:, 1], pred[:, 0] * (w_gt / w_pred), pred[:, 1] * (h_gt / h_pred)
 
 
-def flow_diff(gt, pred):
+def _flow_diff_aten(gt, pred):
     """loss_functions.py:355-365 -> per-pixel end-point error [B,H,W] at the ground truth's resolution."""
     u_gt, v_gt, u_pred, v_pred = _scaled_uv(gt, pred)
     return torch.sqrt(torch.pow((u_gt - u_pred), 2) + torch.pow((v_gt - v_pred), 2))
 
 
-def compute_epe(gt, pred, sync=True):
+def _compute_epe_aten(gt, pred, sync=True):
     """loss_functions.py:368-388: mean EPE; a third ground-truth channel is a validity mask."""
     bs, nc, h_gt, w_gt = gt.size()
     u_gt, v_gt, u_pred, v_pred = _scaled_uv(gt, pred)
@@ -1287,7 +1289,7 @@ def compute_epe(gt, pred, sync=True):
     return avg_epe.item() if sync else avg_epe
 
 
-def outlier_err(gt, pred, tau=[3, 0.05], sync=True):
+def _outlier_err_aten(gt, pred, tau=[3, 0.05], sync=True):
     """loss_functions.py:390-409: KITTI Fl outlier ratio (EPE > 3 px AND > 5 % of the flow magnitude)."""
     u_gt, v_gt, u_pred, v_pred = _scaled_uv(gt, pred)
     valid_gt = gt[:, 2]
@@ -1301,7 +1303,7 @@ def outlier_err(gt, pred, tau=[3, 0.05], sync=True):
     return f_err.item() if sync else f_err
 
 
-def compute_all_epes(gt, rigid_pred, non_rigid_pred, rigidity_mask, THRESH=0.5, sync=True):
+def _compute_all_epes_aten(gt, rigid_pred, non_rigid_pred, rigidity_mask, THRESH=0.5, sync=True):
     """loss_functions.py:411-429 -> [all_epe, rigid_epe, non_rigid_epe, outliers]."""
     _, _, h_pred, w_pred = rigid_pred.size()
     _, _, h_gt, w_gt = gt.size()
@@ -1312,16 +1314,16 @@ def compute_all_epes(gt, rigid_pred, non_rigid_pred, rigidity_mask, THRESH=0.5, 
     total_pred = non_rigid_pred + rigid_pred
     gt_non_rigid = (rigidity_gt_mask <= THRESH).type_as(gt).expand_as(gt) * gt
     gt_rigid = (rigidity_gt_mask > THRESH).type_as(gt).expand_as(gt) * gt
-    all_epe = compute_epe(gt, total_pred, sync)
-    rigid_epe = compute_epe(gt_rigid, rigid_pred, sync)
-    non_rigid_epe = compute_epe(gt_non_rigid, non_rigid_pred, sync)
-    outliers = outlier_err(gt, total_pred, sync=sync)
+    all_epe = _compute_epe_aten(gt, total_pred, sync)
+    rigid_epe = _compute_epe_aten(gt_rigid, rigid_pred, sync)
+    non_rigid_epe = _compute_epe_aten(gt_non_rigid, non_rigid_pred, sync)
+    outliers = _outlier_err_aten(gt, total_pred, sync=sync)
     return [all_epe, rigid_epe, non_rigid_epe, outliers]
 
 
-def compute_errors(gt, pred, crop=True):
+def _compute_errors_aten(gt, pred, crop=True):
     """loss_functions.py:432-467: [abs_diff, abs_rel, sq_rel, a1, a2, a3] of median-scaled depth (Garg/Eigen crop).
-    gt, pred: [B,H,W]; returns 0-dim tensors like the reference (no host sync inside)."""
+    gt, pred: [B,H,W]; returns 0-dim tensors like the reference (on a device, the boolean indexing syncs once per sample)."""
     abs_diff, abs_rel, sq_rel, a1, a2, a3 = 0, 0, 0, 0, 0, 0
     batch_size = gt.size(0)
     if crop:
@@ -1344,6 +1346,49 @@ def compute_errors(gt, pred, crop=True):
         abs_rel += torch.mean(torch.abs(valid_gt - valid_pred) / valid_gt)
         sq_rel += torch.mean(((valid_gt - valid_pred) ** 2) / valid_gt)
     return [metric / batch_size for metric in [abs_diff, abs_rel, sq_rel, a1, a2, a3]]
+
+
+def _values(t, sync):
+    """one read-back for sync=True (Python floats), else 0-dim views of the device result"""
+    return t.tolist() if sync else list(t.unbind(0))
+
+
+def flow_diff(gt, pred):
+    """loss_functions.py:355-365 -> per-pixel end-point error [B,H,W] at the ground truth's resolution."""
+    if gt.is_cuda:
+        return _metrics.flow_metrics(gt, pred, epe_map=True)[1]
+    return _flow_diff_aten(gt, pred)
+
+
+def compute_epe(gt, pred, sync=True):
+    """loss_functions.py:368-388: mean EPE; a third ground-truth channel is a validity mask."""
+    if gt.is_cuda:
+        return _values(_metrics.flow_metrics(gt, pred)[:1], sync)[0]
+    return _compute_epe_aten(gt, pred, sync)
+
+
+def outlier_err(gt, pred, tau=[3, 0.05], sync=True):
+    """loss_functions.py:390-409: KITTI Fl outlier ratio (EPE > 3 px AND > 5 % of the flow magnitude)."""
+    if gt.is_cuda:
+        if gt.size(1) < 3:
+            raise IndexError("outlier_err: the validity channel gt[:, 2] is missing")
+        return _values(_metrics.flow_metrics(gt, pred, tau=tau)[1:], sync)[0]
+    return _outlier_err_aten(gt, pred, tau, sync)
+
+
+def compute_all_epes(gt, rigid_pred, non_rigid_pred, rigidity_mask, THRESH=0.5, sync=True):
+    """loss_functions.py:411-429 -> [all_epe, rigid_epe, non_rigid_epe, outliers]."""
+    if gt.is_cuda:
+        return _values(_metrics.flow_metrics(gt, rigid_pred, non_rigid_pred, masks=(rigidity_mask,), THRESH=THRESH), sync)
+    return _compute_all_epes_aten(gt, rigid_pred, non_rigid_pred, rigidity_mask, THRESH, sync)
+
+
+def compute_errors(gt, pred, crop=True):
+    """loss_functions.py:432-467: [abs_diff, abs_rel, sq_rel, a1, a2, a3] of median-scaled depth (Garg/Eigen crop).
+    gt, pred: [B,H,W]; returns 0-dim tensors like the reference (no host sync inside)."""
+    if gt.is_cuda:
+        return list(_metrics.depth_errors(gt, pred, crop).unbind(0))
+    return _compute_errors_aten(gt, pred, crop)
 
 
 def edge_aware_smoothness_per_pixel(img, pred):

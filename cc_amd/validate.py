@@ -7,8 +7,11 @@ What differs from the reference, deliberately:
     THRESH, and -- only for the optional per-sample hook -- rotation_mode / padding_mode).
   * the ~25 stock-torch launches of the rigidity-mask composition (train.py:673-687) are ONE HIP launch (`cc_rigidity_compose`,
     cc_amd/csrc/validate.hip) -> `rigidity_composition`.
-  * the metrics stay on the device (`sync=False`) and are read back once at the end of the loop instead of eight `.item()` host
-    syncs per sample.
+  * the metrics are HIP kernels (cc_amd/metrics.py, cc_amd/csrc/metrics.hip): the eight flow errors of a sample are ONE
+    `flow_metrics` call with both rigidity masks, the depth errors one `depth_errors` call (exact medians by radix select, no
+    boolean indexing).  No metric call synchronises with the host, so the loop body can be captured into a graph; the values
+    stay on the device and are read back once at the end of the loop (`_finish`) instead of eight `.item()` host syncs per
+    sample.
   * TensorBoard image / histogram logging and the terminal progress bar (train.py:615-633,700-741,758-768) are UI and out of
     scope; `on_sample(i, dict_of_intermediates)` is the hook a caller's own logging attaches to -- it receives every tensor the
     reference logs.
@@ -20,6 +23,7 @@ import types
 import torch
 
 from . import loss_functions as LF
+from . import metrics
 from ._lib import engine, STREAM
 from .inverse_warp import pose2flow
 from .logger import AverageMeter
@@ -80,7 +84,7 @@ def validate_depth_with_gt(val_loader, disp_net, epoch=0, logger=None, output_wr
                 output_disp = LF.spatial_normalize(output_disp)                # :603-604
             output_depth = 1 / output_disp                                     # :606
             depth = depth.to(dev)
-            errors.update(LF.compute_errors(depth, output_depth.squeeze(1)))   # :624 (0-dim device tensors, no sync)
+            errors.update(list(metrics.depth_errors(depth, output_depth.squeeze(1)).unbind(0)))   # :624 (0-dim device tensors, no sync)
             if on_sample is not None:
                 on_sample(i, dict(tgt_img=tgt_img, depth=depth, output_disp=output_disp, output_depth=output_depth))
     return _finish(errors), error_names
@@ -117,11 +121,11 @@ def validate_flow_with_gt(val_loader, disp_net, pose_net, mask_net, flow_net, ep
             flow_cam = pose2flow(depth.squeeze(1), pose[:, 2], intrinsics, intrinsics_inv)       # :672
             r = rigidity_composition(explainability_mask, flow_cam, flow_fwd, args.THRESH,
                                      want=RIGIDITY_FIELDS if on_sample is not None else ("rigidity_mask_combined", "total_flow"))
-            obj_map_gt_expanded = obj_map_gt.unsqueeze(1).type_as(flow_fwd)    # :689
             bad = torch.isnan(flow_gt.sum()) | torch.isnan(r.total_flow.sum())  # :746 (device flag; reported after the loop)
             nan_seen = bad if nan_seen is None else (nan_seen | bad)
-            _epe_errors = LF.compute_all_epes(flow_gt, flow_cam, flow_fwd, r.rigidity_mask_combined, sync=False) + \
-                LF.compute_all_epes(flow_gt, flow_cam, flow_fwd, (1 - obj_map_gt_expanded), sync=False)   # :748
+            # :748, both compute_all_epes calls in one: the predicted mask and 1 - obj_map_gt (:689, inverted in the kernel)
+            _epe_errors = list(metrics.flow_metrics(flow_gt, flow_cam, flow_fwd, masks=(r.rigidity_mask_combined, ("1-", obj_map_gt)),
+                                                    THRESH=0.5).unbind(0))
             errors.update(_epe_errors)
             if on_sample is not None:
                 on_sample(i, dict(tgt_img=tgt_img, ref_imgs=ref_imgs, flow_gt=flow_gt, depth=depth, pose=pose,

@@ -470,6 +470,31 @@ int cc_rigidity_compose(const float* exp_mask, int MC, const float* flow_cam, co
                         float* census, float* combined, float* flow_non_rigid, float* flow_rigid, float* total_flow,
                         float* oob_rigid, float* oob_non_rigid, float thresh, int B, int H, int W, void* stream);
 
+/* ---------------------------------------------------------------- validation metrics (loss_functions.py:355-467)
+ * Sync-free and deterministic: no host synchronisation, fp64 per-workgroup partials in `ws` reduced in a fixed order, integer
+ * atomics only (the radix histograms of the depth medians); `ws` is zeroed on the stream where needed, sized by the *_ws query.
+ * Bilinear resizes are F.interpolate(mode='bilinear', align_corners=False).
+ *
+ * cc_flow_metrics: gt [B,Cg,Hg,Wg] (Cg = 2, or 3 with channel 2 the validity mask), rigid_pred [B,2,Hp,Wp] and, with masks,
+ * non_rigid_pred [B,2,Hp,Wp]; mask0 / mask1 NULL or [B,1,Hm,Wm] each at its own size (inv: the mask is 1 - mask).
+ *   no mask (non_rigid_pred NULL): pred = rigid_pred, out[2] = [compute_epe, outlier_err] (:368-409; outlier NaN for Cg = 2);
+ *   per mask k: out[4k..4k+3] = compute_all_epes (:411-429) = [all_epe, rigid_epe, non_rigid_epe, outliers]
+ *     (rigid: mask resized to the prediction > thresh; gt masked on every channel by the mask resized to the ground truth).
+ * tau_px / tau_rel: the outlier thresholds (3, 0.05).  epe_map [B,Hg,Wg] or NULL: flow_diff (:355-365) of the (total)
+ * prediction, with mask0 when masks are given.  ws: cc_flow_metrics_ws(B, Hg, Wg, nmasks) bytes. */
+size_t cc_flow_metrics_ws(int B, int Hg, int Wg, int nmasks);
+int cc_flow_metrics(const float* gt, int Cg, int Hg, int Wg, const float* rigid_pred, const float* non_rigid_pred, int Hp, int Wp,
+                    const float* mask0, int Hm0, int Wm0, int inv0, const float* mask1, int Hm1, int Wm1, int inv1, float thresh,
+                    float tau_px, float tau_rel, int B, float* epe_map, float* out, void* ws, void* stream);
+/* cc_depth_errors: compute_errors (:432-467) of gt / pred [B,H,W] inside the crop box rows [y1,y2) x cols [x1,x2) (the whole image
+ * for crop=False) -> out6 = [abs_diff, abs_rel, sq_rel, a1, a2, a3]: per sample valid = 0 < gt < 80, p = clamp(pred, 1e-3, 80)
+ * scaled by median(gt) / median(p) (exact lower medians by radix select), six means; summed over samples in order, / B.
+ * An empty sample or a NaN among its valid predictions gives NaN where torch.median / mean do.
+ * ws: cc_depth_errors_ws(B, H, W) bytes. */
+size_t cc_depth_errors_ws(int B, int H, int W);
+int cc_depth_errors(const float* gt, const float* pred, int B, int H, int W, int y1, int y2, int x1, int x2, float* out6, void* ws,
+                    void* stream);
+
 /* ---------------------------------------------------------------- optimizer (train.py:307-310,568)
  * torch.optim.Adam(betas, eps, weight_decay=0) on the flat fp32 bucket; grads are multiplied by grad_scale first
  * (1/world_size after the RCCL all-reduce).  step_dev: device float, incremented by the call. */
