@@ -4,24 +4,13 @@
 // (scale, reference frame) -- ~700 launches per training step -- by one launch each way.  One work-item per sample.
 #include "cc_common.h"
 #include "jobs.h"
+#include "pose_mat.h"
 #include "../../include/ccengine.h"
 
 namespace {
 
-struct Rot { float R[9]; float cx, sx, cy, sy, cz, sz; };
-
-__device__ __forceinline__ void euler(const float* p, Rot& r) {
-    r.cx = cosf(p[3]); r.sx = sinf(p[3]);
-    r.cy = cosf(p[4]); r.sy = sinf(p[4]);
-    r.cz = cosf(p[5]); r.sz = sinf(p[5]);
-    // (Rx.Ry).Rz
-    const float a00 = r.cy, a01 = 0.f, a02 = r.sy;
-    const float a10 = r.sx * r.sy, a11 = r.cx, a12 = -r.sx * r.cy;
-    const float a20 = -r.cx * r.sy, a21 = r.sx, a22 = r.cx * r.cy;
-    r.R[0] = a00 * r.cz + a01 * r.sz; r.R[1] = -a00 * r.sz + a01 * r.cz; r.R[2] = a02;
-    r.R[3] = a10 * r.cz + a11 * r.sz; r.R[4] = -a10 * r.sz + a11 * r.cz; r.R[5] = a12;
-    r.R[6] = a20 * r.cz + a21 * r.sz; r.R[7] = -a20 * r.sz + a21 * r.cz; r.R[8] = a22;
-}
+using ccpose::Rot;
+using ccpose::euler;
 
 __global__ void k_pose_proj_fwd(const float* __restrict__ pose, long pose_stride, const float* __restrict__ K,
                                 float* __restrict__ P, int N, float kdiv) {

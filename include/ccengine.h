@@ -495,6 +495,37 @@ size_t cc_depth_errors_ws(int B, int H, int W);
 int cc_depth_errors(const float* gt, const float* pred, int B, int H, int W, int y1, int y2, int x1, int x2, float* out6, void* ws,
                     void* stream);
 
+/* ---------------------------------------------------------------- KITTI evaluation (kitti_eval/, test_disp.py, test_pose.py)
+ * Same contract as the validation metrics: no allocation, no host synchronisation, integer atomics only, fp64 partials reduced
+ * in a fixed order; `ws` is sized by the *_ws query and zeroed on the stream where needed.
+ *
+ * cc_velo_depth: generate_depth_map (depth_evaluation_utils.py:148-191) of N raw velodyne points [N,4] (the fourth value is
+ * ignored: 1) with P_velo2im [3,4] (device, fp64) -> depth [H,W] fp32: points with x >= 0 projected in double, u/z and v/z rounded
+ * half to even minus 1, kept inside the image; the last point in file order wins a pixel, then for every sub2ind key
+ * v*(W-1)+u-1 held by more than one point the pixel of its first point gets their minimum z; negative depths become 0.
+ * ws: cc_velo_depth_ws(H, W) bytes. */
+size_t cc_velo_depth_ws(int H, int W);
+int cc_velo_depth(const float* points, long N, const double* P_velo2im, float* depth, int H, int W, void* ws, void* stream);
+/* cc_spline_zoom: scipy.ndimage.zoom(src, (H/h, W/w)) with order 3, mode 'constant', cval 0, then .clip(lo, hi) (test_disp.py:125),
+ * for B images src [B,h,w] fp32 -> dst [B,H,W] fp32, bit-exact with SciPy (fp64 spline coefficients in ws, h, w, H, W >= 2).
+ * ws: cc_spline_zoom_ws(B, h, w) bytes. */
+size_t cc_spline_zoom_ws(int B, int h, int w);
+int cc_spline_zoom(const float* src, int B, int h, int w, float* dst, int H, int W, float lo, float hi, void* ws, void* stream);
+/* cc_eigen_errors: one image of test_disp.py:124-141: mask min_depth < gt < max_depth inside the Garg crop (generate_mask,
+ * depth_evaluation_utils.py:194-206), compute_errors (:171-187) of pred * scale -> out [2,7] fp64 = abs_rel, sq_rel, rms,
+ * log_rms, a1, a2, a3.  Row 1: scale = np.median(gt) / np.median(pred) over the mask (the mean of the middle pair for an even
+ * count).  Row 0: scale = mean(disp[r] / pose_norm[r] for disp[r] > 0), 0 without any, from the displacements [R] (fp64) and
+ * the norms of the pose network's translations [R] (fp32); both NULL: row 0 is 0.  ws: cc_eigen_errors_ws(H, W) bytes. */
+size_t cc_eigen_errors_ws(int H, int W);
+int cc_eigen_errors(const float* gt, const float* pred, int H, int W, double min_depth, double max_depth, const double* disp,
+                    const float* pose_norm, int R, double* out, void* ws, void* stream);
+/* cc_pose_snippet_errors: test_pose.py:69-91 and compute_pose_error (:107-122) for the S snippets of one sequence: pred [S,L-1,6]
+ * fp32 network poses (the zero pose goes in at L/2), gt_seq [F,3,4] fp64 raw sequence poses, snippet s covering frames
+ * first[s] + i*step, i < L (2 <= L <= 16).  rotation_mode 0: euler, 1: quat (pose_vec2mat in fp32, then fp64).
+ * -> err [S,2] fp64 = ATE / L, RE / L; final_or_null [S,L,3,4] fp64 the composed predicted poses. */
+int cc_pose_snippet_errors(const float* pred, const double* gt_seq, const int* first, int S, int L, int F, int step,
+                           int rotation_mode, double* err, double* final_or_null, void* stream);
+
 /* ---------------------------------------------------------------- optimizer (train.py:307-310,568)
  * torch.optim.Adam(betas, eps, weight_decay=0) on the flat fp32 bucket; grads are multiplied by grad_scale first
  * (1/world_size after the RCCL all-reduce).  step_dev: device float, incremented by the call. */
