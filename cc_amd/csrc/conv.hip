@@ -18,8 +18,7 @@
 // lane = pixel (coalesced along x) with a wave-uniform k so the (c,i,j) decode runs on the scalar unit.
 // Epilogue fuses bias, residual add, ReLU / LeakyReLU(0.2) / a*sigmoid+b.
 //
-// Weight gradient: second kernel, M = channels of dY, N = (c,i,j), K = pixels, split over pixel ranges with a
-// deterministic second-stage reduction (no atomics).
+// Weight gradients: conv_wgrad.hip (and the kernels it dispatches to); activation backward / bias gradients: conv_act.hip.
 #include <stdio.h>
 #include <stdlib.h>
 #include <stddef.h>
@@ -36,33 +35,28 @@
 
 // ---- per-kernel timing (measurement aid for bench.py's roofline line; off unless cc_timing_enable(1) was called on this
 // process; autograd runs the backward pass on its own threads): the MAIN device kernel of every conv / weight-gradient call is bracketed with HIP events on its own stream, so the
-// reported duration is the kernel's (what rocprofv3 --kernel-trace shows), not the C-ABI call's.
-namespace cctiming {
+// reported duration is the kernel's (what rocprofv3 --kernel-trace shows), not the C-ABI call's.  The registry lives here;
+// cctiming::Scope (conv_internal.h) is what the convolution units bracket their launches with.
 #ifdef CC_TOOLS
+namespace cctiming {
 struct Rec { std::string name; double gflop; hipEvent_t e0, e1; };
 static std::vector<Rec>* recs = nullptr;
 static std::mutex mtx;
-struct Scope {
-    hipEvent_t e1 = nullptr;
-    hipStream_t s;
-    Scope(const char* name, double gflop, hipStream_t st, bool active = true) : s(st) {
-        if (!recs || !active) return;
-        hipEvent_t e0 = nullptr;
-        (void)hipEventCreate(&e0);
-        (void)hipEventCreate(&e1);
-        {
-            std::lock_guard<std::mutex> lk(mtx);
-            if (!recs) return;
-            recs->push_back(Rec{name, gflop, e0, e1});
-        }
-        (void)hipEventRecord(e0, s);
+Scope::Scope(const char* name, double gflop, hipStream_t st, bool active) : s(st) {
+    if (!recs || !active) return;
+    hipEvent_t e0 = nullptr;
+    (void)hipEventCreate(&e0);
+    (void)hipEventCreate(&e1);
+    {
+        std::lock_guard<std::mutex> lk(mtx);
+        if (!recs) return;
+        recs->push_back(Rec{name, gflop, e0, e1});
     }
-    ~Scope() { if (e1) (void)hipEventRecord(e1, s); }
-};
-#else
-struct Scope { Scope(const char*, double, hipStream_t, bool = true) {} };      // product build: no registry, no events
-#endif
+    (void)hipEventRecord(e0, s);
+}
+Scope::~Scope() { if (e1) (void)hipEventRecord(e1, s); }
 }  // namespace cctiming
+#endif
 
 namespace {
 
@@ -76,8 +70,10 @@ inline int pick_bm_fwd(int M) {
     return M > 64 ? 128 : (M > 32 ? 64 : ((M > 16 || no16) ? 32 : 16));
 }
 
-constexpr int BN = 128;   // pixels per workgroup tile
-constexpr int BK = 16;    // reduction chunk
+using ccint::BK;
+using ccint::BN;
+using ccint::MAXGRP;
+using ccint::pick_bm;
 
 using namespace cctail;
 
@@ -908,7 +904,6 @@ __global__ __launch_bounds__(256) void k_splitk_epilogue_multi(EPM a) {
                                           c.add ? c.add[(long)n * c.add_bs + o] : 0.f);
 }
 
-static int dbg_flag_early(const char* name) { return cctools::env_flag(name); }
 
 struct ConvPlan {
     bool use_patch;
@@ -923,7 +918,6 @@ struct ConvPlan {
     size_t pad_floats;         // ... and size (behind the partial slabs in the workspace)
 };
 
-static int env_int_early(const char* name, int dflt) { return cctools::env_int(name, dflt); }
 
 // pixel tiles of a problem (grid.x of its launch): stacked tiny maps take one tile per ipt images
 inline long conv_tiles(const GG& g, const ConvPlan& p) { return (long)((g.B + p.ipt - 1) / p.ipt) * p.tiles_x * p.tiles_y; }
@@ -960,11 +954,11 @@ inline ConvPlan plan_conv(const GG& g, int mult = 1) {
         // always split-K: the partial slabs have the padded pitch, and the deterministic epilogue kernel that sums them writes the
         // real output.  Large layers only (the copy, 23 % empty tile columns and the forced second pass have to pay), never for the
         // grouped launches of parallel branches (they share one direct launch today).
-        if (!dbg_flag_early("CC_NO_WINO_PAD") && (g.IW % 4) != 0 && g.IH >= 2 && g.M >= env_int_early("CC_WINOP_MINM", 256) &&
-            g.Cin >= env_int_early("CC_WINOP_MINC", 256)) {
+        if (!cctools::env_flag("CC_NO_WINO_PAD") && (g.IW % 4) != 0 && g.IH >= 2 && g.M >= cctools::env_int("CC_WINOP_MINM", 256) &&
+            g.Cin >= cctools::env_int("CC_WINOP_MINC", 256)) {
             int wp = (g.IW + 3) & ~3;
             while (!(wp / 2 >= 16 || wp / 2 == 8)) wp += 4;
-            if (4 * (wp - g.IW) <= wp && (long)g.B * ((g.IH + 1) / 2) * (wp / 2) >= env_int_early("CC_WINOP_MINQ", 64)) {
+            if (4 * (wp - g.IW) <= wp && (long)g.B * ((g.IH + 1) / 2) * (wp / 2) >= cctools::env_int("CC_WINOP_MINQ", 64)) {
                 ccint::WinoPlan wq = ccint::wino_plan(g.B, g.Cin, g.IH, wp, g.M, mult);
                 if (wq.ok) {
                     if (wq.nsplit < 2) {                    // the epilogue pass is what un-pads the output
@@ -995,7 +989,7 @@ inline ConvPlan plan_conv(const GG& g, int mult = 1) {
     {   // a narrower channel tile when it saves >= 25 % of the PADDED output channels: M = 65 / 96 -> 3 x 32 instead of 128,
         // 129 -> 3 x 64 instead of 256, 260 -> 9 x 32 instead of 384 (concatenations with a 1-2 channel map, the 96-channel
         // decoder layers): -0.33 ms/step (r3s3 A/B; thresholds 12-25 % equal, 35 % loses it)
-        const int thr = env_int_early("CC_CONV_BM_PADSAVE", 25);
+        const int thr = cctools::env_int("CC_CONV_BM_PADSAVE", 25);
         if (thr > 0 && p.bm > 32) {
             const int cur = ((g.M + p.bm - 1) / p.bm) * p.bm;
             for (int b2 = p.bm / 2; b2 >= 32; b2 /= 2) {
@@ -1008,13 +1002,13 @@ inline ConvPlan plan_conv(const GG& g, int mult = 1) {
         const long a32 = (long)((g.OWt + 31) / 32) * 32 * (((g.OHt + 3) / 4) * 4);
         const long a16 = (long)((g.OWt + 15) / 16) * 16 * (((g.OHt + 7) / 8) * 8);
         // ties (all maps of <= 16x52: both shapes pad them equally) go to 8 x 16: -0.07 ms/step (r3s3)
-        p.tw16 = ((a16 < a32 || (a16 == a32 && env_int_early("CC_CONV_TW16_TIES", 1))) && !dbg_flag_early("CC_CONV_NO_TW16")) ? 1 : 0;
+        p.tw16 = ((a16 < a32 || (a16 == a32 && cctools::env_int("CC_CONV_TW16_TIES", 1))) && !cctools::env_flag("CC_CONV_NO_TW16")) ? 1 : 0;
     }
     // Maps of <= 4 lattice rows (DispResNet6's 4x13 / 2x7 / 1x4 levels and their parity classes): one image fills 1-4 of the 8 tile
     // rows and the matrix cores multiply padding (a 2x7 map: 14 live pixels of 128).  The 8 x 16 tile then stacks the rows of
     // 8 / OHt consecutive images, each with its own halo rows in the patch.
     p.ipt = 1;
-    if (g.OHt <= 4 && g.B >= 2 && env_int_early("CC_CONV_STACK", 1) && !dbg_flag_early("CC_CONV_CK16")) {
+    if (g.OHt <= 4 && g.B >= 2 && cctools::env_int("CC_CONV_STACK", 1) && !cctools::env_flag("CC_CONV_CK16")) {
         p.tw16 = 1;
         p.ipt = 8 / g.OHt < g.B ? 8 / g.OHt : g.B;
     }
@@ -1022,9 +1016,9 @@ inline ConvPlan plan_conv(const GG& g, int mult = 1) {
     {   // few pixel tiles: shrink the channel tile (more workgroups, every one over the whole reduction) before resorting to
         // split-K (partial slabs + an epilogue launch); CC_CONV_BM_MINBLOCKS: block count below which the tile is halved
         const long tiles = (long)g.B * ((g.OWt + tw - 1) / tw) * ((g.OHt + th - 1) / th);
-        const int thr = env_int_early("CC_CONV_BM64_BELOW", 0);
+        const int thr = cctools::env_int("CC_CONV_BM64_BELOW", 0);
         if (p.bm == 128 && tiles * ((g.M + 127) / 128) < thr) p.bm = 64;
-        const int minb = env_int_early("CC_CONV_BM_MINBLOCKS", 0);
+        const int minb = cctools::env_int("CC_CONV_BM_MINBLOCKS", 0);
         while (p.bm > 32 && tiles * ((g.M + p.bm - 1) / p.bm) < minb) p.bm /= 2;
     }
     const int ylast = g.dy0 + (g.Rt - 1) * g.dstep, xlast = g.dx0 + (g.St - 1) * g.dstep;
@@ -1039,7 +1033,7 @@ inline ConvPlan plan_conv(const GG& g, int mult = 1) {
     }
     p.PWr = (tw - 1) * g.si + (xmax - p.xmin) + 1;
     // 16-byte aligned variant: start every patch row at the 4-float boundary at or below its first column
-    p.aligned = (g.IW % 4 == 0) && !dbg_flag_early("CC_NO_ALIGNED_PATCH");
+    p.aligned = (g.IW % 4 == 0) && !cctools::env_flag("CC_NO_ALIGNED_PATCH");
     p.shift = 0;
     if (p.aligned) {
         p.shift = ((p.xmin % 4) + 4) % 4;                  // si * tx0 is a multiple of 4
@@ -1052,9 +1046,9 @@ inline ConvPlan plan_conv(const GG& g, int mult = 1) {
     // CC_CONV_CK16=1 restores the round-1 plan (16 wherever one stage fits in 64 KB).
     p.ck = 8;
     auto smem_of = [&](int ck, int tps) { return (size_t)(2 * tps * ck * p.bm + 2 * ck * p.PS) * sizeof(float); };
-    if (dbg_flag_early("CC_CONV_CK16") && smem_of(16, 1) <= 64 * 1024) p.ck = 16;
+    if (cctools::env_flag("CC_CONV_CK16") && smem_of(16, 1) <= 64 * 1024) p.ck = 16;
     // three taps per pipeline stage when the extra weight buffers still leave two workgroups per CU (2 x 80 KB)
-    p.tps = (g.Rt * g.St >= 3 && smem_of(p.ck, 3) <= 80 * 1024 && !dbg_flag_early("CC_CONV_TPS1")) ? 3 : 1;
+    p.tps = (g.Rt * g.St >= 3 && smem_of(p.ck, 3) <= 80 * 1024 && !cctools::env_flag("CC_CONV_TPS1")) ? 3 : 1;
     p.smem = smem_of(p.ck, p.tps);
     if (p.bm >= 32 && p.smem < 16384) p.smem = 16384;        // the epilogue transposes one 32x32 tile per wave through LDS
     p.use_patch = (p.smem <= 150 * 1024) && g.Cin > 0;
@@ -1067,10 +1061,10 @@ inline ConvPlan plan_conv(const GG& g, int mult = 1) {
     const int nchunk = p.Cpad / p.ck;
     p.nsplit = 1;
     p.cps = nchunk;
-    if (blocks < env_int_early("CC_CONV_SPLIT_BELOW", 384) && nchunk >= 4 && !(g.so != 1 && dbg_flag_early("CC_DBG_NO_PARITY_SPLIT"))) {
-        long want = (env_int_early("CC_CONV_SPLIT_TARGET", 512) + blocks - 1) / blocks;
-        if (want > nchunk / env_int_early("CC_CONV_MINCHUNKS", 1)) want = nchunk / env_int_early("CC_CONV_MINCHUNKS", 1);
-        if (want > env_int_early("CC_CONV_MAXSPLIT", 32)) want = env_int_early("CC_CONV_MAXSPLIT", 32);
+    if (blocks < cctools::env_int("CC_CONV_SPLIT_BELOW", 384) && nchunk >= 4 && !(g.so != 1 && cctools::env_flag("CC_DBG_NO_PARITY_SPLIT"))) {
+        long want = (cctools::env_int("CC_CONV_SPLIT_TARGET", 512) + blocks - 1) / blocks;
+        if (want > nchunk / cctools::env_int("CC_CONV_MINCHUNKS", 1)) want = nchunk / cctools::env_int("CC_CONV_MINCHUNKS", 1);
+        if (want > cctools::env_int("CC_CONV_MAXSPLIT", 32)) want = cctools::env_int("CC_CONV_MAXSPLIT", 32);
         if (want >= 2) {
             p.cps = (int)((nchunk + want - 1) / want);
             p.nsplit = (nchunk + p.cps - 1) / p.cps;
@@ -1111,665 +1105,6 @@ inline ConvPlan plan_conv(const GG& g, int mult = 1) {
 }
 
 inline size_t conv_ws_floats(const ConvPlan& p) { return 64 + p.wp_floats + p.part_floats + p.pad_floats; }
-
-// ------------------------------------------------------------------ weight gradient
-constexpr int MAXGRP = 4;       // same-shaped weight-gradient problems per launch (parallel branches of a network)
-struct WG {
-    const float* a;   // "dY-like" tensor [B, M, AH, AW] (batch stride a_bs), sampled on the full lattice (ty, tx)
-    const float* x;   // gathered tensor [B, Cin, IH, IW]
-    float* out;       // partial tiles ws[split][M][N] (or the final gradient when nsplit == 1 -> strided store)
-    const float* ga[MAXGRP]; const float* gxp[MAXGRP]; float* gout[MAXGRP];   // per-problem pointers (blockIdx.z / nsplit)
-    int nsplit;
-    int B, M, AH, AW; long a_bs;
-    int Cin, IH, IW; long x_bs;
-    int Rt, St, dy0, dx0, dstep, si;
-    long o_sm, o_sc; int o_ri, o_sj;     // gradient strides (used when direct == 1)
-    int direct, accum;
-    int pix_per_split;
-};
-
-template <int BM>
-__device__ __forceinline__ void wgrad_body(const WG& g, const int bx_, const int by_, const int bz_) {
-    const int grp = bz_ / g.nsplit, zsplit = bz_ - grp * g.nsplit;
-    const float* __restrict__ a_ = g.ga[grp];
-    const float* __restrict__ x_ = g.gxp[grp];
-    float* __restrict__ out_ = g.gout[grp];
-    constexpr int WM = (BM >= 64) ? BM / 2 : 32;
-    constexpr int WN = (BM >= 64) ? 64 : 32;
-    constexpr int TM = WM / 32, TN = WN / 32;
-    constexpr int AP = BM + 4, BP = BN + 4;
-    constexpr int AQ = BM / 16;
-    __shared__ float As[2][BK * AP];   // As[pp][m]
-    __shared__ float Bs[2][BK * BP];   // Bs[pp][jn]
-
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = (BM >= 64) ? (wid >> 1) : 0;
-    const int wn = (BM >= 64) ? (wid & 1) : wid;
-    const int m0 = by_ * BM;
-    const int n0 = bx_ * BN;
-    const int RS = g.Rt * g.St;
-    const int Ntot = g.Cin * RS;
-    const int HWa = g.AH * g.AW;
-    const long Ptot = (long)g.B * HWa;
-    const long pbeg = (long)zsplit * g.pix_per_split;
-    long pend = pbeg + g.pix_per_split;
-    if (pend > Ptot) pend = Ptot;
-    const int x_cs = g.IH * g.IW;
-
-    // loader roles: pp = tid & 15 (pixel within the chunk), row group = tid >> 4 (16 groups)
-    const int pp = tid & 15, rgp = tid >> 4;
-    // B columns handled by this thread: jn = rgp + 16*q  -> constant over the pixel loop
-    int xoff[8], tdy[8], tdx[8];
-#pragma unroll
-    for (int q = 0; q < 8; q++) {
-        const int jn = n0 + rgp + 16 * q;
-        if (jn < Ntot) {
-            const int c = jn / RS, rem = jn - c * RS;
-            const int i = rem / g.St, j = rem - i * g.St;
-            tdy[q] = g.dy0 + i * g.dstep;
-            tdx[q] = g.dx0 + j * g.dstep;
-            xoff[q] = c * x_cs + tdy[q] * g.IW + tdx[q];
-        } else {
-            tdy[q] = -(1 << 28);
-            tdx[q] = 0;
-            xoff[q] = 0;
-        }
-    }
-    float ra[AQ], rb[8];
-    unsigned okA = 0, okB = 0;
-    // branch-free loads: invalid elements read element 0 of their tensor and are zeroed by a select AT STORE TIME
-    // (hipcc otherwise wraps every predicated load in its own s_cbranch_execz block; and a select placed right after
-    // the load would force s_waitcnt vmcnt(0) ahead of the MFMAs of the current chunk)
-    auto load_chunk = [&](long pbase) {
-        okA = 0;
-        okB = 0;
-        const long p = pbase + pp;
-        const bool pv = p < pend;
-        const long ps = pv ? p : 0;
-        const int n = (int)(ps / HWa);
-        const int t = (int)(ps - (long)n * HWa);
-        const int ty = t / g.AW, tx = t - ty * g.AW;
-        const long abase = (long)n * g.a_bs + ty * g.AW + tx;
-#pragma unroll
-        for (int q = 0; q < AQ; q++) {
-            const int m = m0 + rgp + 16 * q;
-            const bool ok = pv && (m < g.M);
-            ra[q] = a_[ok ? abase + (long)m * HWa : 0];
-            okA |= (ok ? 1u : 0u) << q;
-        }
-        const int iy0 = g.si * ty, ix0 = g.si * tx;
-        const long xb = (long)n * g.x_bs + (long)iy0 * g.IW + ix0;
-#pragma unroll
-        for (int q = 0; q < 8; q++) {
-            const int iy = iy0 + tdy[q], ix = ix0 + tdx[q];
-            const bool ok = pv && ((unsigned)iy < (unsigned)g.IH) && ((unsigned)ix < (unsigned)g.IW);
-            rb[q] = x_[ok ? xb + xoff[q] : 0];
-            okB |= (ok ? 1u : 0u) << q;
-        }
-    };
-    auto store_chunk = [&](int buf) {
-#pragma unroll
-        for (int q = 0; q < AQ; q++) As[buf][pp * AP + rgp + 16 * q] = ((okA >> q) & 1u) ? ra[q] : 0.f;
-#pragma unroll
-        for (int q = 0; q < 8; q++) Bs[buf][pp * BP + rgp + 16 * q] = ((okB >> q) & 1u) ? rb[q] : 0.f;
-    };
-
-    f32x16 acc[TM][TN];
-#pragma unroll
-    for (int a = 0; a < TM; a++)
-#pragma unroll
-        for (int b = 0; b < TN; b++)
-#pragma unroll
-            for (int r = 0; r < 16; r++) acc[a][b][r] = 0.f;
-
-    const int l31 = lane & 31, lk = lane >> 5;
-    const long nchunks = (pend > pbeg) ? (pend - pbeg + BK - 1) / BK : 0;
-    if (nchunks > 0) {
-        load_chunk(pbeg);
-        store_chunk(0);
-    }
-    __syncthreads();
-    for (long ch = 0; ch < nchunks; ch++) {
-        const int buf = (int)(ch & 1);
-        if (ch + 1 < nchunks) load_chunk(pbeg + (ch + 1) * BK);
-        {
-            float af[BK / 2][TM], bf[BK / 2][TN];
-#pragma unroll
-            for (int ks = 0; ks < BK / 2; ks++) {
-#pragma unroll
-                for (int a = 0; a < TM; a++) af[ks][a] = As[buf][(2 * ks + lk) * AP + wm * WM + a * 32 + l31];
-#pragma unroll
-                for (int b = 0; b < TN; b++) bf[ks][b] = Bs[buf][(2 * ks + lk) * BP + wn * WN + b * 32 + l31];
-            }
-#pragma unroll
-            for (int ks = 0; ks < BK / 2; ks++)
-#pragma unroll
-                for (int a = 0; a < TM; a++)
-#pragma unroll
-                    for (int b = 0; b < TN; b++)
-                        acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[ks][a], bf[ks][b], acc[a][b], 0, 0, 0);
-        }
-        if (ch + 1 < nchunks) store_chunk(buf ^ 1);
-        __syncthreads();
-    }
-    // epilogue: D col = lane&31 -> (c,i,j) column, row -> channel m
-#pragma unroll
-    for (int b = 0; b < TN; b++) {
-        const int jn = n0 + wn * WN + b * 32 + l31;
-        if (jn >= Ntot) continue;
-        long obase;
-        if (g.direct) {
-            const int c = jn / RS, rem = jn - c * RS;
-            const int i = rem / g.St, j = rem - i * g.St;
-            obase = (long)c * g.o_sc + i * g.o_ri + j * g.o_sj;
-        } else {
-            obase = (long)zsplit * g.M * Ntot + jn;
-        }
-#pragma unroll
-        for (int a = 0; a < TM; a++)
-#pragma unroll
-            for (int r = 0; r < 16; r++) {
-                const int m = m0 + wm * WM + a * 32 + (r & 3) + 8 * (r >> 2) + 4 * lk;
-                if (m < g.M) {
-                    float* o = out_ + obase + (g.direct ? (long)m * g.o_sm : (long)m * Ntot);
-                    *o = (g.direct && g.accum) ? (*o + acc[a][b][r]) : acc[a][b][r];
-                }
-            }
-    }
-}
-
-template <int BM>
-__global__ __launch_bounds__(256) void k_wgrad(WG g) {
-    if constexpr (CC_XCD_MASK & 4) {
-        // XCD order (cc_common.h) over the flattened grid, x fastest: the tiles of one (problem, pixel range) -- which gather the same
-        // slices of dY and x -- run on one XCD
-        const int gx = (int)gridDim.x, gy = (int)gridDim.y;
-        const int b = cc_xcd_order((int)blockIdx.x + gx * ((int)blockIdx.y + gy * (int)blockIdx.z), gx * gy * (int)gridDim.z);
-        const int r = b / gx;
-        wgrad_body<BM>(g, b - r * gx, r % gy, r / gy);
-    } else {
-        wgrad_body<BM>(g, (int)blockIdx.x, (int)blockIdx.y, (int)blockIdx.z);
-    }
-}
-
-// Problems of DIFFERENT shapes in one launch (the single-layer weight gradients a backward stage leaves parked until its end -- the
-// stride-2 / 1x1 / small-map layers: 15-40 us launches of 30-600 workgroups each, mostly ramp-up and drain; cc_conv2d_wgrad_list).
-// blockIdx.x ranges over the classes' grids back to back; a class's grid is flattened x-fastest.
-constexpr int MAXWCLS = 12;
-struct WGM { WG c[MAXWCLS]; int n; int bx_end[MAXWCLS]; int gx[MAXWCLS], gy[MAXWCLS]; };
-template <int BM>
-__global__ __launch_bounds__(256) void k_wgrad_multi(WGM a) {
-    int k = 0, first = 0, end = a.bx_end[0];
-#pragma unroll
-    for (int q = 0; q < MAXWCLS - 1; q++)
-        if (q + 1 < a.n && (int)blockIdx.x >= a.bx_end[q]) { k = q + 1; first = a.bx_end[q]; end = a.bx_end[q + 1]; }
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(CC_HIPEMU)
-    const WG& g = *(reinterpret_cast<const WG*>((const char*)__builtin_amdgcn_kernarg_segment_ptr() + offsetof(WGM, c)) + k);
-#else
-    const WG& g = a.c[k];
-#endif
-    const int b = (CC_XCD_MASK & 4) ? cc_xcd_order((int)blockIdx.x - first, end - first) : (int)blockIdx.x - first;      // (as k_wgrad)
-    const int gx = a.gx[k], gy = a.gy[k];
-    const int bx = b % gx, r = b / gx;
-    wgrad_body<BM>(g, bx, r % gy, r / gy);
-}
-
-// ------------------------------------------------------------------ weight gradient, patch-staged (main path)
-// gw[m][c][i][j] = sum_{n,ty,tx} a[n][m][ty][tx] * x[n][c][si*ty + i - pad][si*tx + j - pad] as ONE GEMM PER TAP:
-//   D_t[m][c] += A[m][pixel] * X_t[pixel][c],  X_t = the input patch shifted by tap t (never materialised).
-// Workgroup = (BMW rows of dY) x (32 input channels) x (a group of <= TG taps), looping over 2 x 32 pixel tiles of
-// its split; per tile dY (pixel-minor, row stride 65) and the 32-channel input patch (channel stride odd) are
-// LDS-DMA'd, both MFMA operands are then conflict-free strided ds_reads (lane = m resp. lane = channel, k = pixel).
-// Every MFMA is useful work (no im2col padding); accumulators: one 32x32 tile per (m-tile, tap), spread over the 4 waves.
-constexpr int WTH = 2;          // lattice rows per pixel tile
-constexpr int WPIX = WTH * 32;  // 64 pixels = 32 MFMA k-steps
-constexpr int APS = WPIX + 1;   // dY row stride in LDS (odd -> bank = (m + p) mod 32)
-
-struct WP {
-    const float* a; const float* x; const float* zeros; float* ws;
-    int B, M, AH, AW; long a_bs;
-    int Cin, IH, IW; long x_bs;
-    int R, S, si, pad;
-    int PH, PWr, PSc, npos;
-    int tiles_x, tiles_y, ntiles, tiles_per_split, nsplit;
-    int TG, ngroups, Cp32, nbuf;
-    int dbg;   // ablation switches (CC_WGRAD_DBG): 1 = skip the per-tile LDS-DMA, 2 = skip the MFMAs
-};
-
-// Wave specialisation: waves 0-3 only read LDS and issue MFMAs, waves 4-5 only issue the LDS-DMA of the NEXT pixel
-// tile (their ~20-instruction address chains would otherwise sit in front of the MFMAs of an in-order wave).
-constexpr int WG_THREADS = 384;
-
-template <int BMW, int NT>
-__global__ __launch_bounds__(384) void k_wgrad_patch(WP g) {
-    constexpr int MT = BMW / 32;
-    HIP_DYNAMIC_SHARED(float, smem)
-    const int a_sz = BMW * APS, p_sz = 32 * g.PSc;
-    float* As = smem;                         // [nbuf][BMW][APS]
-    float* Ps = smem + g.nbuf * a_sz;         // [nbuf][32][PSc]
-
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int l31 = lane & 31, lk = lane >> 5;
-    // blockIdx.x -> (m-tile, c-tile, tap group)
-    int bx = blockIdx.x;
-    const int grp = bx % g.ngroups;
-    bx /= g.ngroups;
-    const int ctile = bx % (g.Cp32 / 32);
-    const int mtile = bx / (g.Cp32 / 32);
-    const int m0 = mtile * BMW, c0 = ctile * 32;
-    const int t_first = grp * g.TG;
-    const int T = g.R * g.S;
-    int ntap = T - t_first;
-    if (ntap > g.TG) ntap = g.TG;
-    const int x_cs = g.IH * g.IW, a_cs = g.AH * g.AW;
-    const int pt_beg = blockIdx.z * g.tiles_per_split;
-    int pt_end = pt_beg + g.tiles_per_split;
-    if (pt_end > g.ntiles) pt_end = g.ntiles;
-    const int RI = (g.npos + 63) >> 6;
-
-    const bool loader = wid >= 4;
-    const int lw = wid - 4;                    // loader wave index (0/1)
-    // accumulator tiles of this wave: q = wid + 4*k -> (mt = q % MT, tap = q / MT)
-    int my_mt[NT], my_tap[NT];
-    f32x16 acc[NT];
-#pragma unroll
-    for (int k = 0; k < NT; k++) {
-        const int q = (wid & 3) + 4 * k;
-        my_mt[k] = q % MT;
-        my_tap[k] = q / MT;
-#pragma unroll
-        for (int r = 0; r < 16; r++) acc[k][r] = 0.f;
-    }
-
-    auto load_tile = [&](int pt, int buf) {
-        const int tile_x = pt % g.tiles_x;
-        const int r2 = pt / g.tiles_x;
-        const int tile_y = r2 % g.tiles_y;
-        const int n = r2 / g.tiles_y;
-        const int ty0 = tile_y * WTH, tx0 = tile_x * 32;
-        // dY rows: one LDS-DMA per channel m (64 pixels = 2 lattice rows of 32)
-        {
-            const int ty = ty0 + lk, tx = tx0 + l31;
-            const bool ok = (ty < g.AH) && (tx < g.AW);
-            const float* an = g.a + (long)n * g.a_bs + (long)ty * g.AW + tx;
-            float* dst = As + buf * a_sz;
-            for (int mm = lw; mm < BMW; mm += 2) {
-                const int m = m0 + mm;
-                const float* src = (ok && m < g.M) ? an + (long)m * a_cs : g.zeros + lane;
-                __builtin_amdgcn_global_load_lds(CC_GLOBAL_PTR(src), CC_LDS_PTR(dst + mm * APS), 4, 0, 0);
-            }
-        }
-        // input patch of 32 channels: positions pos = py*PWr + px, py < PH
-        {
-            const int gy0 = g.si * ty0 - g.pad, gx0 = g.si * tx0 - g.pad;
-            const float* xn = g.x + (long)n * g.x_bs;
-            float* dst = Ps + buf * p_sz;
-            for (int r = 0; r < RI; r++) {
-                const int pos = lane + 64 * r;
-                const int py = pos / g.PWr, px = pos - py * g.PWr;
-                const int iy = gy0 + py, ix = gx0 + px;
-                const bool inb = ((unsigned)iy < (unsigned)g.IH) && ((unsigned)ix < (unsigned)g.IW);
-                const long go = (long)iy * g.IW + ix;
-                if (pos < g.npos) {                 // lanes past the patch stay out of the DMA (EXEC-masked)
-                    for (int cc = lw; cc < 32; cc += 2) {
-                        const int c = c0 + cc;
-                        const float* src = (inb && c < g.Cin) ? xn + (long)c * x_cs + go : g.zeros + lane;
-                        __builtin_amdgcn_global_load_lds(CC_GLOBAL_PTR(src), CC_LDS_PTR(dst + cc * g.PSc + 64 * r), 4, 0, 0);
-                    }
-                }
-            }
-        }
-    };
-
-    if (pt_beg < pt_end) {
-        if (loader) {
-            load_tile(pt_beg, 0);
-            CC_WAIT_VMCNT0();
-        }
-        __syncthreads();
-        for (int pt = pt_beg; pt < pt_end; pt++) {
-            const int buf = (g.nbuf == 2) ? ((pt - pt_beg) & 1) : 0;
-            if (loader) {
-                if (g.nbuf == 2 && pt + 1 < pt_end && !(g.dbg & 1)) {
-                    load_tile(pt + 1, buf ^ 1);
-                    CC_WAIT_VMCNT0();
-                }
-            } else if (!(g.dbg & 2)) {
-                const float* Ab = As + buf * a_sz + l31 * APS + lk;          // lane = m row, k = pixel
-                const float* Pb = Ps + buf * p_sz + l31 * g.PSc + g.si * lk; // lane = channel
-                // branch-free inner loop: every accumulator slot multiplies (slots past the tap group re-do its last
-                // tap and are dropped in the epilogue), all operands of a k-step are fetched before its MFMAs
-                int toff[NT];
-#pragma unroll
-                for (int k = 0; k < NT; k++) {
-                    const int tt = my_tap[k] < ntap ? my_tap[k] : ntap - 1;
-                    const int t = t_first + tt;
-                    const int i = t / g.S, j = t - i * g.S;
-                    toff[k] = i * g.PWr + j;
-                }
-#pragma unroll
-                for (int row = 0; row < WTH; row++) {
-                    const float* Ar = Ab + row * 32;
-                    const float* Pr = Pb + (g.si * row) * g.PWr;
-#pragma unroll 4
-                    for (int ks = 0; ks < 16; ks++) {
-                        float af[MT], bv[NT];
-#pragma unroll
-                        for (int a = 0; a < MT; a++) af[a] = Ar[a * 32 * APS + 2 * ks];
-#pragma unroll
-                        for (int k = 0; k < NT; k++) bv[k] = Pr[(2 * g.si) * ks + toff[k]];
-#pragma unroll
-                        for (int k = 0; k < NT; k++) {
-                            const float av = (MT == 1) ? af[0] : (my_mt[k] ? af[MT - 1] : af[0]);   // no runtime register indexing
-                            acc[k] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv[k], acc[k], 0, 0, 0);
-                        }
-                    }
-                }
-            }
-            if (g.nbuf == 1) {
-                __syncthreads();
-                if (loader && pt + 1 < pt_end) {
-                    load_tile(pt + 1, 0);
-                    CC_WAIT_VMCNT0();
-                }
-            }
-            __syncthreads();
-        }
-    }
-    if (loader) return;
-    // partial slabs: ws[split][t][m][c]  (c contiguous: D col = lane&31 = channel -> coalesced)
-#pragma unroll
-    for (int k = 0; k < NT; k++) {
-        if (my_tap[k] >= ntap) continue;
-        const int t = t_first + my_tap[k];
-        float* o = g.ws + (((long)blockIdx.z * T + t) * g.M) * g.Cp32 + c0 + l31;
-#pragma unroll
-        for (int r = 0; r < 16; r++) {
-            const int m = m0 + my_mt[k] * 32 + (r & 3) + 8 * (r >> 2) + 4 * lk;
-            if (m < g.M) o[(long)m * g.Cp32] = acc[k][r];
-        }
-    }
-}
-
-// ------------------------------------------------------------------ weight gradient of 3x3 / stride 1 / pad 1 convs (main path)
-// The layers that carry ~85 % of the step's weight-gradient FLOPs.  Same per-tap GEMM as k_wgrad_patch
-//   D_(i,j)[m][c] += dY[m][pixel] * X[c][pixel + (i-1, j-1)]
-// but every byte moves by 16-byte LDS-DMA (4x fewer DMA instructions -- the dword form is issue-bound, measured) and
-// every MFMA operand comes from a conflict-free ds_read_b128:
-//   * dY tile [BM m][2 x 32 px] as 16-byte chunks, XOR-swizzled by (m & 15) through the SOURCE address of the DMA
-//     (LDS image stays lane-linear); a chunk = 4 pixels = the A operand of two k-steps (lane>>5 picks the pixel);
-//   * input patch [32 c][4 rows][40 cols] (cols tx0-4 .. tx0+35: 16-byte aligned in global memory), channel stride 41
-//     chunks (odd -> 16 consecutive channels hit 16 different bank quads); three chunks of one patch row hold the B
-//     operands of the 3 taps of that row for 4 pixels;
-//   * one wave per (tap row i, 32-row m tile): 3 accumulator tiles, 4 ds_read_b128 per 6 MFMAs.
-constexpr int W3_PC = 41;       // chunks per channel in the patch (40 used + 1 pad)
-
-struct W3 {
-    const float* a; const float* x; const float* zeros; float* ws;
-    const float* ga[MAXGRP]; const float* gxp[MAXGRP]; float* gws[MAXGRP];      // per-problem pointers (blockIdx.y)
-    int B, M, AH, AW; long a_bs;
-    int Cin; long x_bs;
-    int tiles_x, tiles_y, ntiles, tiles_per_split, nsplit, Cpad, dbg;
-};
-
-// Workgroup = 4 waves (a 3- or 6-wave workgroup lands 2+2+1+1 on the SIMDs and caps at 75 % of the MFMA rate:
-// tools/mfma_probe.hip measures 116 vs 155 TFLOP/s).  It covers MT m-tiles x CT channel-tiles (MT*CT = 4) x 3 tap rows
-// = 12 (tap row, tile) groups, three per wave = 9 accumulators; every k-step pair costs 4 ds_read_b128 per 12 MFMAs.
-template <int MT, int CT>
-__global__ __launch_bounds__(256, 2) void k_wgrad3x3(W3 g) {
-    const float* __restrict__ a_ = g.ga[blockIdx.y];
-    const float* __restrict__ x_ = g.gxp[blockIdx.y];
-    float* __restrict__ ws_ = g.gws[blockIdx.y];
-    constexpr int BM = 32 * MT, BC = 32 * CT;
-    constexpr int A_SLOTS = BM * 16;                           // 16-byte slots of the dY tile
-    constexpr int P_SLOTS = ((BC * W3_PC + 63) / 64) * 64;     // rounded up so that every DMA instruction runs all 64 lanes
-    HIP_DYNAMIC_SHARED(float, smem)
-    float4* As = reinterpret_cast<float4*>(smem);              // [A_SLOTS]
-    float4* Ps = reinterpret_cast<float4*>(smem) + A_SLOTS;    // [P_SLOTS]
-
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int l31 = lane & 31, lk = lane >> 5;
-    const int ctiles = g.Cpad / BC;
-    const int ctile = blockIdx.x % ctiles, mtile = blockIdx.x / ctiles;
-    const int m0 = mtile * BM, c0 = ctile * BC;
-    const int HW = g.AH * g.AW;
-    const int pt_beg = blockIdx.z * g.tiles_per_split;
-    int pt_end = pt_beg + g.tiles_per_split;
-    if (pt_end > g.ntiles) pt_end = g.ntiles;
-
-    // this wave's three groups: gidx = wid + 4k -> tap row gidx % 3, tile gidx / 3 -> (mt, ct)
-    int g_row[3], g_mt[3], g_ct[3];
-    f32x16 acc[3][3];
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-        const int gi = wid + 4 * k;
-        g_row[k] = gi % 3;
-        const int tl = gi / 3;
-        g_mt[k] = tl % MT;
-        g_ct[k] = tl / MT;
-#pragma unroll
-        for (int j = 0; j < 3; j++)
-#pragma unroll
-            for (int r = 0; r < 16; r++) acc[k][j][r] = 0.f;
-    }
-
-    auto load_tile = [&](int pt) {
-        const int tile_x = pt % g.tiles_x;
-        const int r2 = pt / g.tiles_x;
-        const int tile_y = r2 % g.tiles_y;
-        const int n = r2 / g.tiles_y;
-        const int ty0 = tile_y * 2, tx0 = tile_x * 32;
-        // dY: LDS slot s = m*16 + sc holds pixel chunk pc = sc ^ (m & 15) of row m  (pc = row*8 + col4)
-        for (int s0 = wid * 64; s0 < A_SLOTS; s0 += 256) {
-            const int sl = s0 + lane;
-            const int mm = sl >> 4, sc = sl & 15;
-            const int pc = sc ^ (mm & 15);
-            const int ty = ty0 + (pc >> 3), tx = tx0 + 4 * (pc & 7);
-            const int m = m0 + mm;
-            const bool ok = (m < g.M) && (ty < g.AH) && (tx < g.AW);
-            const float* src = ok ? a_ + (long)n * g.a_bs + (long)m * HW + (long)ty * g.AW + tx : g.zeros;
-            __builtin_amdgcn_global_load_lds(CC_GLOBAL_PTR(src), CC_LDS_PTR(As + s0), 16, 0, 0);
-        }
-        // patch: LDS slot s = c*41 + r, r = py*10 + ch (r == 40: pad)
-        for (int s0 = wid * 64; s0 < P_SLOTS; s0 += 256) {
-            const int sl = s0 + lane;
-            const int cc = sl / W3_PC, r = sl - cc * W3_PC;
-            const int py = r / 10, ch = r - py * 10;
-            const int iy = ty0 - 1 + py, ix = tx0 - 4 + 4 * ch;
-            const int c = c0 + cc;
-            const bool ok = (cc < BC) && (r < 40) && (c < g.Cin) && ((unsigned)iy < (unsigned)g.AH) && ((unsigned)ix < (unsigned)g.AW);
-            const float* src = ok ? x_ + (long)n * g.x_bs + (long)c * HW + (long)iy * g.AW + ix : g.zeros;
-            __builtin_amdgcn_global_load_lds(CC_GLOBAL_PTR(src), CC_LDS_PTR(Ps + s0), 16, 0, 0);
-        }
-    };
-
-    for (int pt = pt_beg; pt < pt_end; pt++) {
-        if (pt > pt_beg) __syncthreads();                                 // everyone is done reading the previous tile
-        if (!(g.dbg & 1) || pt == pt_beg) load_tile(pt);
-        CC_WAIT_VMCNT0();
-        __syncthreads();
-        // MFMA k index (lane>>5) <-> the two HALVES of a 32-pixel row: lanes 0-31 take pixel chunk pq, lanes 32-63 chunk
-        // pq+4, each through its own ds_read_b128 address -> element e of every chunk feeds MFMA e directly
-        if (g.dbg & 2) continue;
-#pragma unroll
-        for (int row = 0; row < 2; row++) {
-#pragma unroll 2
-            for (int pq = 0; pq < 4; pq++) {
-#pragma unroll
-                for (int k = 0; k < 3; k++) {
-                    const int mrow = g_mt[k] * 32 + l31;
-                    float4 av = As[mrow * 16 + ((row * 8 + pq + 4 * lk) ^ (mrow & 15))];
-                    const float4* Pr = Ps + (g_ct[k] * 32 + l31) * W3_PC + (row + g_row[k]) * 10 + 4 * lk + pq;
-                    float4 w0 = Pr[0], w1 = Pr[1], w2 = Pr[2];
-                    CC_KEEP4(av); CC_KEEP4(w0); CC_KEEP4(w1); CC_KEEP4(w2);
-                    const float a[4] = {av.x, av.y, av.z, av.w};
-                    const float w[12] = {w0.x, w0.y, w0.z, w0.w, w1.x, w1.y, w1.z, w1.w, w2.x, w2.y, w2.z, w2.w};
-#pragma unroll
-                    for (int e = 0; e < 4; e++)
-#pragma unroll
-                        for (int j = 0; j < 3; j++)
-                            acc[k][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[e], w[3 + j + e], acc[k][j], 0, 0, 0);
-                }
-            }
-        }
-    }
-    // partial slabs ws[split][t][m][c], t = tap_row*3 + j   (same layout as k_wgrad_patch -> same reduce kernel)
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-#pragma unroll
-        for (int j = 0; j < 3; j++) {
-            float* o = ws_ + (((long)blockIdx.z * 9 + (g_row[k] * 3 + j)) * g.M) * g.Cpad + c0 + g_ct[k] * 32 + l31;
-#pragma unroll
-            for (int r = 0; r < 16; r++) {
-                const int m = m0 + g_mt[k] * 32 + (r & 3) + 8 * (r >> 2) + 4 * lk;
-                if (m < g.M) o[(long)m * g.Cpad] = acc[k][j][r];
-            }
-        }
-    }
-}
-
-__global__ void k_zero64(float* p) { p[threadIdx.x] = 0.f; }
-
-struct RG { const float* ws[MAXGRP]; float* gw[MAXGRP]; };
-
-struct WPlan {
-    bool ok;
-    int bmw, nt, TG, ngroups, Cp32, PH, PWr, PSc, npos, nbuf, tiles_x, tiles_y, ntiles, nsplit, tps;
-    size_t smem, ws_floats;
-};
-
-template <int BMW, int NT>
-inline void launch_wgrad_patch(const WP& w, dim3 grid, size_t smem, hipStream_t s) {
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_wgrad_patch<BMW, NT>), grid, dim3(WG_THREADS), smem, s, w);
-}
-
-static int dbg_flag(const char* name) { return cctools::env_flag(name); }
-
-inline WPlan plan_wgrad(int B, int M, int AH, int AW, int Cin, int R, int S, int si) {
-    WPlan p = {};
-    const int T = R * S;
-    p.bmw = (M > 32) ? 64 : 32;
-    const int MT = p.bmw / 32;
-    // NT accumulator tiles per wave: cover min(T, 9) taps per group
-    const int tg_target = T < 9 ? T : 9;
-    p.nt = (MT * tg_target + 3) / 4;
-    if (p.nt > 5) p.nt = 5;
-    p.TG = (4 * p.nt) / MT;
-    if (p.TG > T) p.TG = T;
-    p.ngroups = (T + p.TG - 1) / p.TG;
-    p.Cp32 = ((Cin + 31) / 32) * 32;
-    p.PH = (WTH - 1) * si + R;
-    p.PWr = 31 * si + S;
-    p.npos = p.PH * p.PWr;
-    p.PSc = p.npos | 1;                       // odd channel stride
-    auto smem_of = [&](int nbuf) { return (size_t)nbuf * (p.bmw * APS + 32 * p.PSc) * sizeof(float); };
-    p.nbuf = 2;
-    if (smem_of(2) > 150 * 1024) p.nbuf = 1;
-    p.smem = smem_of(p.nbuf);
-    // measured on MI355X (profiles/r01_*): the im2col-style k_wgrad is still ~2-8 % faster end to end than this
-    // per-tap kernel (small-channel layers pad to 32 channels here); kept selectable for tuning: CC_WGRAD_PATCH=1
-    p.ok = p.smem <= 150 * 1024 && dbg_flag("CC_WGRAD_PATCH");
-    p.tiles_x = (AW + 31) / 32;
-    p.tiles_y = (AH + WTH - 1) / WTH;
-    p.ntiles = B * p.tiles_x * p.tiles_y;
-    const long base = (long)((M + p.bmw - 1) / p.bmw) * (p.Cp32 / 32) * p.ngroups;
-    long nsplit = (512 + base - 1) / base;
-    if (nsplit > p.ntiles) nsplit = p.ntiles;
-    if (nsplit < 1) nsplit = 1;
-    p.tps = (int)((p.ntiles + nsplit - 1) / nsplit);
-    p.nsplit = (p.ntiles + p.tps - 1) / p.tps;
-    p.ws_floats = 64 + (size_t)p.nsplit * T * M * p.Cp32;
-    return p;
-}
-
-// ------------------------------------------------------------------ activation backward + bias gradient
-// geff = gy * act'(y) (in place allowed);  partial[m][n*cpp + chunk] = sum over the chunk of geff.
-// grid (cpp, C, B): one (image, channel) plane chunk per workgroup -> no per-element index arithmetic, float4 accesses
-// when the plane size allows (HBM-bound: 2 reads + 1 write per element).
-
-struct AB {      // up to MAXGRP same-shaped problems per launch: blockIdx.z = problem * zper + image
-    const float* gy[MAXGRP]; const float* y[MAXGRP]; float* geff[MAXGRP]; float* partial[MAXGRP]; float* gbias_direct[MAXGRP];
-    int zper;
-};
-
-template <bool VEC4>
-__global__ __launch_bounds__(256) void k_act_bwd(AB t, int HW, long gy_bs, long y_bs, long ge_bs, int act, float act_a,
-                                                 float act_b, int nb, int accum) {
-    __shared__ float red[4];
-    const int grp = (int)blockIdx.z / t.zper, zimg = (int)blockIdx.z - grp * t.zper;
-    const float* __restrict__ gy = t.gy[grp];
-    const float* __restrict__ y = t.y[grp];
-    float* __restrict__ geff = t.geff[grp];
-    float* __restrict__ partial = t.partial[grp];
-    float* __restrict__ gbias_direct = t.gbias_direct[grp];
-    const int m = blockIdx.y, cpp = gridDim.x;
-    float s[1] = {0.f};
-    // nb == 1: this workgroup owns image zimg; nb == B (small maps, zper == 1): it walks all images itself and
-    // writes the channel's bias gradient directly (no second-stage launch)
-    for (int nn = 0; nn < nb; nn++) {
-        const int n = zimg + nn;
-        const float* __restrict__ gp = gy + (long)n * gy_bs + (long)m * HW;
-        const float* __restrict__ yp = (act != ACT_NONE) ? y + (long)n * y_bs + (long)m * HW : nullptr;
-        float* __restrict__ ep = geff ? geff + (long)n * ge_bs + (long)m * HW : nullptr;
-        if (VEC4) {
-            // four iterations' loads (up to 8 x 16 bytes) in flight per work item; same element order as a one-by-one loop
-            const int nq = HW >> 2, stp = cpp * 256;
-            for (int q0 = blockIdx.x * 256 + threadIdx.x; q0 < nq; q0 += 4 * stp) {
-                float4 gg[4], vv[4];
-#pragma unroll
-                for (int u = 0; u < 4; u++) {
-                    const int q = q0 + u * stp;
-                    gg[u] = (q < nq) ? ((const float4*)gp)[q] : make_float4(0.f, 0.f, 0.f, 0.f);
-                    vv[u] = (q < nq && act != ACT_NONE) ? ((const float4*)yp)[q] : make_float4(0.f, 0.f, 0.f, 0.f);
-                }
-#pragma unroll
-                for (int u = 0; u < 4; u++) {
-                    const int q = q0 + u * stp;
-                    if (q < nq) {
-                        float4 g = gg[u];
-                        if (act != ACT_NONE) {
-                            g.x = act_grad(g.x, vv[u].x, act, act_a, act_b);
-                            g.y = act_grad(g.y, vv[u].y, act, act_a, act_b);
-                            g.z = act_grad(g.z, vv[u].z, act, act_a, act_b);
-                            g.w = act_grad(g.w, vv[u].w, act, act_a, act_b);
-                        }
-                        if (ep) ((float4*)ep)[q] = g;
-                        s[0] += (g.x + g.y) + (g.z + g.w);
-                    }
-                }
-            }
-        } else {
-            for (int e = blockIdx.x * 256 + threadIdx.x; e < HW; e += cpp * 256) {
-                float g = gp[e];
-                if (act != ACT_NONE) g = act_grad(g, yp[e], act, act_a, act_b);
-                if (ep) ep[e] = g;
-                s[0] += g;
-            }
-        }
-    }
-    cc::block_sum_256<1>(s, red);
-    if (threadIdx.x == 0) {
-        if (gbias_direct) gbias_direct[m] = accum ? (gbias_direct[m] + s[0]) : s[0];
-        else if (partial) partial[(long)m * (cpp * t.zper) + zimg * cpp + blockIdx.x] = s[0];
-    }
-}
-
-struct BR { const float* partial[MAXGRP]; float* gbias[MAXGRP]; };
-
-__global__ __launch_bounds__(64) void k_bias_reduce(BR t, int nchunk, int accum) {
-    const float* __restrict__ partial = t.partial[blockIdx.y];
-    float* __restrict__ gbias = t.gbias[blockIdx.y];
-    const int m = blockIdx.x;
-    float s = 0.f;
-    for (int k = threadIdx.x; k < nchunk; k += 64) s += partial[(long)m * nchunk + k];
-    s = cc::wave_sum(s);
-    if (threadIdx.x == 0) gbias[m] = accum ? (gbias[m] + s) : s;
-}
-
-inline int pick_bm(int M) { return M > 64 ? 128 : (M > 32 ? 64 : 32); }
 
 inline void launch_gg_flat(const GG& g, hipStream_t s) {
     const long Ntot = (long)g.B * g.OHt * g.OWt;
@@ -1910,8 +1245,7 @@ inline int wino_flip(const GG& g) { return g.dstep < 0 ? 1 : 0; }
 // kernel moves rows as 16-byte pieces, so dY and the input are first copied into rows padded with zeros to a multiple of 4 (zero
 // dY columns add nothing, zero input columns are the convolution's own padding) -- two 1-2 MB copies in one launch against half
 // the time of the im2col kernel on these 512-channel layers (profiles/r04_ab_round4.txt).
-struct PadJob { const float* src; float* dst; long bs; int rows_per_image; };        // rows of image n start at src + n * bs
-struct PadTab { PadJob j[2 * MAXGRP]; int n, B, W, Wp; long row_end[2 * MAXGRP]; };     // row_end: cumulative B * rows_per_image
+struct PadTab { ccint::PadJob j[2 * MAXGRP]; int n, B, W, Wp; long row_end[2 * MAXGRP]; };     // row_end: cumulative B * rows_per_image
 __global__ __launch_bounds__(256) void k_pad_rows(PadTab t) {
     const int q4 = t.Wp >> 2;                                  // float4s per padded row
     const long e = (long)blockIdx.x * 256 + threadIdx.x;       // one float4 of one padded row
@@ -1923,7 +1257,7 @@ __global__ __launch_bounds__(256) void k_pad_rows(PadTab t) {
     for (int q = 0; q < 2 * MAXGRP - 1; q++)
         if (q + 1 < t.n && row >= t.row_end[q]) { k = q + 1; first = t.row_end[q]; }
     if (row >= t.row_end[t.n - 1]) return;
-    const PadJob& j = t.j[k];
+    const ccint::PadJob& j = t.j[k];
     const long r = row - first;
     const int n = (int)(r / j.rows_per_image);
     const long rr = r - (long)n * j.rows_per_image;
@@ -1935,17 +1269,29 @@ __global__ __launch_bounds__(256) void k_pad_rows(PadTab t) {
     v.w = c4 + 3 < t.W ? s[c4 + 3] : 0.f;
     *reinterpret_cast<float4*>(j.dst + (r * t.Wp + c4)) = v;
 }
+}  // namespace
+
+void ccint::pad_rows_launch(const PadJob* jobs, int n, int B, int W, int Wp, hipStream_t s) {
+    PadTab t = {};
+    t.n = n; t.B = B; t.W = W; t.Wp = Wp;
+    long rows = 0;
+    for (int k = 0; k < n; k++) {
+        t.j[k] = jobs[k];
+        rows += (long)B * jobs[k].rows_per_image;
+        t.row_end[k] = rows;
+    }
+    const long nf4 = rows * (Wp >> 2);
+    hipLaunchKernelGGL(k_pad_rows, dim3((unsigned)((nf4 + 255) / 256)), dim3(256), 0, s, t);
+}
+
+namespace {
 
 // Winograd over a zero-padded copy of the input (ConvPlan::wpad): the copy goes behind the problem's partial slabs; pr / wg are
 // re-pointed at it (rows of wpad floats, dense [B][Cin][H][wpad])
 inline void wino_pad_input(const GG& g, const ConvPlan& p, float* part, hipStream_t s, ccint::WinoProb& pr, ccint::WinoGeom& wg) {
     float* xpad = part + p.part_floats;
-    PadTab t = {};
-    t.B = g.B; t.W = g.IW; t.Wp = p.wpad; t.n = 1;
-    t.j[0] = PadJob{g.x, xpad, g.x_bs, g.Cin * g.IH};
-    t.row_end[0] = (long)g.B * g.Cin * g.IH;
-    const long nf4 = t.row_end[0] * (p.wpad >> 2);
-    hipLaunchKernelGGL(k_pad_rows, dim3((unsigned)((nf4 + 255) / 256)), dim3(256), 0, s, t);
+    const ccint::PadJob job = {g.x, xpad, g.x_bs, g.Cin * g.IH};
+    ccint::pad_rows_launch(&job, 1, g.B, g.IW, p.wpad, s);
     if (cctools::env_flag("CC_WINO_TRACE"))
         fprintf(stderr, "wino padded input: B%d M%d C%d %dx%d -> pitch %d, nsplit %d dstep %d\n", g.B, g.M, g.Cin, g.IH, g.IW, p.wpad, p.nsplit, g.dstep);
     pr.x = xpad;
@@ -2100,20 +1446,15 @@ inline bool launch_classes(const ClsIn* cs, int n, hipStream_t s, bool idle_taps
                 for (int k = 0; k < n; k++)
                     if (cs[k].p.wpad != p.wpad || cs[k].p.part_floats != p.part_floats || !cs[k].part) return false;
                 for (int k0 = 0; k0 < n; k0 += 2 * MAXGRP) {
-                    PadTab t = {};
-                    t.B = cs[0].g.B; t.W = cs[0].g.IW; t.Wp = p.wpad;
-                    long rows = 0;
+                    ccint::PadJob jobs[2 * MAXGRP];
+                    int nj = 0;
                     for (int k = k0; k < n && k < k0 + 2 * MAXGRP; k++) {
                         const GG& g = cs[k].g;
                         float* xpad = cs[k].part + p.part_floats;
-                        t.j[t.n] = PadJob{g.x, xpad, g.x_bs, g.Cin * g.IH};
-                        rows += (long)g.B * g.Cin * g.IH;
-                        t.row_end[t.n] = rows;
-                        t.n++;
+                        jobs[nj++] = ccint::PadJob{g.x, xpad, g.x_bs, g.Cin * g.IH};
                         pr[k].x = xpad;
                     }
-                    const long nf4 = rows * (p.wpad >> 2);
-                    hipLaunchKernelGGL(k_pad_rows, dim3((unsigned)((nf4 + 255) / 256)), dim3(256), 0, s, t);
+                    ccint::pad_rows_launch(jobs, nj, cs[0].g.B, cs[0].g.IW, p.wpad, s);
                 }
                 wg.W = p.wpad;
                 wg.x_bs = (long)cs[0].g.Cin * cs[0].g.IH * p.wpad;
@@ -2221,7 +1562,7 @@ inline bool launch_classes(const ClsIn* cs, int n, hipStream_t s, bool idle_taps
 // the G (x parity classes) same-shaped problems of the *_group entry points: split-K planned for the whole launch (mult)
 inline bool launch_gg_classes(const GG* gs, int n, int mult, const float* const* zeros, const float* const* wps,
                               float* const* parts, hipStream_t s) {
-    if (n < 2 || n > MAXCLS || dbg_flag_early("CC_NO_CLASS_MERGE")) return false;
+    if (n < 2 || n > MAXCLS || cctools::env_flag("CC_NO_CLASS_MERGE")) return false;
     ClsIn cs[MAXCLS];
     for (int k = 0; k < n; k++) {
         cs[k].g = gs[k];
@@ -2619,15 +1960,15 @@ static void list_plan_splits(ListCls** cls, int n, int target) {
         const GG& g = cls[k]->c.g;
         const int nchunk = p.Cpad / p.ck;
         long want = 1;
-        if (fill < env_int_early("CC_CONV_FILL_BELOW", 256) && nchunk >= 4) want = (target + fill - 1) / fill;
+        if (fill < cctools::env_int("CC_CONV_FILL_BELOW", 256) && nchunk >= 4) want = (target + fill - 1) / fill;
         else if (nchunk >= 8) {
             const double len = (double)nchunk * ((g.Rt * g.St + 2) / 3);
-            const double cmin = env_int_early("CC_CONV_CLASS_STAGES", 24);
+            const double cmin = cctools::env_int("CC_CONV_CLASS_STAGES", 24);
             const double cap = t_ideal > cmin ? t_ideal : cmin;
             if (len > 2 * cap) want = (long)(len / cap + 0.999);
         }
-        if (want > nchunk / env_int_early("CC_CONV_MINCHUNKS", 1)) want = nchunk / env_int_early("CC_CONV_MINCHUNKS", 1);
-        if (want > env_int_early("CC_CONV_MAXSPLIT", 32)) want = env_int_early("CC_CONV_MAXSPLIT", 32);
+        if (want > nchunk / cctools::env_int("CC_CONV_MINCHUNKS", 1)) want = nchunk / cctools::env_int("CC_CONV_MINCHUNKS", 1);
+        if (want > cctools::env_int("CC_CONV_MAXSPLIT", 32)) want = cctools::env_int("CC_CONV_MAXSPLIT", 32);
         p.nsplit = 1; p.cps = nchunk;
         if (want >= 2) {
             p.cps = (int)((nchunk + want - 1) / want);
@@ -2688,496 +2029,6 @@ int cc_conv2d_list(int n, const long* desc_host, float* ws, int split_target, vo
     if (list_run(n, desc_host, ws, split_target > 0 ? split_target : 512, true, (hipStream_t)stream) < 0) return CC_ERR_ARG;
     CC_CHECK_LAUNCH();
     return CC_OK;
-}
-
-struct W3Plan { bool ok; int mt, nbuf, tiles_x, tiles_y, ntiles, nsplit, tps, Cp32; size_t smem, ws_floats; };
-
-static int env_int(const char* name, int dflt) { return cctools::env_int(name, dflt); }
-
-inline W3Plan plan_w3(int B, int M, int AH, int AW, int Cin, int R, int S, int si, int pad, int IH, int IW, int G = 1) {
-    W3Plan p = {};
-    p.ok = (R == 3 && S == 3 && si == 1 && pad == 1 && IH == AH && IW == AW && (AW % 4) == 0 && AW >= 16 && Cin >= 32 && M >= env_int("CC_W3_MINM", 64) &&
-            !dbg_flag("CC_NO_WGRAD3X3"));   // measured (tools/wgrad_ablate.py): wins for M > 64 (1.2-1.45x), loses below 64;
-                                            // M = 64 (<2, 2> tiles): -0.2 ms/step against the thin / generic kernels (r3o A/B)
-    if (!p.ok) return p;
-    p.mt = (M > 64) ? 4 : ((M > 32 && Cin > 32) ? 2 : ((Cin > 64) ? 1 : 2));
-    p.nbuf = 1;
-    const int BM = 32 * p.mt, BC = 32 * (4 / p.mt);
-    p.Cp32 = ((Cin + BC - 1) / BC) * BC;
-    p.tiles_x = (AW + 31) / 32;
-    p.tiles_y = (AH + 1) / 2;
-    p.ntiles = B * p.tiles_x * p.tiles_y;
-    const long base = (long)((M + BM - 1) / BM) * (p.Cp32 / BC) * (G > 1 ? G : 1);
-    long nsplit = (env_int("CC_W3_SPLIT", 512) + base - 1) / base;      // 512: measured -0.27 ms/step vs 256 (r02f A/B)
-    const long mt_ = env_int("CC_W3_MINTILES", 3);
-    const long cap = (p.ntiles + mt_ - 1) / mt_;  // >= 6 pixel tiles per split: every split writes a 9*M*Cpad partial slab
-    if (nsplit > cap) nsplit = cap;
-    if (nsplit > p.ntiles) nsplit = p.ntiles;
-    if (nsplit < 1) nsplit = 1;
-    p.tps = (int)((p.ntiles + nsplit - 1) / nsplit);
-    p.nsplit = (p.ntiles + p.tps - 1) / p.tps;
-    p.smem = (size_t)(BM * 16 + ((BC * W3_PC + 63) / 64) * 64) * 16;
-    p.ws_floats = 64 + (size_t)p.nsplit * 9 * M * p.Cp32;
-    return p;
-}
-
-static size_t wgrad_ws_bytes_base(int B, int M, int AH, int AW, int Cin, int R, int S, int si);
-static size_t wgrad_ws_bytes_rest(int B, int M, int AH, int AW, int Cin, int R, int S, int si);
-
-struct WinoPadPlan { bool ok; int Wp; ccint::WinoWgradPlan wp; size_t pad_floats; };     // pad_floats: padded x + dY of ONE problem
-inline WinoPadPlan wino_pad_plan(int B, int M, int AH, int AW, int Cin, int G) {
-    WinoPadPlan p = {};
-    if ((AW % 4) == 0 || AH < 2 || dbg_flag("CC_NO_WINO_WGRAD_PAD")) return p;
-    // large weight matrices only: the copies and the kernel's per-workgroup epilogue have to pay (measured per shape)
-    if (M < env_int_early("CC_WWP_MINM", 96) || Cin < env_int_early("CC_WWP_MINC", 96)) return p;
-    p.Wp = (AW + 3) & ~3;
-    p.wp = ccint::wino_wgrad_plan(B, M, AH, p.Wp, Cin, G, env_int_early("CC_WWP_MINQ", 64));
-    p.ok = p.wp.ok != 0;
-    p.pad_floats = ((size_t)B * (Cin + M) * AH * p.Wp + 3) & ~(size_t)3;
-    return p;
-}
-
-size_t cc_conv2d_wgrad_ws_bytes(int B, int M, int AH, int AW, int Cin, int R, int S, int si) {
-    // the thin path is confirmed at launch (pad, input width): size for it AND for the path it would fall back to
-    size_t thin = ccint::wgrad_thin_ws_floats(B, M, AH, AW, Cin, R, S, si) * sizeof(float);
-    if (R == 3 && S == 3 && si == 1 && M <= 2) {          // a head's weight gradient (conv_heads.hip)
-        const ccint::HeadWgradPlan hp = ccint::head_wgrad_plan(B, M, AH, AW, Cin);
-        if (hp.ok && hp.ws_floats * sizeof(float) > thin) thin = hp.ws_floats * sizeof(float);
-    }
-    const size_t base = wgrad_ws_bytes_base(B, M, AH, AW, Cin, R, S, si);
-    return ((thin > base ? thin : base) + 15) & ~(size_t)15;        // (the areas of a group's problems follow each other: keep them 16-byte aligned)
-}
-
-static size_t wgrad_ws_bytes_base(int B, int M, int AH, int AW, int Cin, int R, int S, int si) {
-    size_t wino = 0;
-    if (R == 3 && S == 3 && si == 1) {       // Winograd path (pad / input size are implied by "same" convolutions: checked again at launch)
-        for (int G = 1; G <= MAXGRP; G++) {       // every group size: the split search is not monotonic in G
-            const ccint::WinoWgradPlan wp = ccint::wino_wgrad_plan(B, M, AH, AW, Cin, G);
-            if (wp.ok && wp.ws_floats * sizeof(float) > wino) wino = wp.ws_floats * sizeof(float);
-            const WinoPadPlan pp = wino_pad_plan(B, M, AH, AW, Cin, G);
-            if (pp.ok && (pp.wp.ws_floats + pp.pad_floats) * sizeof(float) > wino) wino = (pp.wp.ws_floats + pp.pad_floats) * sizeof(float);
-        }
-    }
-    const size_t rest = wgrad_ws_bytes_rest(B, M, AH, AW, Cin, R, S, si);
-    return wino > rest ? wino : rest;
-}
-
-static size_t wgrad_ws_bytes_rest(int B, int M, int AH, int AW, int Cin, int R, int S, int si) {
-    {   // the 3x3/s1/p1 path (pad and input size are implied by "same" convolutions: checked again at launch)
-        const W3Plan q = plan_w3(B, M, AH, AW, Cin, R, S, si, 1, AH, AW);
-        if (q.ok) return q.ws_floats * sizeof(float);
-    }
-    const WPlan p = plan_wgrad(B, M, AH, AW, Cin, R, S, si);
-    if (p.ok) return p.ws_floats * sizeof(float);
-    const long Ntot = (long)Cin * R * S;
-    const long P = (long)B * AH * AW;
-    const int bm = pick_bm(M);
-    const long tiles = ((Ntot + BN - 1) / BN) * ((M + bm - 1) / bm);
-    long nsplit = (env_int_early("CC_WGRAD_SPLIT_TARGET", 512) + tiles - 1) / tiles;
-    const long mr = env_int_early("CC_WGRAD_MINRANGE", 32);
-    const long maxsplit = (P + mr - 1) / mr;  // small maps still need >= 256 workgroups: split down to 32-pixel ranges (-0.16 ms/step against 64, r3s3)
-    if (nsplit > maxsplit) nsplit = maxsplit;
-    if (nsplit < 1) nsplit = 1;
-    return nsplit <= 1 ? 16 : (size_t)nsplit * M * Ntot * sizeof(float);
-}
-
-/* gw[m, c, r, s] (strides o_*) = sum_{n,ty,tx} a[n, m, ty, tx] * x[n, c, si*ty - pad + r, si*tx - pad + s].
- * conv2d weight-gradient: a = dY [B,Cout,OH,OW], x = input, si = stride, o strides of [Cout,Cin,R,S];
- * ConvTranspose2d weight-gradient: a = input [B,Cin,IH,IW], x = dY, si = stride, o strides of [Cin,Cout,R,S].
- * Group form: G (<= 4) same-shaped problems in one launch (+ one reduction launch); a / x / gw: HOST arrays of device
- * addresses; ws: G consecutive areas of cc_conv2d_wgrad_ws_bytes() each. */
-// launches of the generic kernel collected by cc_conv2d_wgrad_list instead of issued one by one
-struct WgradParked { WG g; int bm; dim3 grid; double gflop; };
-struct WgradCollector { WgradParked* p; int cap, n; ccint::WinoWgradParked* wino; };      // wino: parked Winograd problems (or null)
-
-static void launch_wgrad_parked(const WgradCollector& c, hipStream_t s) {
-    for (int bm = 128; bm >= 32; bm /= 2) {
-        int i = 0;
-        while (i < c.n) {
-            WGM m = {};
-            long blk = 0;
-            double gf = 0;
-            for (; i < c.n && m.n < MAXWCLS; i++) {
-                if (c.p[i].bm != bm) continue;
-                const dim3& gr = c.p[i].grid;
-                const long nb = (long)gr.x * gr.y * gr.z;
-                if (m.n && blk + nb >= (1l << 31)) break;          // (a problem that large goes into a launch of its own: never dropped)
-                m.c[m.n] = c.p[i].g;
-                m.gx[m.n] = (int)gr.x; m.gy[m.n] = (int)gr.y;
-                blk += nb;
-                m.bx_end[m.n] = (int)blk;
-                gf += c.p[i].gflop;
-                m.n++;
-            }
-            if (!m.n) break;
-            char nm[64];
-            snprintf(nm, sizeof nm, "k_wgrad_multi<%d>%s", bm, "");
-            cctiming::Scope tsc(nm, gf, s);
-            if (bm == 128) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_wgrad_multi<128>), dim3((unsigned)blk), dim3(256), 0, s, m);
-            else if (bm == 64) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_wgrad_multi<64>), dim3((unsigned)blk), dim3(256), 0, s, m);
-            else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_wgrad_multi<32>), dim3((unsigned)blk), dim3(256), 0, s, m);
-        }
-    }
-}
-
-static int wgrad_group_impl(int G, const long* a, const long* x, const long* gw, float* ws, int B, int M, int AH, int AW, long a_bs,
-                            int Cin, int IH, int IW, long x_bs, int R, int S, int si, int pad, long o_sm, long o_sc, int accumulate,
-                            void* stream, ccint::RedSink* sink, const float* zeros64 = nullptr, WgradCollector* park = nullptr) {
-    if (G <= 0 || G > MAXGRP || B <= 0 || M <= 0 || Cin <= 0) return CC_ERR_ARG;
-    hipStream_t s = (hipStream_t)stream;
-    long rd[MAXGRP][ccint::RD_LONGS];
-    const size_t stride_f = cc_conv2d_wgrad_ws_bytes(B, M, AH, AW, Cin, R, S, si) / sizeof(float);
-    if (R == 3 && S == 3 && si == 1 && pad == 1 && IH == AH && IW == AW) {
-        // Winograd F(3x3, 2x2): 16 instead of 36 multiply-adds per 2x2 tile (wino_wgrad.hip); same slab layout / reduction as k_wgrad3x3
-        ccint::WinoWgradPlan wp = ccint::wino_wgrad_plan(B, M, AH, AW, Cin, G);
-        if (wp.ok && park && park->wino && park->wino->n + G <= ccint::WINO_WGRAD_PARK_CAP) wp = ccint::wino_wgrad_plan_parked(wp, M);
-        if (wp.ok) {
-            const float *ap[MAXGRP], *xp[MAXGRP];
-            float* wsp[MAXGRP];
-            for (int k = 0; k < G; k++) { ap[k] = (const float*)a[k]; xp[k] = (const float*)x[k]; wsp[k] = ws + k * stride_f + 64; }
-            bool ok;
-            {
-                char nm[128];
-                int nl = snprintf(nm, sizeof nm, "k_wino_wgrad");
-                if (cctools::env_flag("CC_TIMING_DETAIL"))
-                    snprintf(nm + nl, sizeof nm - nl, " G%d B%d M%d C%d %dx%d k%d wg%d", G, B, M, Cin, AH, AW, wp.nsplit,
-                             wp.nmb * wp.ncb * G * wp.nsplit);
-                ccint::WinoWgradParked* wpark = park ? park->wino : nullptr;
-                cctiming::Scope tsc(nm, 2e-9 * 16.0 * G * B * ((AH + 1) / 2) * ((AW + 1) / 2) * (double)M * Cin, s,
-                                    !(wpark && wpark->n + G <= ccint::WINO_WGRAD_PARK_CAP));
-                ok = ccint::wino_wgrad_launch(wp, ap, xp, wsp, G, B, M, AH, AW, a_bs, Cin, x_bs, s, wpark);
-            }
-            if (ok) {
-                for (int k = 0; k < G; k++) {
-                    const long d[ccint::RD_LONGS] = {1, (long)wsp[k], (long)gw[k], wp.nsplit, accumulate, o_sm, o_sc, 9, M, Cin, wp.Cp};
-                    for (int i = 0; i < ccint::RD_LONGS; i++) rd[k][i] = d[i];
-                }
-                if (ccint::wgrad_reduce_emit(sink, &rd[0][0], G, s) != CC_OK) return CC_ERR_ARG;
-                CC_CHECK_LAUNCH();
-                return CC_OK;
-            }
-        }
-    }
-    if (R == 3 && S == 3 && si == 1 && pad == 1 && IH == AH && IW == AW) {
-        WinoPadPlan pp = wino_pad_plan(B, M, AH, AW, Cin, G);
-        if (pp.ok && park && park->wino && park->wino->n + G <= ccint::WINO_WGRAD_PARK_CAP) {
-            const size_t slabs = (pp.wp.ws_floats + 3) & ~(size_t)3;          // the padded copies keep their place behind the stand-alone plan's slabs
-            pp.wp = ccint::wino_wgrad_plan_parked(pp.wp, M);
-            pp.wp.ws_floats = slabs;
-        }
-        if (pp.ok) {
-            const float *ap[MAXGRP], *xp[MAXGRP];
-            float* wsp[MAXGRP];
-            PadTab t = {};
-            t.B = B; t.W = AW; t.Wp = pp.Wp;
-            long rows = 0;
-            for (int k = 0; k < G; k++) {
-                float* area = ws + k * stride_f;
-                wsp[k] = area + 64;
-                float* xpad = area + ((pp.wp.ws_floats + 3) & ~(size_t)3);
-                float* apad = xpad + (size_t)B * Cin * AH * pp.Wp;
-                t.j[2 * k] = PadJob{(const float*)x[k], xpad, x_bs, Cin * AH};
-                rows += (long)B * Cin * AH; t.row_end[2 * k] = rows;
-                t.j[2 * k + 1] = PadJob{(const float*)a[k], apad, a_bs, M * AH};
-                rows += (long)B * M * AH; t.row_end[2 * k + 1] = rows;
-                xp[k] = xpad; ap[k] = apad;
-            }
-            t.n = 2 * G;
-            const long nf4 = rows * (pp.Wp >> 2);
-            bool ok;
-            {
-                char nm[128];
-                int nl = snprintf(nm, sizeof nm, "k_wino_wgrad");
-                if (cctools::env_flag("CC_TIMING_DETAIL"))
-                    snprintf(nm + nl, sizeof nm - nl, " G%d B%d M%d C%d %dx%d(pad %d) k%d wg%d", G, B, M, Cin, AH, AW, pp.Wp, pp.wp.nsplit,
-                             pp.wp.nmb * pp.wp.ncb * G * pp.wp.nsplit);
-                ccint::WinoWgradParked* wpark = park ? park->wino : nullptr;
-                cctiming::Scope tsc(nm, 2e-9 * 16.0 * G * B * ((AH + 1) / 2) * (pp.Wp / 2) * (double)M * Cin, s,
-                                    !(wpark && wpark->n + G <= ccint::WINO_WGRAD_PARK_CAP));
-                hipLaunchKernelGGL(k_pad_rows, dim3((unsigned)((nf4 + 255) / 256)), dim3(256), 0, s, t);
-                ok = ccint::wino_wgrad_launch(pp.wp, ap, xp, wsp, G, B, M, AH, pp.Wp, (long)M * AH * pp.Wp, Cin, (long)Cin * AH * pp.Wp, s, wpark);
-            }
-            if (ok) {
-                for (int k = 0; k < G; k++) {
-                    const long d[ccint::RD_LONGS] = {1, (long)wsp[k], (long)gw[k], pp.wp.nsplit, accumulate, o_sm, o_sc, 9, M, Cin, pp.wp.Cp};
-                    for (int i = 0; i < ccint::RD_LONGS; i++) rd[k][i] = d[i];
-                }
-                if (ccint::wgrad_reduce_emit(sink, &rd[0][0], G, s) != CC_OK) return CC_ERR_ARG;
-                CC_CHECK_LAUNCH();
-                return CC_OK;
-            }
-        }
-    }
-    if (R == 3 && S == 3 && si == 1 && pad == 1 && IH == AH && IW == AW && M <= 2) {
-        // weight gradient of a prediction head: HBM-bound VALU kernel (conv_heads.hip), one launch per problem
-        const ccint::HeadWgradPlan hp = ccint::head_wgrad_plan(B, M, AH, AW, Cin);
-        if (hp.ok && hp.ws_floats <= stride_f) {
-            bool ok = true;
-            char nm[128];
-            int nl = snprintf(nm, sizeof nm, "k_wgrad_thinm<%d>", M);
-            if (cctools::env_flag("CC_TIMING_DETAIL"))
-                snprintf(nm + nl, sizeof nm - nl, " G%d B%d M%d C%d %dx%d r3 s1 k%d", G, B, M, Cin, AH, AW, hp.nblk);
-            {
-                cctiming::Scope tsc(nm, 2e-9 * G * B * AH * AW * (double)M * Cin * 9, s);
-                for (int k = 0; k < G && ok; k++)
-                    ok = ccint::head_wgrad_launch(hp, (const float*)a[k], (const float*)x[k], ws + k * stride_f, B, M, AH, AW, a_bs, Cin, x_bs, s);
-            }
-            if (ok && cctools::env_flag("CC_HEAD_TRACE"))
-                fprintf(stderr, "head wgrad: G%d B%d M%d C%d %dx%d R%d nblk %d\n", G, B, M, Cin, AH, AW, hp.R, hp.nblk);
-            if (ok) {
-                for (int k = 0; k < G; k++) {
-                    const long d[ccint::RD_LONGS] = {0, (long)(ws + k * stride_f), (long)gw[k], hp.nblk, accumulate, o_sm, o_sc, M, (long)Cin * 9, 9, 3, 3, 1};
-                    for (int i = 0; i < ccint::RD_LONGS; i++) rd[k][i] = d[i];
-                }
-                if (ccint::wgrad_reduce_emit(sink, &rd[0][0], G, s) != CC_OK) return CC_ERR_ARG;
-                CC_CHECK_LAUNCH();
-                return CC_OK;
-            }
-        }
-    }
-    {   // thin layers fill the chip on their own: one launch per problem
-        bool thin = true;
-        char nm[128];
-        ccint::wgrad_thin_name(B, M, AH, AW, Cin, IH, IW, R, S, si, pad, nm, 64);
-        if (nm[0] && cctools::env_flag("CC_TIMING_DETAIL")) {
-            const size_t nl = strlen(nm);
-            snprintf(nm + nl, sizeof nm - nl, " G%d B%d M%d C%d %dx%d r%d s%d", G, B, M, Cin, AH, AW, R, si);
-        }
-        // (recorded only when the thin path is taken: the name is empty otherwise; alignment can still turn a problem away, then
-        // the record brackets nothing)
-        cctiming::Scope tsc(nm[0] ? nm : "k_wgrad_thin<declined>", nm[0] ? 2e-9 * G * B * AH * AW * (double)M * Cin * R * S : 0.0,
-                            nm[0] ? s : nullptr, nm[0] != 0 && !ccint::wgrad_thin_parking());
-        for (int k = 0; k < G && thin; k++)
-            thin = ccint::wgrad_thin_launch((const float*)a[k], (const float*)x[k], (float*)gw[k], ws + k * stride_f, B, M, AH, AW, a_bs,
-                                            Cin, IH, IW, x_bs, R, S, si, pad, o_sm, o_sc, accumulate, s, sink);
-        // eligibility depends on the geometry (and 16-byte alignment of the pointers): all problems or none, in practice
-        if (thin) {
-            CC_CHECK_LAUNCH();
-            return CC_OK;
-        }
-    }
-    RG rg = {};
-    const W3Plan q = plan_w3(B, M, AH, AW, Cin, R, S, si, pad, IH, IW, G);
-    if (q.ok) {
-        W3 w = {};
-        w.zeros = zeros64 ? zeros64 : ws;
-        for (int k = 0; k < G; k++) {
-            w.ga[k] = (const float*)a[k]; w.gxp[k] = (const float*)x[k]; w.gws[k] = ws + k * stride_f + 64;
-            rg.ws[k] = w.gws[k]; rg.gw[k] = (float*)gw[k];
-        }
-        w.B = B; w.M = M; w.AH = AH; w.AW = AW; w.a_bs = a_bs; w.Cin = Cin; w.x_bs = x_bs;
-        w.tiles_x = q.tiles_x; w.tiles_y = q.tiles_y; w.ntiles = q.ntiles; w.tiles_per_split = q.tps; w.nsplit = q.nsplit;
-        w.Cpad = q.Cp32;
-        if (!zeros64) hipLaunchKernelGGL(k_zero64, dim3(1), dim3(64), 0, s, ws);
-        const int BM = 32 * q.mt, BC = 32 * (4 / q.mt);
-        dim3 grid((unsigned)(((M + BM - 1) / BM) * (q.Cp32 / BC)), (unsigned)G, (unsigned)q.nsplit);
-        w.dbg = env_int("CC_W3_DBG", 0);
-        {
-            char nm[128];
-            int nl = snprintf(nm, sizeof nm, "k_wgrad3x3<%d, %d>", q.mt, 4 / q.mt);
-            if (cctools::env_flag("CC_TIMING_DETAIL"))
-                snprintf(nm + nl, sizeof nm - nl, " G%d B%d M%d C%d %dx%d k%d wg%d", G, B, M, Cin, AH, AW, q.nsplit,
-                         (int)(grid.x * grid.y * grid.z));
-            cctiming::Scope tsc(nm, 2e-9 * G * B * AH * AW * (double)M * Cin * 9, s);
-            if (q.mt == 4) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_wgrad3x3<4, 1>), grid, dim3(256), q.smem, s, w);
-            else if (q.mt == 2) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_wgrad3x3<2, 2>), grid, dim3(256), q.smem, s, w);
-            else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_wgrad3x3<1, 4>), grid, dim3(256), q.smem, s, w);
-        }
-        for (int k = 0; k < G; k++) {
-            const long d[ccint::RD_LONGS] = {1, (long)rg.ws[k], (long)rg.gw[k], q.nsplit, accumulate, o_sm, o_sc, 9, M, Cin, q.Cp32};
-            for (int i = 0; i < ccint::RD_LONGS; i++) rd[k][i] = d[i];
-        }
-        if (ccint::wgrad_reduce_emit(sink, &rd[0][0], G, s) != CC_OK) return CC_ERR_ARG;
-        CC_CHECK_LAUNCH();
-        return CC_OK;
-    }
-    const WPlan p = plan_wgrad(B, M, AH, AW, Cin, R, S, si);
-    if (p.ok) {       // experimental per-tap kernel (CC_WGRAD_PATCH=1): one problem at a time
-        for (int k = 0; k < G; k++) {
-            float* wsk = ws + k * stride_f;
-            WP w = {};
-            w.a = (const float*)a[k]; w.x = (const float*)x[k]; w.zeros = wsk; w.ws = wsk + 64;
-            w.B = B; w.M = M; w.AH = AH; w.AW = AW; w.a_bs = a_bs; w.Cin = Cin; w.IH = IH; w.IW = IW; w.x_bs = x_bs;
-            w.R = R; w.S = S; w.si = si; w.pad = pad; w.PH = p.PH; w.PWr = p.PWr; w.PSc = p.PSc; w.npos = p.npos;
-            w.tiles_x = p.tiles_x; w.tiles_y = p.tiles_y; w.ntiles = p.ntiles; w.tiles_per_split = p.tps; w.nsplit = p.nsplit;
-            w.TG = p.TG; w.ngroups = p.ngroups; w.Cp32 = p.Cp32; w.nbuf = p.nbuf;
-            w.dbg = cctools::env_int("CC_WGRAD_DBG", 0);
-            hipLaunchKernelGGL(k_zero64, dim3(1), dim3(64), 0, s, wsk);      // the LDS-DMA halo source (a kernel, not a memset node)
-            dim3 grid((unsigned)(((M + p.bmw - 1) / p.bmw) * (p.Cp32 / 32) * p.ngroups), 1, (unsigned)p.nsplit);
-            if (p.bmw == 64) {
-                if (p.nt == 5) launch_wgrad_patch<64, 5>(w, grid, p.smem, s);
-                else if (p.nt == 4) launch_wgrad_patch<64, 4>(w, grid, p.smem, s);
-                else if (p.nt == 3) launch_wgrad_patch<64, 3>(w, grid, p.smem, s);
-                else if (p.nt == 2) launch_wgrad_patch<64, 2>(w, grid, p.smem, s);
-                else launch_wgrad_patch<64, 1>(w, grid, p.smem, s);
-            } else {
-                if (p.nt >= 3) launch_wgrad_patch<32, 3>(w, grid, p.smem, s);
-                else if (p.nt == 2) launch_wgrad_patch<32, 2>(w, grid, p.smem, s);
-                else launch_wgrad_patch<32, 1>(w, grid, p.smem, s);
-            }
-            const long d[ccint::RD_LONGS] = {1, (long)w.ws, (long)gw[k], p.nsplit, accumulate, o_sm, o_sc, R * S, M, Cin, p.Cp32};
-            if (ccint::wgrad_reduce_emit(sink, d, 1, s) != CC_OK) return CC_ERR_ARG;
-        }
-        CC_CHECK_LAUNCH();
-        return CC_OK;
-    }
-    const long Ntot = (long)Cin * R * S;
-    const long P = (long)B * AH * AW;
-    const int bm = pick_bm(M);
-    const long tiles = ((Ntot + BN - 1) / BN) * ((M + bm - 1) / bm) * G;
-    // a problem that will share a launch with others (cc_conv2d_wgrad_list) does not have to fill the chip alone: fewer, longer
-    // pixel ranges -- fewer 64 KB partial tiles written, reduced and paid for in epilogues (never more splits than stand-alone:
-    // the workspace is sized for that).  Measured (profiles/r04_ab_round4.txt): target 256 / ranges >= 64 pixels -0.13 ms against
-    // the stand-alone plan; much longer chains lose again (target 64: +0.5 ms, 32: +1.6 ms -- the kernel is slow per k-step)
-    const bool parked = park && park->n < park->cap;
-    const long target = parked ? env_int_early("CC_WGRAD_PARK_TARGET", 256) : env_int_early("CC_WGRAD_SPLIT_TARGET", 512);
-    long nsplit = (target + tiles - 1) / tiles;
-    const long mr = parked ? env_int_early("CC_WGRAD_PARK_MINRANGE", 64) : env_int_early("CC_WGRAD_MINRANGE", 32);
-    const long maxsplit = (P + mr - 1) / mr;  // small maps still need >= 256 workgroups: split down to 32-pixel ranges (-0.16 ms/step against 64, r3s3)
-    if (nsplit > maxsplit) nsplit = maxsplit;
-    if (nsplit < 1) nsplit = 1;
-    long pps = (P + nsplit - 1) / nsplit;
-    pps = ((pps + BK - 1) / BK) * BK;
-    nsplit = (P + pps - 1) / pps;
-    WG g = {};
-    g.B = B; g.M = M; g.AH = AH; g.AW = AW; g.a_bs = a_bs;
-    g.Cin = Cin; g.IH = IH; g.IW = IW; g.x_bs = x_bs;
-    g.Rt = R; g.St = S; g.dy0 = -pad; g.dx0 = -pad; g.dstep = 1; g.si = si;
-    g.o_sm = o_sm; g.o_sc = o_sc; g.o_ri = S; g.o_sj = 1;
-    g.direct = (nsplit == 1);
-    g.accum = accumulate;
-    g.nsplit = (int)nsplit;
-    for (int k = 0; k < G; k++) {
-        g.ga[k] = (const float*)a[k]; g.gxp[k] = (const float*)x[k];
-        g.gout[k] = g.direct ? (float*)gw[k] : ws + k * stride_f;
-        rg.ws[k] = ws + k * stride_f; rg.gw[k] = (float*)gw[k];
-    }
-    g.pix_per_split = (int)pps;
-    dim3 grid((unsigned)((Ntot + BN - 1) / BN), (unsigned)((M + bm - 1) / bm), (unsigned)(nsplit * G));
-    if (park && park->n < park->cap) {
-        park->p[park->n++] = WgradParked{g, bm, grid, 2e-9 * G * B * AH * AW * (double)M * Cin * R * S};
-    } else {
-        char nm[128];
-        int nl = snprintf(nm, sizeof nm, "k_wgrad<%d>", bm);
-        if (cctools::env_flag("CC_TIMING_DETAIL"))
-            snprintf(nm + nl, sizeof nm - nl, " G%d B%d M%d C%d %dx%d r%d s%d k%ld wg%d", G, B, M, Cin, AH, AW, R, si, (long)nsplit,
-                     (int)(grid.x * grid.y * grid.z));
-        cctiming::Scope tsc(nm, 2e-9 * G * B * AH * AW * (double)M * Cin * R * S, s);
-        if (bm == 128) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_wgrad<128>), grid, dim3(256), 0, s, g);
-        else if (bm == 64) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_wgrad<64>), grid, dim3(256), 0, s, g);
-        else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_wgrad<32>), grid, dim3(256), 0, s, g);
-    }
-    if (!g.direct) {
-        for (int k = 0; k < G; k++) {
-            const long d[ccint::RD_LONGS] = {0, (long)rg.ws[k], (long)rg.gw[k], nsplit, accumulate, o_sm, o_sc, M, Ntot, R * S, S, S, 1};
-            for (int i = 0; i < ccint::RD_LONGS; i++) rd[k][i] = d[i];
-        }
-        if (ccint::wgrad_reduce_emit(sink, &rd[0][0], G, s) != CC_OK) return CC_ERR_ARG;
-    }
-    CC_CHECK_LAUNCH();
-    return CC_OK;
-}
-
-int cc_conv2d_wgrad_group(int G, const long* a, const long* x, const long* gw, float* ws, int B, int M, int AH, int AW, long a_bs,
-                          int Cin, int IH, int IW, long x_bs, int R, int S, int si, int pad, long o_sm, long o_sc, int accumulate,
-                          void* stream) {
-    return wgrad_group_impl(G, a, x, gw, ws, B, M, AH, AW, a_bs, Cin, IH, IW, x_bs, R, S, si, pad, o_sm, o_sc, accumulate, stream,
-                            nullptr);
-}
-
-/* ... with the reductions of the partial slabs left to the caller: their descriptors (16 longs each, at most G) are written to
- * red_host[0 .. *nred_host) and ws must stay untouched until cc_wgrad_reduce_table has run on them.  zeros64_or_null: 64 zero
- * floats that outlive the launch (the LDS-DMA source of halo pixels; without it a fill launch precedes the kernel). */
-int cc_conv2d_wgrad_group_defer(int G, const long* a, const long* x, const long* gw, float* ws, int B, int M, int AH, int AW,
-                                long a_bs, int Cin, int IH, int IW, long x_bs, int R, int S, int si, int pad, long o_sm, long o_sc,
-                                int accumulate, const float* zeros64_or_null, long* red_host, int red_cap, int* nred_host,
-                                void* stream) {
-    if (!red_host || !nred_host || red_cap < G) return CC_ERR_ARG;
-    ccint::RedSink sink = {red_host, red_cap, 0};
-    const int r = wgrad_group_impl(G, a, x, gw, ws, B, M, AH, AW, a_bs, Cin, IH, IW, x_bs, R, S, si, pad, o_sm, o_sc, accumulate,
-                                   stream, &sink, zeros64_or_null);
-    *nred_host = sink.n;
-    return r;
-}
-
-/* n groups of DIFFERENT shapes (what a backward stage has parked at its end): desc_host = n x 32 longs
- *   {G, a[4], x[4], gw[4], ws, B, M, AH, AW, a_bs, Cin, IH, IW, x_bs, R, S, si, pad, o_sm, o_sc, accumulate, 0, 0}
- * -- each group exactly as one cc_conv2d_wgrad_group_defer call (same kernels, same arithmetic, same reduce descriptors, in list
- * order), except that the groups the planner sends to the generic kernel share launches (k_wgrad_multi: up to 12 per launch). */
-int cc_conv2d_wgrad_list(int n, const long* desc_host, const float* zeros64_or_null, long* red_host, int red_cap, int* nred_host,
-                         void* stream) {
-    if (n <= 0 || !desc_host || !red_host || !nred_host) return CC_ERR_ARG;
-    hipStream_t s = (hipStream_t)stream;
-    constexpr int CAP = 64;
-    static thread_local WgradParked parked[CAP];
-    static thread_local ccint::WinoWgradParked wino_parked;
-    wino_parked.n = 0;
-    WgradCollector col = {parked, CAP, 0, cctools::env_flag("CC_NO_WINO_WGRAD_LIST") ? nullptr : &wino_parked};
-    ccint::RedSink sink = {red_host, red_cap, 0};
-    // the thin weight gradients of the list share launches too (wgrad_thin.hip: per kernel instance); launched when this call ends
-    struct ThinPark {
-        hipStream_t s; bool was;
-        explicit ThinPark(hipStream_t st) : s(st), was(ccint::wgrad_thin_park(true)) {}
-        ~ThinPark() {
-            const double gf = ccint::wgrad_thin_parked_gflop();
-            if (gf > 0) {
-                cctiming::Scope tsc("k_wgrad_thin_multi", gf, s);
-                ccint::wgrad_thin_flush(s);
-            }
-            ccint::wgrad_thin_park(was);
-        }
-    } thin_park(s);
-    for (int i = 0; i < n; i++) {
-        const long* d = desc_host + 32l * i;
-        const int G = (int)d[0];
-        // on an error in the middle of the list: what was collected is launched (its reduce descriptors describe slabs that are then
-        // really written) and the descriptors emitted so far are handed back, so that the caller's state stays consistent
-        auto bail = [&](int code) {
-            launch_wgrad_parked(col, s);
-            if (wino_parked.n > 0) ccint::wino_wgrad_launch_parked(&wino_parked, s);
-            *nred_host = sink.n;
-            return code;
-        };
-        if (G <= 0 || G > MAXGRP || sink.n + G > red_cap) return bail(CC_ERR_ARG);
-        const int before = col.n;
-        const int r = wgrad_group_impl(G, d + 1, d + 5, d + 9, (float*)d[13], (int)d[14], (int)d[15], (int)d[16], (int)d[17], d[18],
-                                       (int)d[19], (int)d[20], (int)d[21], d[22], (int)d[23], (int)d[24], (int)d[25], (int)d[26], d[27],
-                                       d[28], (int)d[29], stream, &sink, zeros64_or_null, &col);
-        if (r != CC_OK) return bail(r);
-        if (col.n > before && col.p[before].g.direct) {
-            // a problem that writes its gradient itself (no split): it must not share a launch with an earlier one of the same target
-            bool dup = false;
-            for (int j = 0; j < before && !dup; j++)
-                if (col.p[j].g.direct)
-                    for (int u = 0; u < MAXGRP && !dup; u++)
-                        for (int v = 0; v < MAXGRP; v++)
-                            if (col.p[j].g.gout[u] && col.p[j].g.gout[u] == col.p[before].g.gout[v]) { dup = true; break; }
-            if (dup) {
-                const WgradParked keep = col.p[before];
-                col.n = before;
-                launch_wgrad_parked(col, s);
-                col.p[0] = keep;
-                col.n = 1;
-            }
-        }
-    }
-    launch_wgrad_parked(col, s);
-    if (wino_parked.n > 0) {
-        double gf = 0;
-        for (int i = 0; i < wino_parked.n; i++) gf += wino_parked.d[i].gflop;
-        cctiming::Scope tsc("k_wino_wgrad_multi", gf, s);
-        ccint::wino_wgrad_launch_parked(&wino_parked, s);
-    }
-    *nred_host = sink.n;
-    CC_CHECK_LAUNCH();
-    return CC_OK;
-}
-
-int cc_conv2d_wgrad(const float* a, const float* x, float* gw, float* ws, int B, int M, int AH, int AW, long a_bs, int Cin,
-                    int IH, int IW, long x_bs, int R, int S, int si, int pad, long o_sm, long o_sc, int accumulate, void* stream) {
-    const long ap = (long)a, xp = (long)x, gp = (long)gw;
-    return cc_conv2d_wgrad_group(1, &ap, &xp, &gp, ws, B, M, AH, AW, a_bs, Cin, IH, IW, x_bs, R, S, si, pad, o_sm, o_sc, accumulate,
-                                 stream);
 }
 
 /* ---- per-kernel timing (measurement aid): cc_timing_enable(1) starts recording (process-wide), cc_timing_collect
@@ -3280,7 +2131,7 @@ int cc_conv2d_dgrad_kernel(int B, int K, int OH, int OW, int C, int R, int S, in
     }
     ConvPlan p = plan_conv(gs[0]);
     bool multi = false;
-    if (stride == 2 && prepacked && all && n >= 2 && !dbg_flag_early("CC_NO_CLASS_MERGE")) {
+    if (stride == 2 && prepacked && all && n >= 2 && !cctools::env_flag("CC_NO_CLASS_MERGE")) {
         multi = true;
         int tps = 3, maxsplit = 1;
         for (int k = 0; k < n; k++) {
@@ -3293,211 +2144,6 @@ int cc_conv2d_dgrad_kernel(int B, int K, int OH, int OW, int C, int R, int S, in
     }
     patch_name(p, multi, (char*)name_out_host, cap);
     return CC_OK;
-}
-
-int cc_conv2d_wgrad_kernel(int B, int M, int AH, int AW, int Cin, int IH, int IW, int R, int S, int si, int pad,
-                           void* name_out_host, int cap) {
-    char* out = (char*)name_out_host;
-    if (R == 3 && S == 3 && si == 1 && pad == 1 && IH == AH && IW == AW && ccint::wino_wgrad_plan(B, M, AH, AW, Cin, 1).ok) {
-        snprintf(out, cap, "k_wino_wgrad");
-        return CC_OK;
-    }
-    ccint::wgrad_thin_name(B, M, AH, AW, Cin, IH, IW, R, S, si, pad, out, cap);
-    if (out[0]) return CC_OK;
-    const W3Plan q = plan_w3(B, M, AH, AW, Cin, R, S, si, pad, IH, IW);
-    if (q.ok) { snprintf(out, cap, "k_wgrad3x3<%d, %d>", q.mt, 4 / q.mt); return CC_OK; }
-    const WPlan p = plan_wgrad(B, M, AH, AW, Cin, R, S, si);
-    if (p.ok) { snprintf(out, cap, "k_wgrad_patch<%d, %d>", p.bmw, p.nt); return CC_OK; }
-    snprintf(out, cap, "k_wgrad<%d>", pick_bm(M));
-    return CC_OK;
-}
-
-// Bias gradients of a whole backward stage in ONE launch.  With the activation derivative applied in the data-gradient epilogues
-// (planned backward), the per-layer pass left over is a pure reduction of the pre-activation gradient over (B, H, W): 84 launches
-// of 5-8 us per step.  The trainer parks them (the gradients stay alive for the parked weight-gradient launches anyway) and
-// cc_bias_grad_table sums up to NBJ layers per launch; per-chunk partials are finished by cc_wgrad_reduce_table (kind 4), small
-// maps are written directly -- block decomposition and summation order are k_act_bwd's.
-constexpr int NBJ = 32;
-struct BJ {
-    const float* gy; float* partial; float* gbias; long gy_bs;
-    int B, C, HW, cpp, single, accum, vec4, blk_end;
-};
-struct BT { BJ j[NBJ]; int n; };
-
-__global__ __launch_bounds__(256) void k_bias_table(BT t) {
-    __shared__ float red[4];
-    int k = 0, first = 0;
-#pragma unroll 1
-    for (int q = 0; q + 1 < t.n; q++)
-        if ((int)blockIdx.x >= t.j[q].blk_end) { k = q + 1; first = t.j[q].blk_end; }
-    const BJ& j = t.j[k];
-    const int bid = (int)blockIdx.x - first;
-    const int per_m = j.single ? 1 : j.B * j.cpp;                 // workgroups per channel
-    const int m = bid / per_m, rem = bid - m * per_m;
-    const int zimg = j.single ? 0 : rem / j.cpp, chunk = j.single ? 0 : rem - zimg * j.cpp;
-    const int cpp = j.single ? 1 : j.cpp, nb = j.single ? j.B : 1, HW = j.HW;
-    float s[1] = {0.f};
-    for (int nn = 0; nn < nb; nn++) {
-        const float* __restrict__ gp = j.gy + (long)(zimg + nn) * j.gy_bs + (long)m * HW;
-        if (j.vec4) {
-            const int nq = HW >> 2, stp = cpp * 256;
-            for (int q0 = chunk * 256 + threadIdx.x; q0 < nq; q0 += 4 * stp) {
-                float4 gg[4];
-#pragma unroll
-                for (int u = 0; u < 4; u++) {
-                    const int q = q0 + u * stp;
-                    gg[u] = (q < nq) ? ((const float4*)gp)[q] : make_float4(0.f, 0.f, 0.f, 0.f);
-                }
-#pragma unroll
-                for (int u = 0; u < 4; u++)
-                    if (q0 + u * stp < nq) s[0] += (gg[u].x + gg[u].y) + (gg[u].z + gg[u].w);
-            }
-        } else {
-            for (int e = chunk * 256 + threadIdx.x; e < HW; e += cpp * 256) s[0] += gp[e];
-        }
-    }
-    cc::block_sum_256<1>(s, red);
-    if (threadIdx.x == 0) {
-        if (j.single) j.gbias[m] = j.accum ? (j.gbias[m] + s[0]) : s[0];
-        else j.partial[(long)m * (j.cpp * j.B) + zimg * j.cpp + chunk] = s[0];
-    }
-}
-
-size_t cc_act_bwd_ws_bytes(int C) { return (size_t)C * 64 * sizeof(float); }
-
-/* geff = gy * act'(y) (geff may alias gy or be null), gbias[c] = sum_{n,p} geff (gbias may be null).
- * Group form: G (<= 4) same-shaped problems per launch; gy / y / geff / gbias: HOST arrays of device addresses (0 = null,
- * uniformly over the group); ws: G areas of cc_act_bwd_ws_bytes(C) each. */
-static int act_bwd_bias_impl(int G, const long* gy, const long* y, const long* geff, const long* gbias, float* ws, int B, int C, int H,
-                             int W, long gy_bs, long y_bs, long geff_bs, int act, float act_a, float act_b, int accumulate_bias,
-                             void* stream, ccint::RedSink* sink) {
-    if (G <= 0 || G > MAXGRP || B <= 0 || C <= 0) return CC_ERR_ARG;
-    const bool has_y = y && y[0], has_ge = geff && geff[0], has_gb = gbias && gbias[0];
-    if (act != ACT_NONE && !has_y) return CC_ERR_ARG;
-    hipStream_t s = (hipStream_t)stream;
-    const int HW = H * W;
-    int cpp = (HW + 8191) / 8192;                       // chunks per (image, channel) plane; B * cpp <= 64 partials per channel
-    const int cap = 64 / B > 0 ? 64 / B : 1;
-    cpp = cpp < 1 ? 1 : (cpp > cap ? cap : cpp);
-    if (B > 64) return CC_ERR_ARG;
-    bool vec4 = (HW % 4 == 0) && (gy_bs % 4 == 0) && (y_bs % 4 == 0) && (geff_bs % 4 == 0);
-    for (int k = 0; k < G; k++)
-        vec4 = vec4 && ((((uintptr_t)gy[k]) | (uintptr_t)(has_y ? y[k] : 0) | (uintptr_t)(has_ge ? geff[k] : 0)) % 16 == 0);
-    // small maps with enough channels to occupy the chip: one workgroup per channel, bias gradient written in place
-    const bool single = ((long)B * HW <= 32768) && ((long)C * B * HW * G <= (1l << 22) || (long)C * G >= 128);
-    const int nb = single ? B : 1;
-    const size_t wstride = cc_act_bwd_ws_bytes(C) / sizeof(float);
-    AB t = {};
-    BR r = {};
-    t.zper = single ? 1 : B;
-    for (int k = 0; k < G; k++) {
-        t.gy[k] = (const float*)gy[k];
-        t.y[k] = has_y ? (const float*)y[k] : nullptr;
-        t.geff[k] = has_ge ? (float*)geff[k] : nullptr;
-        t.gbias_direct[k] = (single && has_gb) ? (float*)gbias[k] : nullptr;
-        t.partial[k] = (has_gb && !single) ? ws + k * wstride : nullptr;
-        r.partial[k] = t.partial[k];
-        r.gbias[k] = has_gb ? (float*)gbias[k] : nullptr;
-    }
-    dim3 grid(single ? 1 : cpp, C, (single ? 1 : B) * G);
-    const int nchunk = single ? 1 : cpp * B;
-    if (vec4)
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_act_bwd<true>), grid, dim3(256), 0, s, t, HW, gy_bs, y_bs, geff_bs, act, act_a, act_b,
-                           nb, accumulate_bias);
-    else
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_act_bwd<false>), grid, dim3(256), 0, s, t, HW, gy_bs, y_bs, geff_bs, act, act_a, act_b,
-                           nb, accumulate_bias);
-    if (has_gb && !single) {
-        if (sink) {      // second stage parked: kind 4 of the reduce table (same per-channel summation as k_bias_reduce)
-            for (int k = 0; k < G; k++) {
-                const long d[ccint::RD_LONGS] = {4, (long)r.partial[k], (long)r.gbias[k], nchunk, accumulate_bias, 0, 0, C};
-                if (ccint::wgrad_reduce_emit(sink, d, 1, s) != CC_OK) return CC_ERR_ARG;
-            }
-        } else {
-            hipLaunchKernelGGL(k_bias_reduce, dim3(C, G), dim3(64), 0, s, r, nchunk, accumulate_bias);
-        }
-    }
-    CC_CHECK_LAUNCH();
-    return CC_OK;
-}
-
-int cc_act_bwd_bias_group(int G, const long* gy, const long* y, const long* geff, const long* gbias, float* ws, int B, int C, int H,
-                          int W, long gy_bs, long y_bs, long geff_bs, int act, float act_a, float act_b, int accumulate_bias,
-                          void* stream) {
-    return act_bwd_bias_impl(G, gy, y, geff, gbias, ws, B, C, H, W, gy_bs, y_bs, geff_bs, act, act_a, act_b, accumulate_bias, stream,
-                             nullptr);
-}
-
-/* ... with the second stage of the bias gradient (sum of the per-chunk partials in ws) left to the caller: descriptors for
- * cc_wgrad_reduce_table (16 longs each, at most G, none when the kernel wrote gbias itself) go to red_host[0 .. *nred_host);
- * ws must stay untouched until that call. */
-int cc_act_bwd_bias_group_defer(int G, const long* gy, const long* y, const long* geff, const long* gbias, float* ws, int B, int C,
-                                int H, int W, long gy_bs, long y_bs, long geff_bs, int act, float act_a, float act_b,
-                                int accumulate_bias, long* red_host, int red_cap, int* nred_host, void* stream) {
-    if (!red_host || !nred_host || red_cap < G) return CC_ERR_ARG;
-    ccint::RedSink sink = {red_host, red_cap, 0};
-    const int rc = act_bwd_bias_impl(G, gy, y, geff, gbias, ws, B, C, H, W, gy_bs, y_bs, geff_bs, act, act_a, act_b, accumulate_bias,
-                                     stream, &sink);
-    *nred_host = sink.n;
-    return rc;
-}
-
-/* Bias gradient gbias[c] (+)= sum_{n,h,w} gy[n,c,h,w], parked: nothing is launched.  job_host[12] receives the job for
- * cc_bias_grad_table; when the map is large enough to be summed in chunks, red_host[16] receives the descriptor of the second
- * stage for cc_wgrad_reduce_table and *nred_host = 1 (else 0).  ws: cc_act_bwd_ws_bytes(C) bytes, untouched until both ran. */
-int cc_bias_grad_defer(const float* gy, float* gbias, float* ws, int B, int C, int H, int W, long gy_bs, int accumulate,
-                       long* job_host, long* red_host, int* nred_host) {
-    if (!gy || !gbias || !job_host || !red_host || !nred_host || B <= 0 || B > 64 || C <= 0 || H <= 0 || W <= 0) return CC_ERR_ARG;
-    const int HW = H * W;
-    int cpp = (HW + 8191) / 8192;                       // as act_bwd_bias_impl
-    const int cap = 64 / B > 0 ? 64 / B : 1;
-    cpp = cpp < 1 ? 1 : (cpp > cap ? cap : cpp);
-    const bool vec4 = (HW % 4 == 0) && (gy_bs % 4 == 0) && (((uintptr_t)gy) % 16 == 0);
-    // one workgroup per channel (no second stage) only where it walks <= 4096 elements: in a table launch the longest job
-    // sets the duration (k_act_bwd's own threshold is 32768: there a second launch would cost more than the walk)
-    const bool single = (long)B * HW <= 4096;
-    if (!single && !ws) return CC_ERR_ARG;
-    const long job[12] = {(long)gy, single ? 0 : (long)ws, (long)gbias, gy_bs, B, C, HW, cpp, single ? 1 : 0, accumulate ? 1 : 0,
-                          vec4 ? 1 : 0, 0};
-    for (int i = 0; i < 12; i++) job_host[i] = job[i];
-    *nred_host = 0;
-    if (!single) {
-        const long d[ccint::RD_LONGS] = {4, (long)ws, (long)gbias, (long)cpp * B, accumulate ? 1 : 0, 0, 0, C};
-        for (int i = 0; i < ccint::RD_LONGS; i++) red_host[i] = d[i];
-        *nred_host = 1;
-    }
-    return CC_OK;
-}
-
-/* Run n parked bias-gradient jobs (12 longs each, from cc_bias_grad_defer): one launch per 32. */
-int cc_bias_grad_table(const long* jobs_host, int n, void* stream) {
-    if (!jobs_host || n <= 0) return CC_ERR_ARG;
-    hipStream_t s = (hipStream_t)stream;
-    for (int j0 = 0; j0 < n; j0 += NBJ) {
-        BT t = {};
-        int bx = 0;
-        t.n = n - j0 < NBJ ? n - j0 : NBJ;
-        for (int k = 0; k < t.n; k++) {
-            const long* d = jobs_host + (long)(j0 + k) * 12;
-            BJ& j = t.j[k];
-            j.gy = (const float*)d[0]; j.partial = (float*)d[1]; j.gbias = (float*)d[2]; j.gy_bs = d[3];
-            j.B = (int)d[4]; j.C = (int)d[5]; j.HW = (int)d[6]; j.cpp = (int)d[7]; j.single = (int)d[8]; j.accum = (int)d[9];
-            j.vec4 = (int)d[10];
-            if (!j.gy || !j.gbias || j.B <= 0 || j.C <= 0 || j.HW <= 0 || j.cpp <= 0 || (!j.single && !j.partial)) return CC_ERR_ARG;
-            bx += j.single ? j.C : j.C * j.B * j.cpp;
-            j.blk_end = bx;
-        }
-        hipLaunchKernelGGL(k_bias_table, dim3((unsigned)bx), dim3(256), 0, s, t);
-    }
-    CC_CHECK_LAUNCH();
-    return CC_OK;
-}
-
-int cc_act_bwd_bias(const float* gy, const float* y_or_null, float* geff_or_null, float* gbias_or_null, float* ws, int B,
-                    int C, int H, int W, long gy_bs, long y_bs, long geff_bs, int act, float act_a, float act_b,
-                    int accumulate_bias, void* stream) {
-    const long a = (long)gy, b = (long)y_or_null, c = (long)geff_or_null, d = (long)gbias_or_null;
-    return cc_act_bwd_bias_group(1, &a, &b, &c, &d, ws, B, C, H, W, gy_bs, y_bs, geff_bs, act, act_a, act_b, accumulate_bias, stream);
 }
 
 }  // extern "C"

@@ -3,7 +3,32 @@
 #include <stddef.h>
 #include <hip/hip_runtime.h>
 
+// ---- per-kernel timing (tools build only; the registry and cc_timing_* are in conv.hip): a Scope brackets the main device kernel
+// of a call with HIP events on its stream.  active = false: nothing is recorded.
+namespace cctiming {
+#ifdef CC_TOOLS
+struct Scope {
+    hipEvent_t e1 = nullptr;
+    hipStream_t s;
+    Scope(const char* name, double gflop, hipStream_t st, bool active = true);
+    ~Scope();
+};
+#else
+struct Scope { Scope(const char*, double, hipStream_t, bool = true) {} };      // product build: no registry, no events
+#endif
+}  // namespace cctiming
+
 namespace ccint {
+
+constexpr int MAXGRP = 4;       // same-shaped problems per group launch (parallel branches of a network)
+constexpr int BN = 128;         // im2col GEMM kernels (k_gather_gemm, k_wgrad): pixels / (c, r, s) columns per workgroup tile
+constexpr int BK = 16;          // ... and their reduction chunk
+inline int pick_bm(int M) { return M > 64 ? 128 : (M > 32 ? 64 : 32); }      // ... and their row tile
+
+// rows of W floats copied into rows zero-padded to Wp (a multiple of 4) floats (conv.hip k_pad_rows): up to 2 * MAXGRP jobs of B
+// images each in one launch; the padded copy of a job is dense
+struct PadJob { const float* src; float* dst; long bs; int rows_per_image; };        // rows of image n start at src + n * bs
+void pad_rows_launch(const PadJob* jobs, int n, int B, int W, int Wp, hipStream_t s);
 
 // second stage of the split weight-gradient kernels (wgrad_reduce.hip): host descriptors of RD_LONGS longs each
 constexpr int RD_LONGS = 16;

@@ -1,4 +1,4 @@
-// Second stage of every split weight-gradient kernel (k_wgrad, k_wgrad3x3 / k_wgrad_patch, k_wgrad_thin): the partial slabs of up
+// Second stage of every split weight-gradient kernel (k_wgrad, k_wgrad3x3 / k_wino_wgrad, k_wgrad_thin): the partial slabs of up
 // to NRD problems are summed -- in a fixed order, no atomics -- by ONE launch.  The slabs of a layer are 4-50 MB and its
 // reduction alone is a 8-15 us launch at ~1.4 TB/s (latency, not bandwidth: 9-300 workgroups); the weight gradients are not
 // needed before the optimizer step, so the trainer parks the descriptors (cc_conv2d_wgrad_group_defer) and reduces a whole

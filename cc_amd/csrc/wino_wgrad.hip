@@ -32,7 +32,7 @@ namespace {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-constexpr int WG_MAXP = 4;                 // problems per launch (= conv.hip MAXGRP)
+constexpr int WG_MAXP = 4;                 // problems per launch (= conv_internal.h MAXGRP)
 constexpr int OBLK = 16 * 8 * 64;          // floats of one operand chunk: [f 16][quad 2][row 64][t4]
 constexpr int XPW = 16 * 16 * 4;           // floats of one wave's input patch: [channel 16][input row 4][16 floats]
 constexpr int WGT = 512;

@@ -85,3 +85,20 @@ def test_product_package_reads_no_environment():
             delattr(config.debug, k)
         for k, v in saved.items():
             setattr(config.debug, k, v)
+
+
+def test_conv_planners_answer_the_recorded_plans(golden_dir):
+    """The host planners of the product library against tests/golden/conv_plans.json (tools/plan_sweep.py --write-fixture): the
+    weight-gradient workspace and the kernel the weight-gradient, forward and data-gradient calls dispatch to, for every
+    convolution layer of the four networks at the benchmarked sizes and for the geometries of tests/parity.py.  The names are the
+    ones the dispatchers' timing scopes carry -- for the weight gradient: `k_wino_wgrad` also over zero-padded copies (widths that
+    are not multiples of 4), `k_wgrad_thinm<M>` for the prediction heads.  A planner edit has to show up as a diff of that file."""
+    import json
+    from tools import plan_sweep
+    fx = json.load(open(os.path.join(golden_dir, "conv_plans.json")))
+    assert fx["columns"][10:] == plan_sweep.COLUMNS and len(fx["rows"]) >= 100
+    got = plan_sweep.answers(build.build(), [tuple(r[:10]) for r in fx["rows"]])
+    bad = [(r[:10], r[10:], g) for r, g in zip(fx["rows"], got) if r[10:] != g]
+    assert not bad, (len(bad), bad[:8])
+    names = {r[11] for r in fx["rows"]}
+    assert "k_wino_wgrad" in names and any(n.startswith("k_wgrad_thinm<") for n in names)

@@ -10,13 +10,28 @@ issued together (NOTES.md, "Loads in flight")."""
 import glob
 import os
 import re
+import shutil
 import subprocess
 import sys
 import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-FILT = "/opt/rocm/lib/llvm/bin/llvm-cxxfilt"
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+from cc_amd import build as _build  # noqa: E402
+
+HIPCC = _build.HIPCC
+FILT = next((p for p in ("/opt/rocm/lib/llvm/bin/llvm-cxxfilt", shutil.which("llvm-cxxfilt"), shutil.which("c++filt"))
+             if p and os.path.exists(p)), "c++filt")
+
+
+def compile_asm(src, out, tree=ROOT):
+    """gfx950 assembly of one kernel source with the flags the library is built with (cc_amd/build.py; `tree`: the checkout the
+    source belongs to, for its include directory).  -> the CompletedProcess (returncode != 0: stderr says why)."""
+    flags = list(_build.FLAGS)
+    flags[flags.index("-I") + 1] = os.path.join(tree, "include")
+    return subprocess.run([HIPCC] + flags + _build.FILE_FLAGS.get(os.path.basename(src), []) +
+                          ["--cuda-device-only", "-S", "-o", out, src], capture_output=True, text=True)
 
 
 def demangle(n):
@@ -63,9 +78,7 @@ def main():
     with tempfile.TemporaryDirectory() as tmp:
         for f in files:
             out = os.path.join(tmp, os.path.basename(f) + ".s")
-            r = subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-I",
-                                os.path.join(ROOT, "include"), "--cuda-device-only", "-S", "-o", out, f],
-                               capture_output=True, text=True)
+            r = compile_asm(f, out)
             if r.returncode != 0:
                 print("%s: hipcc failed\n%s" % (f, r.stderr[-2000:]))
                 continue
