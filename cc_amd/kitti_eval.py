@@ -1,12 +1,18 @@
-"""KITTI evaluation on the device: Eigen-split depth (reference test_disp.py with kitti_eval/depth_evaluation_utils.py) and
-odometry ATE / RE (test_pose.py with kitti_eval/pose_evaluation_utils.py).
+"""KITTI evaluation on the device: Eigen-split depth (reference test_disp.py with kitti_eval/depth_evaluation_utils.py),
+odometry ATE / RE (test_pose.py with kitti_eval/pose_evaluation_utils.py), KITTI 2015 optical flow (test_flow.py) and motion
+segmentation (test_mask.py), the last two on datasets/validation_flow.py's tree.
 
-Thin wrappers over the HIP entries of cc_amd/csrc/kitti_eval.hip (include/ccengine.h, "KITTI evaluation"), the two evaluation
-loops, dataset readers that mirror the reference's metadata code on `pathlib` and PIL, and a command line:
+Thin wrappers over the HIP entries of cc_amd/csrc/kitti_eval.hip and kitti_flow_eval.hip (include/ccengine.h, "KITTI
+evaluation" and "KITTI 2015 flow and mask evaluation"), the four evaluation loops, dataset readers that mirror the reference's
+metadata code on `pathlib` and PIL, and a command line:
 
     python -m cc_amd.kitti_eval depth --pretrained-dispnet D.pth.tar [--pretrained-posenet P.pth.tar] --dataset-dir RAW \\
         --dataset-list test_files_eigen.txt
     python -m cc_amd.kitti_eval pose P.pth.tar --dataset-dir ODOMETRY --sequences 09 10
+    python -m cc_amd.kitti_eval flow --kitti-dir KITTI2015 --pretrained-disp D --pretrained-pose P --pretrained-mask M \\
+        --pretrained-flow F
+    python -m cc_amd.kitti_eval mask --kitti-dir KITTI2015 --pretrained-disp D --pretrained-pose P --pretrained-mask M \\
+        --pretrained-flow F
 
 The ground-truth depth map, the spline zoom of the prediction, the masked median scaling and the errors all run as kernels; the
 evaluation loops read results back to the host once, after the loop.  Readers return what the files hold (uint8 frames, raw
@@ -16,6 +22,9 @@ import argparse
 import datetime
 import math
 import pathlib
+import struct
+import types
+import zlib
 
 import numpy as np
 import torch
@@ -25,6 +34,13 @@ from ._lib import engine, STREAM
 ERROR_NAMES = ['abs_rel', 'sq_rel', 'rms', 'log_rms', 'a1', 'a2', 'a3']       # test_disp.py:144
 POSE_ERROR_NAMES = ['ATE', 'RE']                                               # test_pose.py:96
 ROTATION_MODES = {'euler': 0, 'quat': 1}
+FLOW_ERROR_NAMES = ['epe_total', 'epe_sp', 'epe_mv', 'Fl', 'epe_total_gt_mask', 'epe_sp_gt_mask', 'epe_mv_gt_mask',
+                    'Fl_gt_mask']                                              # test_flow.py:106
+MASK_COUNT_NAMES = ['tp_0', 'fp_0', 'fn_0', 'tp_1', 'fp_1', 'fn_1']            # test_mask.py:105
+MASK_ROWS = ('full', 'census', 'bare')                                         # the rows of the counts buffer
+NORM_FIELDS = ("rigidity_mask", "rigidity_mask_census", "rigidity_mask_combined", "flow_fwd_non_rigid", "flow_fwd_rigid",
+               "total_flow")
+PNG_SIGNATURE = b'\x89PNG\r\n\x1a\n'
 
 
 def _ws(nbytes, dev):
@@ -99,6 +115,114 @@ def pose_snippet_errors(pred, gt_seq, first, rotation_mode='euler', step=1, want
     engine().call("cc_pose_snippet_errors", pred.detach().float().contiguous(), gt_seq.to(dev, torch.float64).contiguous(), first, S,
                   L, gt_seq.shape[0], int(step), ROTATION_MODES[rotation_mode], err, final, STREAM)
     return (err, final) if want_final else err
+
+
+def png16_scanlines(data):
+    """The inflated scanlines of a non-interlaced 16-bit RGB PNG held in `data` (bytes): IHDR parsed, the IDAT chunks
+    concatenated and inflated with zlib, the stream split into -> (ftype [H] uint8 the filter byte of every row, rows
+    [H, stride] uint8 its 6*W filtered bytes padded with zeros to a multiple of 8, W).  ValueError for anything that is not
+    bit depth 16, colour type 2, interlace 0."""
+    if data[:8] != PNG_SIGNATURE:
+        raise ValueError("not a PNG file")
+    pos, idat, ihdr = 8, [], None
+    while pos + 8 <= len(data):
+        length, kind = struct.unpack(">I4s", data[pos:pos + 8])
+        body = data[pos + 8:pos + 8 + length]
+        pos += 12 + length
+        if kind == b'IHDR':
+            ihdr = struct.unpack(">IIBBBBB", body)
+        elif kind == b'IDAT':
+            idat.append(body)
+        elif kind == b'IEND':
+            break
+    if ihdr is None:
+        raise ValueError("PNG without an IHDR chunk")
+    W, H, depth, colour, _, _, interlace = ihdr
+    if (depth, colour, interlace) != (16, 2, 0):
+        raise ValueError("flow PNG must be 16-bit RGB, not interlaced (bit depth %d, colour type %d, interlace %d)"
+                         % (depth, colour, interlace))
+    raw = np.frombuffer(zlib.decompress(b''.join(idat)), dtype=np.uint8)
+    if raw.size != H * (1 + 6 * W):
+        raise ValueError("PNG data holds %d bytes, %d x %d 16-bit RGB needs %d" % (raw.size, W, H, H * (1 + 6 * W)))
+    raw = raw.reshape(H, 1 + 6 * W)
+    ftype = raw[:, 0].copy()
+    if ftype.size and ftype.max() > 4:
+        raise ValueError("PNG filter type %d" % int(ftype.max()))
+    rows = np.zeros((H, (6 * W + 7) // 8 * 8), dtype=np.uint8)
+    rows[:, :6 * W] = raw[:, 1:]
+    return ftype, rows, W
+
+
+def png16_flow_decode(ftype, rows, W):
+    """cc_png16_flow_decode: ftype [N,H] and rows [N,H,stride] uint8 on the device (png16_scanlines of N files of one size)
+    -> [N,3,H,W] fp32 = u, v, valid of flow_read_png (flowutils/flow_io.py:96-117)."""
+    assert ftype.dim() == 2 and rows.dim() == 3 and rows.shape[:2] == ftype.shape, "png16_flow_decode: ftype [N,H], rows [N,H,stride]"
+    assert ftype.dtype == torch.uint8 and rows.dtype == torch.uint8
+    N, H, stride = rows.shape
+    gt = torch.empty((N, 3, H, W), dtype=torch.float32, device=rows.device)
+    engine().call("cc_png16_flow_decode", ftype.contiguous(), rows.contiguous(), N, H, int(W), stride, gt, STREAM)
+    return gt
+
+
+def read_flow_png(path, device='cuda'):
+    """flow_read_png + torch.FloatTensor(np.dstack((u, v, valid)).transpose(2, 0, 1)) (validation_flow.py:125-128) of a KITTI
+    flow ground-truth file -> [3,H,W] fp32 on the device.  The host inflates; the PNG filters are undone by the kernel."""
+    with open(str(path), 'rb') as f:
+        ftype, rows, W = png16_scanlines(f.read())
+    dev = torch.device(device)
+    return png16_flow_decode(torch.from_numpy(ftype).to(dev)[None], torch.from_numpy(rows).to(dev)[None], W)[0]
+
+
+def rigidity_composition_norm(explainability_mask, flow_cam, flow_fwd, THRESH, want=NORM_FIELDS):
+    """test_mask.py:129-138 per sample (the reference runs batch size 1, where its .max() over the batch is the sample's):
+    explainability_mask [B,MC>=3,H,W], flow_cam / flow_fwd [B,2,H,W] -> namespace with rigidity_mask (the bare MaskNet mask),
+    rigidity_mask_census, rigidity_mask_combined [B,1,H,W] (0/1 fp32, bit-exact with torch) and flow_fwd_non_rigid,
+    flow_fwd_rigid, total_flow [B,2,H,W].  `want`: the fields to produce (the others are None)."""
+    B, MC, H, W = explainability_mask.shape
+    assert flow_cam.shape == (B, 2, H, W) and flow_fwd.shape == (B, 2, H, W), "rigidity_composition_norm: flows must be [B,2,H,W] of the mask"
+    unknown = set(want) - set(NORM_FIELDS)
+    assert not unknown, "rigidity_composition_norm: unknown fields %s" % sorted(unknown)
+    m = explainability_mask.detach().float().contiguous()
+    fc, ff = flow_cam.detach().float().contiguous(), flow_fwd.detach().float().contiguous()
+    o = {k: (torch.empty((B, 1 if k.startswith("rigidity") else 2, H, W), dtype=torch.float32, device=m.device) if k in want else None)
+         for k in NORM_FIELDS}
+    e = engine()
+    e.call("cc_rigidity_compose_norm", m, MC, fc, ff, o["rigidity_mask"], o["rigidity_mask_census"], o["rigidity_mask_combined"],
+           o["flow_fwd_non_rigid"], o["flow_fwd_rigid"], o["total_flow"], float(THRESH), B, H, W,
+           _ws(e.call("cc_rigidity_compose_norm_ws", B), m.device), STREAM)
+    return types.SimpleNamespace(**o)
+
+
+def mask_iou_counts(obj_map, semantic, masks, counts=None):
+    """mask_error (test_mask.py:224-262) of up to three predicted masks [h,w] fp32 (None: skipped) against obj_map / semantic
+    [Hg,Wg] uint8, all on the device: ADDS tp_0, fp_0, fn_0, tp_1, fp_1, fn_1 of mask k into row k of counts ([3,6] int64 on the
+    device; a zeroed one is made when None) -> counts."""
+    masks = list(masks) + [None] * (3 - len(masks))
+    assert len(masks) == 3, "mask_iou_counts: at most three masks"
+    assert obj_map.dim() == 2 and semantic.shape == obj_map.shape, "mask_iou_counts: obj_map and semantic must be [Hg,Wg] of one shape"
+    assert obj_map.dtype == torch.uint8 and semantic.dtype == torch.uint8, "mask_iou_counts: the maps are uint8"
+    hw = {tuple(m.shape) for m in masks if m is not None}
+    assert len(hw) == 1 and len(next(iter(hw))) == 2, "mask_iou_counts: masks must be [h,w] of one shape"
+    h, w = next(iter(hw))
+    if counts is None:
+        counts = torch.zeros((3, 6), dtype=torch.int64, device=obj_map.device)
+    assert counts.shape == (3, 6) and counts.dtype == torch.int64 and counts.is_contiguous()
+    pm = [None if m is None else m.detach().float().contiguous() for m in masks]
+    engine().call("cc_mask_iou_counts", obj_map.contiguous(), semantic.contiguous(), obj_map.shape[0], obj_map.shape[1], pm[0],
+                  pm[1], pm[2], h, w, counts, STREAM)
+    return counts
+
+
+def mask_ious(counts):
+    """test_mask.py:199-209 for the summed counts [3,6] -> {'full' | 'census' | 'bare': (iou, bg_iou, fg_iou)} in fp64"""
+    c = np.asarray(counts, dtype=np.float64).reshape(3, 6)
+    out = {}
+    with np.errstate(divide='ignore', invalid='ignore'):
+        for k, name in enumerate(MASK_ROWS):
+            bg = c[k, 0] / (c[k, 0] + c[k, 1] + c[k, 2])
+            fg = c[k, 3] / (c[k, 3] + c[k, 4] + c[k, 5])
+            out[name] = ((bg + fg) / 2, bg, fg)
+    return out
 
 
 # ------------------------------------------------------------------------------------------------------------------- readers
@@ -236,6 +360,97 @@ class KittiOdometry(object):
         return sum(len(s['first']) for s in self.sequences)
 
 
+def read_raw_calib_file(path):
+    """validation_flow.py:41-55: `key: values` lines; every value that parses as floats becomes an array, the rest is dropped."""
+    data = {}
+    with open(str(path), 'r') as f:
+        for line in f.readlines():
+            key, value = line.split(':', 1)
+            try:
+                data[key] = np.array([float(x) for x in value.split()])
+            except ValueError:
+                pass
+    return data
+
+
+def _imread_gray(path):
+    from PIL import Image
+    with Image.open(str(path)) as im:
+        return np.array(im)
+
+
+class Kitti2015Flow(object):
+    """The KITTI 2015 scene-flow tree as ValidationFlow / ValidationMask read it (datasets/validation_flow.py:95-185): target
+    frame data_scene_flow_multiview/<phase>/image_2/<index>_10.png, reference frames _08 _09 _11 _12 at sequence_length 5
+    (seq_ids), ground truth data_scene_flow/<phase>/<occ>/<index>_10.png, calibration
+    data_scene_flow_calib/<phase>/calib_cam_to_cam/<index>.txt, obj_map data_scene_flow/<phase>/obj_map/<index>_10.png and, with
+    with_semantic, semantic_labels/<phase>/semantic/<index>_10.png.  Item i -> dict of what the files hold: 'tgt' / 'ref' uint8
+    [H,W,3] frames, 'intrinsics' = P_rect_02[:, :3] as float32, 'flow_path' (decoded on the device: read_flow_png), 'obj_map'
+    [H,W] as stored (ones where the file is missing, :121-124) and 'semantic' [H,W] or None.  `kitti2015_item` turns an item
+    into the reference loader's tuple."""
+
+    def __init__(self, root, sequence_length=5, phase='training', occ='flow_occ', N=200, with_semantic=False):
+        self.root = pathlib.Path(root)
+        self.sequence_length, self.phase, self.occ, self.N, self.with_semantic = sequence_length, phase, occ, N, with_semantic
+        seq_ids = list(range(-int(sequence_length / 2), int(sequence_length / 2) + 1))
+        seq_ids.remove(0)
+        self.seq_ids = [x + 10 for x in seq_ids]
+
+    def paths(self, index):
+        name = str(index).zfill(6)
+        multiview = self.root / 'data_scene_flow_multiview' / self.phase / 'image_2'
+        flow = self.root / 'data_scene_flow' / self.phase
+        return {'tgt': multiview / (name + '_10.png'),
+                'ref': [multiview / (name + '_' + str(k).zfill(2) + '.png') for k in self.seq_ids],
+                'flow': flow / self.occ / (name + '_10.png'),
+                'calib': self.root / 'data_scene_flow_calib' / self.phase / 'calib_cam_to_cam' / (name + '.txt'),
+                'obj_map': flow / 'obj_map' / (name + '_10.png'),
+                'semantic': self.root / 'semantic_labels' / self.phase / 'semantic' / (name + '_10.png')}
+
+    def __getitem__(self, index):
+        if not 0 <= index < self.N:
+            raise IndexError(index)
+        p = self.paths(index)
+        tgt = imread(p['tgt'])
+        obj_map = _imread_gray(p['obj_map']) if p['obj_map'].is_file() else np.ones(tgt.shape[:2], dtype=np.uint8)
+        P_rect = np.reshape(read_raw_calib_file(p['calib'])['P_rect_02'], (3, 4))
+        return {'tgt': tgt, 'ref': [imread(r) for r in p['ref']], 'intrinsics': P_rect[:, :3].astype('float32'),
+                'flow_path': p['flow'], 'obj_map': obj_map,
+                'semantic': _imread_gray(p['semantic']) if self.with_semantic else None, 'paths': p}
+
+    def __len__(self):
+        return self.N
+
+
+def scale_intrinsics(intrinsics, in_hw, out_hw):
+    """custom_transforms.Scale's intrinsics (custom_transforms.py:133-134) in float32 and np.linalg.inv of the result"""
+    K = np.copy(np.asarray(intrinsics, dtype=np.float32))
+    K[0] *= (out_hw[1] / in_hw[1])
+    K[1] *= (out_hw[0] / in_hw[0])
+    return K, np.linalg.inv(K)
+
+
+def kitti2015_item(sample, img_hw, frames_dev, with_flow=True):
+    """One Kitti2015Flow item as the reference's loader hands it to the loop at batch size 1 (Scale(h, w), ArrayToTensor,
+    Normalize; test_flow.py:78-85): -> (tgt_img [1,3,h,w], ref_imgs, intrinsics [1,3,3], intrinsics_inv, flow_gt [1,3,Hg,Wg] or
+    None, obj_map_gt [1,Hg,Wg] fp32, semantic uint8 [Hg,Wg] or None), all on frames_dev's device.  Scale ALWAYS calls imresize
+    (custom_transforms.py:135), so every float frame is byte-scaled to its own min..max even at an equal size; the resize, the
+    division by 255 and the normalisation run on the device (DeviceFrames.resize_crop)."""
+    from .custom_transforms import _bytescale
+    dev = frames_dev.device
+    frames = [sample['tgt']] + list(sample['ref'])
+    u8 = np.stack([_bytescale(np.asarray(f, dtype=np.float32)) for f in frames])
+    x = frames_dev.resize_crop(u8, tuple(img_hw), tuple(img_hw))
+    K, Kinv = scale_intrinsics(sample['intrinsics'], sample['tgt'].shape[:2], img_hw)
+    flow_gt = read_flow_png(sample['flow_path'], dev)[None] if with_flow else None
+    obj_map = torch.from_numpy(np.ascontiguousarray(sample['obj_map'], dtype=np.float32)).to(dev)[None]
+    sem = None
+    if sample['semantic'] is not None:
+        sem = torch.from_numpy(np.where(np.asarray(sample['semantic']) == 26, 26, 0).astype(np.uint8)).to(dev)
+    return (x[:1], [x[k:k + 1] for k in range(1, x.shape[0])], torch.from_numpy(K).to(dev)[None],
+            torch.from_numpy(Kinv).to(dev)[None], flow_gt, obj_map, sem)
+
+
 # ---------------------------------------------------------------------------------------------------------- evaluation loops
 def _device_of(net):
     return next(net.parameters()).device
@@ -352,6 +567,70 @@ def pose_statistics(errors, n_rows=None):
     return {'mean': E.mean(0), 'std': E.std(0)}
 
 
+def evaluate_flow(disp_net, pose_net, mask_net, flow_net, framework, THRESH=0.01, flownet='Back2Future', img_hw=(256, 832)):
+    """test_flow.py:main without argparse over a Kitti2015Flow framework -> (errors [8] fp64 numpy, FLOW_ERROR_NAMES): EPE of
+    the composed flow over all / static / moving pixels and Fl, with the predicted rigidity mask and with the ground-truth object
+    map.  test_flow.py:108-146 is the loop of train.py:650-748 statement for statement (and has no spatial_normalize), so the
+    items go through validate.validate_flow_with_gt unchanged: one launch for the composition, one for the eight errors, one
+    host read-back after the loop.  The ground-truth PNG is inflated on the host and unfiltered on the device."""
+    from . import validate as V
+    from .custom_transforms import DeviceFrames
+    frames_dev = DeviceFrames(device=_device_of(disp_net))
+
+    def items():
+        for i in range(len(framework)):
+            yield kitti2015_item(framework[i], img_hw, frames_dev)[:6]
+
+    args = types.SimpleNamespace(THRESH=THRESH, flownet=flownet, spatial_normalize=False)
+    errors, _ = V.validate_flow_with_gt(items(), disp_net, pose_net, mask_net, flow_net, args=args)
+    return np.asarray(errors, dtype=np.float64), list(FLOW_ERROR_NAMES)
+
+
+def mask_sample_outputs(disp_net, pose_net, mask_net, flow_net, item, flownet='Back2Future'):
+    """test_mask.py:119-127 for one loader item: the four forward passes and pose2flow -> (explainability_mask, flow_cam,
+    flow_fwd)"""
+    from .inverse_warp import pose2flow
+    tgt_img, ref_imgs, intrinsics, intrinsics_inv = item[:4]
+    depth = 1 / disp_net(tgt_img)
+    pose = _pose_of(pose_net(tgt_img, ref_imgs))
+    explainability_mask = mask_net(tgt_img, ref_imgs)
+    if flownet == 'Back2Future':
+        flow_fwd = flow_net(tgt_img, ref_imgs[1:3])[0]
+    else:
+        flow_fwd = flow_net(tgt_img, ref_imgs[2])
+    return explainability_mask, pose2flow(depth.squeeze(1), pose[:, 2], intrinsics, intrinsics_inv), flow_fwd
+
+
+def evaluate_mask(disp_net, pose_net, mask_net, flow_net, framework, THRESH=0.94, flownet='Back2Future', img_hw=(256, 832)):
+    """test_mask.py:main without argparse over a Kitti2015Flow framework built with_semantic=True -> dict with 'full', 'census'
+    and 'bare' = (iou, bg_iou, fg_iou) of the combined, the census-only and the bare MaskNet mask (fp64, from the counts summed
+    over the data set as test_mask.py:199-209), 'counts' [3,6] int64 (MASK_ROWS x MASK_COUNT_NAMES) and 'names'.
+
+    Per sample: four forward passes, pose2flow, cc_rigidity_compose_norm and one cc_mask_iou_counts launch that adds the 18
+    counts into one device buffer; the host reads that buffer once, after the loop.  Samples go one at a time, as in the
+    reference, whose .max() (test_mask.py:131) spans the batch."""
+    from .custom_transforms import DeviceFrames
+    nets = (disp_net, pose_net, mask_net, flow_net)
+    for net in nets:
+        net.eval()
+    dev = _device_of(disp_net)
+    frames_dev = DeviceFrames(device=dev)
+    counts = torch.zeros((3, 6), dtype=torch.int64, device=dev)
+    with torch.no_grad():
+        for i in range(len(framework)):
+            sample = framework[i]
+            assert sample['semantic'] is not None, "evaluate_mask: build the framework with with_semantic=True"
+            item = kitti2015_item(sample, img_hw, frames_dev, with_flow=False)
+            r = rigidity_composition_norm(*mask_sample_outputs(*nets, item, flownet), THRESH,
+                                          want=("rigidity_mask", "rigidity_mask_census", "rigidity_mask_combined"))
+            mask_iou_counts((item[5][0] != 0).to(torch.uint8), item[6],
+                            (r.rigidity_mask_combined[0, 0], r.rigidity_mask_census[0, 0], r.rigidity_mask[0, 0]), counts)
+    c = counts.cpu().numpy()                                                             # the one host read-back
+    out = mask_ious(c)
+    out.update(counts=c, names=list(MASK_COUNT_NAMES))
+    return out
+
+
 # ---------------------------------------------------------------------------------------------------------------- command line
 def _load(name, path, dev, **kw):
     from . import models
@@ -408,8 +687,54 @@ def _pose_main(args):
     print("std \t {:10.4f}, {:10.4f}".format(*res['per_snippet']['std']))
 
 
+def _four_nets(args, dev):
+    """test_flow.py:87-99 / test_mask.py:86-98"""
+    disp_net, _ = _load(args.dispnet, args.pretrained_disp, dev)
+    pose_net, _ = _load(args.posenet, args.pretrained_pose, dev, nb_ref_imgs=4)
+    mask_net, _ = _load(args.masknet, args.pretrained_mask, dev, nb_ref_imgs=4)
+    flow_net, _ = _load(args.flownet, args.pretrained_flow, dev, nlevels=args.nlevels)
+    return disp_net, pose_net, mask_net, flow_net
+
+
+def _flow_main(args):
+    dev = torch.device('cuda')
+    framework = Kitti2015Flow(args.kitti_dir, sequence_length=5, N=args.N)
+    errors, names = evaluate_flow(*_four_nets(args, dev), framework, args.THRESH, args.flownet, (args.img_height, args.img_width))
+    print("Results")
+    print("\t {:>10}, {:>10}, {:>10}, {:>6}, {:>10}, {:>10}, {:>10}, {:>10} ".format(*names))
+    print("Errors \t {:10.4f}, {:10.4f}, {:10.4f}, {:10.4f}, {:10.4f}, {:10.4f}, {:10.4f}, {:10.4f}".format(*errors))
+
+
+def _mask_main(args):
+    dev = torch.device('cuda')
+    framework = Kitti2015Flow(args.kitti_dir, sequence_length=5, N=args.N, with_semantic=True)
+    res = evaluate_mask(*_four_nets(args, dev), framework, args.THRESH, args.flownet, (args.img_height, args.img_width))
+    for title, key in (("Results Full Model", 'full'), ("Results Census only", 'census'), ("Results Bare", 'bare')):
+        print(title)
+        print("\t {:>10}, {:>10}, {:>10} ".format('iou', 'bg_iou', 'fg_iou'))
+        print("Errors \t {:10.4f}, {:10.4f} {:10.4f}".format(*res[key]))
+
+
+def _kitti2015_arguments(q, thresh):
+    q.add_argument('--kitti-dir', dest='kitti_dir', type=str, required=True, help='Path to the kitti2015 scene flow dataset')
+    q.add_argument('--dispnet', dest='dispnet', type=str, default='DispResNet6', help='depth network architecture.')
+    q.add_argument('--posenet', dest='posenet', type=str, default='PoseNetB6', help='pose network architecture.')
+    q.add_argument('--masknet', dest='masknet', type=str, default='MaskNet6', help='explainabity mask network architecture.')
+    q.add_argument('--flownet', dest='flownet', type=str, default='Back2Future', help='flow network architecture.')
+    q.add_argument('--THRESH', dest='THRESH', type=float, default=thresh, help='THRESH')
+    q.add_argument('--pretrained-disp', dest='pretrained_disp', required=True, metavar='PATH', help='path to pre-trained dispnet model')
+    q.add_argument('--pretrained-pose', dest='pretrained_pose', required=True, metavar='PATH', help='path to pre-trained posenet model')
+    q.add_argument('--pretrained-flow', dest='pretrained_flow', required=True, metavar='PATH', help='path to pre-trained flownet model')
+    q.add_argument('--pretrained-mask', dest='pretrained_mask', required=True, metavar='PATH', help='path to pre-trained masknet model')
+    q.add_argument('--nlevels', dest='nlevels', type=int, default=6, help='number of levels in multiscale.')
+    q.add_argument('--dataset', dest='dataset', default='kitti2015', choices=['kitti2015'])
+    q.add_argument('--N', dest='N', type=int, default=200, help='number of samples (the training set holds 200)')
+    q.add_argument("--img-height", default=256, type=int, help="Image height")
+    q.add_argument("--img-width", default=832, type=int, help="Image width")
+
+
 def parser():
-    p = argparse.ArgumentParser(description='KITTI depth (Eigen split) and odometry evaluation on the device')
+    p = argparse.ArgumentParser(description='KITTI depth (Eigen split), odometry, 2015 flow and motion-segmentation evaluation on the device')
     sub = p.add_subparsers(dest='command', required=True)
     d = sub.add_parser('depth', help='test_disp.py: Eigen-split depth errors against velodyne ground truth')
     d.add_argument("--dispnet", dest='dispnet', type=str, default='DispResNet6', help='dispnet architecture')
@@ -434,15 +759,14 @@ def parser():
     q.add_argument("--dataset-dir", default='.', type=str, help="KITTI odometry directory")
     q.add_argument("--sequences", default=['09'], type=str, nargs='*', help="sequences to test")
     q.add_argument("--rotation-mode", default='euler', choices=['euler', 'quat'], type=str)
+    _kitti2015_arguments(sub.add_parser('flow', help='test_flow.py: KITTI 2015 EPE all / static / moving and Fl'), 0.01)
+    _kitti2015_arguments(sub.add_parser('mask', help='test_mask.py: motion-segmentation IoU (full, census only, bare)'), 0.94)
     return p
 
 
 def main(argv=None):
     args = parser().parse_args(argv)
-    if args.command == 'depth':
-        _depth_main(args)
-    else:
-        _pose_main(args)
+    {'depth': _depth_main, 'pose': _pose_main, 'flow': _flow_main, 'mask': _mask_main}[args.command](args)
 
 
 if __name__ == '__main__':

@@ -526,6 +526,33 @@ int cc_eigen_errors(const float* gt, const float* pred, int H, int W, double min
 int cc_pose_snippet_errors(const float* pred, const double* gt_seq, const int* first, int S, int L, int F, int step,
                            int rotation_mode, double* err, double* final_or_null, void* stream);
 
+/* ---------------------------------------------------------------- KITTI 2015 flow and mask evaluation (test_flow.py, test_mask.py)
+ * Same contract again: no allocation, no host synchronisation, integer atomics only (an unsigned maximum of fp32 bit patterns,
+ * 64-bit count sums), `ws` sized by the *_ws query and cleared by a kernel on the stream; every entry can be captured.
+ *
+ * cc_png16_flow_decode: the KITTI flow ground truth (flowutils/flow_io.py:96-117) of N non-interlaced 16-bit RGB PNGs of one
+ * size from their inflated scanlines: ftype [N,H] uint8 the filter byte of every row, rows [N,H,stride] uint8 the 6*W filtered
+ * bytes of every row padded to stride (a multiple of 8).  All five filter types are undone (bytes per pixel = 6) ->
+ * gt [N,3,H,W] fp32 = (R - 32768) / 64, (G - 32768) / 64, B.  W <= 8000. */
+int cc_png16_flow_decode(const unsigned char* ftype, const unsigned char* rows, int N, int H, int W, int stride, float* gt,
+                         void* stream);
+/* cc_rigidity_compose_norm: test_mask.py:129-138 per sample: exp_mask [B,MC>=3,H,W], flow_cam / flow_fwd [B,2,H,W] ->
+ * bare [B,1,H,W] = (1 - (1-exp[:,1])(1-exp[:,2]) > 0.5), census [B,1,H,W] = (1 - |flow_cam - flow_fwd|_2 / max over the sample
+ * > thresh), combined [B,1,H,W] = 1 - (1-bare)(1-census) (masks as 0/1 fp32, bit-exact with torch), flow_non_rigid =
+ * (1-combined) flow_fwd, flow_rigid = combined flow_cam, total_flow their sum [B,2,H,W].  Every output may be NULL.  A sample
+ * whose maximum is 0 or that holds a NaN gets an all-zero census mask.  ws: cc_rigidity_compose_norm_ws(B) bytes. */
+size_t cc_rigidity_compose_norm_ws(int B);
+int cc_rigidity_compose_norm(const float* exp_mask, int MC, const float* flow_cam, const float* flow_fwd, float* bare,
+                             float* census, float* combined, float* flow_non_rigid, float* flow_rigid, float* total_flow,
+                             float thresh, int B, int H, int W, void* ws, void* stream);
+/* cc_mask_iou_counts: mask_error (test_mask.py:224-262) of up to three predicted masks pred0..2 [h,w] fp32 (NULL: skipped)
+ * against obj_map / semantic [Hg,Wg] uint8: label = 255 (ignored) where semantic != 26, else obj_map != 0; the prediction at
+ * ground-truth pixel (i, j) is scipy.ndimage.zoom(order=0)'s pred[floor(i*zy + 0.5), floor(j*zx + 0.5)] with zy = (h-1)/(Hg-1),
+ * zx = (w-1)/(Wg-1) in fp64 (0 where the product exceeds the last index); class = (m >= 1 - m ? 0 : 1).  The call ADDS into
+ * counts [3,6] unsigned 64-bit: per mask tp, fp, fn of class 0, then of class 1.  h, w, Hg, Wg >= 2. */
+int cc_mask_iou_counts(const unsigned char* obj_map, const unsigned char* semantic, int Hg, int Wg, const float* pred0,
+                       const float* pred1, const float* pred2, int h, int w, unsigned long long* counts, void* stream);
+
 /* ---------------------------------------------------------------- optimizer (train.py:307-310,568)
  * torch.optim.Adam(betas, eps, weight_decay=0) on the flat fp32 bucket; grads are multiplied by grad_scale first
  * (1/world_size after the RCCL all-reduce).  step_dev: device float, incremented by the call. */

@@ -13,6 +13,7 @@
 #   sq                SQ counter pass (tools/pmc_sq.py)
 #   mfma              MFMA utilisation of the conv kernels (tools/pmc_mfma.py; run prof0 first for the durations)
 #   layers            per-layer-shape table (tools/layer_rates.py)
+#   flowprof          rocprofv3 --kernel-trace --stats (no counters) of a short KITTI 2015 mask + flow evaluation (tools/kitti_flow_profile.py)
 #   ab:VAR=VAL[,VAR=VAL...]   same-box A/B against the default (tools build of the library; default run first and last)
 #   py:SCRIPT[:ARGS]  python tools/SCRIPT ARGS  (probes: wino_bench.py, conv_bench.py, ...)
 TAG=$1; shift
@@ -109,6 +110,12 @@ for STEP in "$@"; do
     # (the table comes from bench.py's isolated pass: side streams off)
     ( CC_TIMING_DETAIL=1 CC_TIMING_DUMP=$O/layers_$TAG.tsv timeout 400 python bench.py --full --steps 5 --warmup 3 --no-cpu-baseline ) > $O/bench_${TAG}_layers.log 2> $O/bench_${TAG}_layers.err
     python tools/layer_rates.py $O/layers_$TAG.tsv > $O/layer_rates_$TAG.txt; head -${LAYER_ROWS:-40} $O/layer_rates_$TAG.txt | cut -c1-170 ;;
+  flowprof)
+    ( cd /tmp && timeout 500 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_flow_$TAG -o flow -- python $R/tools/kitti_flow_profile.py ) > $O/rocprof_flow_$TAG.log 2>&1; echo "rocprof rc=$?"
+    S=$(find $O/prof_flow_$TAG -name "*kernel_stats.csv" | head -1)
+    [ -n "$S" ] && cp "$S" $O/rocprof_kernel_stats_flow_$TAG.csv && grep -E "^\"?Name|png16|census_max|compose_norm|mask_iou|zero_u32" "$S" | cut -c1-200
+    grep -E "^pass|^host|^device|^counts" $O/rocprof_flow_$TAG.log
+    find $O/prof_flow_$TAG -name "*kernel_trace.csv" -size +20M -delete ;;
   ab)
     export CC_LIB_PATH=${CC_LIB_PATH:-$TOOLS_LIB}
     IFS=';' read -ra VARS <<< "$A"
