@@ -15,6 +15,7 @@ MI355X-first structure around that body:
     passes.  Only the last finisher's exchange is exposed; on one GPU the optimizer and the weight-image refresh leave the
     critical path the same way.
 """
+import collections.abc
 import contextlib
 
 import torch
@@ -35,6 +36,7 @@ class StepConfig:
         self.THRESH, self.qch, self.lambda_oob = 0.01, 0.5, 0.0
         self.smoothness_type = "edgeaware"
         self.lr, self.betas = 1e-4, (0.9, 0.999)
+        self.weight_decay, self.eps = 0.0, 1e-8                                    # --weight-decay; torch.optim.Adam's default eps
         for k, v in kw.items():
             assert hasattr(self, k), k
             setattr(self, k, v)
@@ -226,12 +228,62 @@ class _SideStreamWork:
         torch.cuda.current_stream().wait_stream(self.side)
 
 
+NET_NAMES = ("disp", "pose", "mask", "flow")
+
+
+def _capture_in_progress(t):
+    """is the current stream of tensor t's device being captured into a hipGraph?  (a host write of the hyperparameter table
+    cannot become part of a capture: the copy would be replayed with the values of capture time)"""
+    return bool(t.is_cuda and torch.cuda.is_current_stream_capturing())
+
+
+class _HyperGroup(collections.abc.MutableMapping):
+    """One entry of ``FlatAdam.param_groups``: the view of a network's row of the hyperparameter table that a torch schedule loop
+    expects (``for g in optimizer.param_groups: g['lr'] = ...``).  Writes go through to the table."""
+    KEYS = ("lr", "betas", "eps", "weight_decay", "amsgrad", "params")
+
+    def __init__(self, opt, net):
+        self._opt, self.net = opt, net
+
+    def __getitem__(self, k):
+        if k == "amsgrad":
+            return False
+        if k == "params":
+            return self._opt.params_of(self.net)
+        if k not in self.KEYS:
+            raise KeyError(k)
+        return self._opt.hyper_of(self.net)[k]
+
+    def __setitem__(self, k, v):
+        if k not in ("lr", "betas", "eps", "weight_decay"):
+            raise KeyError("param group key %r cannot be assigned (lr, betas, eps, weight_decay can)" % (k,))
+        self._opt.set_hyper(self.net, **{k: v})
+
+    def __delitem__(self, k):
+        raise TypeError("the keys of a FlatAdam param group are fixed")
+
+    def __iter__(self):
+        return iter(self.KEYS)
+
+    def __len__(self):
+        return len(self.KEYS)
+
+    def __repr__(self):
+        return "_HyperGroup(%s: %r)" % (self.net, self._opt.hyper_of(self.net))
+
+
 class FlatAdam:
-    """train.py:307-310 ``torch.optim.Adam(chain(all params), lr, betas)`` as ONE flat bucket + fused kernels.
+    """train.py:307-310 ``torch.optim.Adam(chain(all params), lr, betas, weight_decay)`` as ONE flat bucket + fused kernels.
+
+    Hyperparameters: one row {lr, beta1, beta2, eps, weight_decay, 0, 0, 0} per entry of `nets` in a small DEVICE table that the
+    kernels read (`hyper_dev`; `bounds_dev` = where each row's elements start in the bucket), with a host mirror: a write
+    (`set_hyper`, `param_groups[k]['lr'] = ..`, `opt.lr = ..`, `load_state_dict`) marks the table dirty and the next step uploads it
+    with one stream-ordered copy, so a step captured into a hipGraph follows an lr schedule and per-network values without being
+    captured again.
 
     Bucket layout: the parameters in train.py:305's chain order (DispResNet6 | PoseNetB6 | MaskNet6 | Back2Future), every NETWORK's
     range starting on a 256-byte boundary (<= 63 zero floats of padding between two networks: zero gradient, zero update), so that
-    each network is a segment that can be exchanged (RCCL), updated (cc_adam_step_segment, float4) and re-imaged on its own."""
+    each network is a segment that can be exchanged (RCCL), updated (cc_adam_step_segment_hyper with the network's row of the table, float4) and re-imaged on its own."""
     ALIGN = 64          # floats
 
     def __init__(self, nets, cfg):
@@ -266,7 +318,26 @@ class FlatAdam:
             self.flat_p[off:off + k].copy_(p.data.reshape(-1))
             p.data = self.flat_p[off:off + k].view_as(p.data)
             p.grad = self.flat_g[off:off + k].view_as(p.data)
-        self.lr, self.betas = cfg.lr, cfg.betas
+        # hyperparameter table: row index = network index (an absent network keeps an unused, empty row); a row owns its network's
+        # segment, padding included (zero parameter, zero gradient: stays zero with weight decay too)
+        rows = len(per_net)
+        b = [size] * (rows + 1)
+        for i in reversed(range(rows)):
+            b[i] = self.net_ranges[i][0] if self.net_ranges[i] is not None else b[i + 1]
+        assert b[0] == 0 and all(x % self.ALIGN == 0 for x in b)
+        self.bounds = b
+        # per network: the indices (into `params`, the chain order) of its parameters -- the `params` of its param group
+        counts = [len(ps) for ps in per_net]
+        self._param_index = [list(range(sum(counts[:i]), sum(counts[:i + 1]))) for i in range(rows)]
+        self.bounds_dev = torch.tensor(b, dtype=torch.int64).to(dev)
+        self.hyper_dev = torch.zeros(rows, 8, device=dev, dtype=torch.float32)
+        self._hyper = [{"lr": cfg.lr, "betas": tuple(cfg.betas), "eps": cfg.eps, "weight_decay": cfg.weight_decay} for _ in range(rows)]
+        self._hyper_host = torch.zeros(rows, 8, dtype=torch.float32)       # what the upload reads: page-locked on a HIP device
+        if dev.type == "cuda":
+            self._hyper_host = self._hyper_host.pin_memory()
+        self._hyper_copied = None                                          # event behind the most recent upload
+        self._hyper_dirty = True
+        self.param_groups = [_HyperGroup(self, i) for i in range(rows) if self.net_ranges[i] is not None]
         # conv weights / biases: the wgrad and bias-gradient kernels accumulate straight into the flat bucket
         # (the trainer switches ops.grad_sinks to this table for the duration of its own forward+backward only)
         self.sinks = {p.data_ptr(): p.grad for p in params}
@@ -347,37 +418,146 @@ class FlatAdam:
     def grad_scale(self):
         return 1.0 / self.world()
 
+    # ------------------------------------------------------------------------------------------------ hyperparameters
+    def _row(self, net):
+        if isinstance(net, str):
+            if net not in NET_NAMES[:len(self._hyper)]:
+                raise KeyError("no network %r (one of %s, or an index)" % (net, ", ".join(NET_NAMES[:len(self._hyper)])))
+            return NET_NAMES.index(net)
+        i = int(net)
+        if not 0 <= i < len(self._hyper):
+            raise IndexError("network index %d out of range (%d networks)" % (i, len(self._hyper)))
+        return i
+
+    def set_hyper(self, net=None, *, lr=None, betas=None, eps=None, weight_decay=None):
+        """Set hyperparameters of one network's row (`net`: an index or one of NET_NAMES) or of all rows (None); arguments left
+        None keep their values.  Takes effect with the next step, captured or not."""
+        if _capture_in_progress(self.hyper_dev):
+            raise RuntimeError("FlatAdam: hyperparameters cannot be changed while a hipGraph capture is in progress "
+                               "(the captured step reads them from device memory: set them before or after the capture)")
+        new = {}
+        if lr is not None:
+            new["lr"] = float(lr)
+        if betas is not None:
+            b1, b2 = betas
+            new["betas"] = (float(b1), float(b2))
+        if eps is not None:
+            new["eps"] = float(eps)
+        if weight_decay is not None:
+            new["weight_decay"] = float(weight_decay)
+        for i in (range(len(self._hyper)) if net is None else [self._row(net)]):
+            self._hyper[i].update(new)
+        self._hyper_dirty = True
+
+    def hyper_of(self, net):
+        """{'lr', 'betas', 'eps', 'weight_decay'} of one network's row"""
+        return dict(self._hyper[self._row(net)])
+
+    def params_of(self, net):
+        """the indices (into `params`, the chain order) of one network's parameters"""
+        return list(self._param_index[self._row(net)])
+
+    def _present(self):
+        return [i for i, r in enumerate(self.net_ranges) if r is not None]
+
+    def _uniform(self):
+        rows = [self._hyper[i] for i in self._present()]
+        return all(h == rows[0] for h in rows)
+
+    def _common(self, key):
+        if any(self._hyper[i][key] != self._hyper[self._present()[0]][key] for i in self._present()):
+            raise ValueError("FlatAdam.%s: the networks have different values (%s): read them per network with hyper_of() / "
+                             "param_groups" % (key, ", ".join("%s=%r" % (NET_NAMES[i] if i < len(NET_NAMES) else i, self._hyper[i][key])
+                                                              for i in self._present())))
+        return self._hyper[self._present()[0]][key]
+
+    lr = property(lambda self: self._common("lr"), lambda self, v: self.set_hyper(lr=v))
+    betas = property(lambda self: self._common("betas"), lambda self, v: self.set_hyper(betas=v))
+
+    def flush_hyper(self):
+        """Upload the table if a write is pending: one small copy from the (pinned) host mirror, ordered on the current stream.
+        Never inside a capture -- CCTrainer.capture() flushes before it begins."""
+        if not self._hyper_dirty or _capture_in_progress(self.hyper_dev):
+            return
+        if self._hyper_copied is not None:
+            self._hyper_copied.synchronize()         # the previous upload has read the host buffer (long ago: a no-op)
+        for i, h in enumerate(self._hyper):
+            self._hyper_host[i, :5] = torch.tensor([h["lr"], h["betas"][0], h["betas"][1], h["eps"], h["weight_decay"]],
+                                                   dtype=torch.float64)
+        self.hyper_dev.copy_(self._hyper_host, non_blocking=True)
+        if self.hyper_dev.is_cuda:
+            self._hyper_copied = torch.cuda.Event()
+            self._hyper_copied.record()
+        self._hyper_dirty = False
+
     def step(self, grad_scale=1.0):
-        engine().call("cc_adam_step", self.flat_p, self.flat_g, self.exp_avg, self.exp_avg_sq, self.step_dev, self.flat_p.numel(),
-                      float(self.lr), float(self.betas[0]), float(self.betas[1]), 1e-8, float(grad_scale), STREAM)
+        """The update of the whole bucket, every network with its own row."""
+        self.flush_hyper()
+        engine().call("cc_adam_step_hyper", self.flat_p, self.flat_g, self.exp_avg, self.exp_avg_sq, self.step_dev,
+                      self.flat_p.numel(), self.hyper_dev, self.bounds_dev, len(self._hyper), float(grad_scale), STREAM)
 
     def tick(self):
         """advance the step counter alone (the segments of this step then update with tick = 0, from any stream)"""
         engine().call("cc_adam_tick", self.step_dev, STREAM)
 
     def step_segment(self, lo, hi, tick, grad_scale=1.0):
-        """The update of elements [lo, hi) of the bucket (lo % 4 == 0); tick: advance the step counter (first segment only)."""
+        """The update of elements [lo, hi) of the bucket (lo % 4 == 0); tick: advance the step counter (first segment only).
+        A range may span several networks' rows (the two segments of the legacy data-parallel forms hold two networks each): it
+        becomes one launch per row it touches, each with that row's hyperparameters."""
         hi = self.flat_p.numel() if hi is None else hi
         assert lo % 4 == 0 and 0 <= lo < hi <= self.flat_p.numel()
-        engine().call("cc_adam_step_segment", self.flat_p[lo:hi], self.flat_g[lo:hi], self.exp_avg[lo:hi], self.exp_avg_sq[lo:hi],
-                      self.step_dev, hi - lo, float(self.lr), float(self.betas[0]), float(self.betas[1]), 1e-8, float(grad_scale),
-                      int(tick), STREAM)
+        self.flush_hyper()
+        # one launch per row the range touches (the per-network pipeline's ranges lie inside one network's segment; the two
+        # segments of the legacy forms hold two networks each)
+        for i in range(len(self._hyper)):
+            a, b = max(lo, self.bounds[i]), min(hi, self.bounds[i + 1])
+            if a < b:
+                engine().call("cc_adam_step_segment_hyper", self.flat_p[a:b], self.flat_g[a:b], self.exp_avg[a:b],
+                              self.exp_avg_sq[a:b], self.step_dev, b - a, self.hyper_dev[i], float(grad_scale), int(tick), STREAM)
+                tick = False
 
     def state_dict(self):
         """The layout of ``torch.optim.Adam.state_dict()`` (what train.py:408-410 stores in optimizer_checkpoint.pth.tar):
-        per-parameter ``step`` / ``exp_avg`` / ``exp_avg_sq`` cut out of the flat buckets, one param group."""
+        per-parameter ``step`` / ``exp_avg`` / ``exp_avg_sq`` cut out of the flat buckets; one param group when all networks have
+        the same hyperparameters, else one per network (``params`` = the index range of its parameters), which a
+        ``torch.optim.Adam`` built with the same groups loads."""
         state = {}
         for i, (p, off) in enumerate(zip(self.params, self.offsets)):
             k = p.numel()
             state[i] = {"step": self.step_dev.detach().clone().reshape(()),
                         "exp_avg": self.exp_avg[off:off + k].view_as(p).clone(),
                         "exp_avg_sq": self.exp_avg_sq[off:off + k].view_as(p).clone()}
-        group = {"lr": self.lr, "betas": tuple(self.betas), "eps": 1e-8, "weight_decay": 0, "amsgrad": False,
-                 "params": list(range(len(self.params)))}
-        return {"state": state, "param_groups": [group]}
+        def group(i, params):
+            h = self._hyper[i]
+            return {"lr": h["lr"], "betas": tuple(h["betas"]), "eps": h["eps"], "weight_decay": h["weight_decay"], "amsgrad": False,
+                    "params": params}
+        if self._uniform():
+            groups = [group(self._present()[0], list(range(len(self.params))))]
+        else:
+            groups = [group(i, self.params_of(i)) for i in self._present()]
+        return {"state": state, "param_groups": groups}
 
     def load_state_dict(self, sd):
-        """Accepts a ``torch.optim.Adam`` state dict over the same parameter order (chain of the four nets)."""
+        """Accepts a ``torch.optim.Adam`` state dict over the same parameter order (chain of the four nets): one param group, or one
+        per trainable network that together partition the parameters in chain order.  The groups' hyperparameters are written
+        to the table, so they hold from the next step on -- of a captured trainer too."""
+        if _capture_in_progress(self.hyper_dev):
+            raise RuntimeError("FlatAdam.load_state_dict: a hipGraph capture is in progress")
+        groups = sd["param_groups"]
+        present = self._present()
+        if len(groups) == 1:
+            want = [list(range(len(self.params)))]
+        elif len(groups) == len(present):
+            want = [self.params_of(i) for i in present]
+        else:
+            raise ValueError("FlatAdam.load_state_dict: %d param groups; expected 1 or one per trainable network (%d)"
+                             % (len(groups), len(present)))
+        for g, w in zip(groups, want):
+            if list(g["params"]) != w:
+                raise ValueError("FlatAdam.load_state_dict: a param group holds parameters %s, expected %d..%d (one group, or the "
+                                 "networks' parameters in chain order)" % (list(g["params"])[:4] + ["..."], w[0], w[-1]))
+            if g.get("amsgrad", False) or g.get("maximize", False):
+                raise ValueError("FlatAdam.load_state_dict: amsgrad / maximize are not supported")
         for i, (p, off) in enumerate(zip(self.params, self.offsets)):
             k = p.numel()
             st = sd["state"].get(i)
@@ -385,8 +565,9 @@ class FlatAdam:
                 self.exp_avg[off:off + k].copy_(st["exp_avg"].reshape(-1))
                 self.exp_avg_sq[off:off + k].copy_(st["exp_avg_sq"].reshape(-1))
                 self.step_dev.fill_(float(st["step"]))
-        g = sd["param_groups"][0]
-        self.lr, self.betas = g["lr"], tuple(g["betas"])
+        for k, g in enumerate(groups):
+            self.set_hyper(None if len(groups) == 1 else present[k], lr=g["lr"], betas=tuple(g["betas"]),
+                           eps=g.get("eps", 1e-8), weight_decay=g.get("weight_decay", 0.0))
 
     def broadcast_from_rank0(self):
         """Start-up: every rank continues from rank 0's parameters AND buffers (a --resume that only rank 0 read from disk, per-rank
@@ -395,9 +576,6 @@ class FlatAdam:
             dist.broadcast(self.flat_p, 0)
             for t in self.extra_state:
                 dist.broadcast(t.data, 0)
-
-
-NET_NAMES = ("disp", "pose", "mask", "flow")
 
 
 class CCTrainer:
@@ -757,6 +935,7 @@ class CCTrainer:
         """Warm up eagerly on a side stream, then capture forward+backward of one step into a hipGraph."""
         assert not config.strict_nan_checks, "config.strict_nan_checks syncs the host per loss term: use use_graph=False with it"
         tgt, refs, K, Kinv = batch
+        self.opt.flush_hyper()              # the captured Adam launches READ the table; its upload is not part of the graph
         self.static_batch = (tgt.clone(), [r.clone() for r in refs], K.clone(), Kinv.clone())
         # the eager warm-up passes must leave no trace: BatchNorm running statistics / num_batches_tracked would otherwise
         # absorb the first batch three times where the reference absorbs it once (train.py:454 runs each batch once) -- and the
@@ -916,6 +1095,7 @@ class CCTrainer:
 
     def step(self, batch):
         """train.py:445-568 for one mini-batch: returns the (device) loss tensors of this step."""
+        self.opt.flush_hyper()              # pending lr / betas / eps / weight-decay writes: in front of the replay, on this stream
         if self.pipeline == "per_network":
             if self._weights_touched():
                 ops.packs.mark_stale()

@@ -565,6 +565,16 @@ int cc_adam_step_segment(float* params, const float* grads, float* exp_avg, floa
 /* step_dev += 1 alone: the per-network pipeline (cc_amd/trainer.py, round 6) advances the counter ONCE at the start of the step and
  * then updates the networks' bucket segments with tick = 0 from different streams, as their gradients arrive. */
 int cc_adam_tick(float* step_dev, void* stream);
+/* The same update with the hyperparameters in DEVICE memory, so that a launch captured into a hipGraph follows values the host
+ * writes between two replays, and with weight decay (torch.optim.Adam's L2 form: g += weight_decay * p, p before the update;
+ * weight_decay == 0 and equal values: the same bits as the entries above).  hyper: [rows, 8] floats, row = {lr, beta1, beta2,
+ * eps, weight_decay, 0, 0, 0}.  bounds: [rows + 1] longs, row r owns elements [bounds[r], bounds[r + 1]) of the bucket (an empty
+ * row: equal bounds); bounds[0] = 0, ascending, every bound a multiple of 4 floats but the last one (= n). */
+int cc_adam_step_hyper(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, float* step_dev, long n,
+                       const float* hyper, const long* bounds, int rows, float grad_scale, void* stream);
+/* ... on a sub-range that lies inside ONE row (base pointers of the range, hyper_row = hyper + 8 * row); tick as above. */
+int cc_adam_step_segment_hyper(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, float* step_dev, long n,
+                               const float* hyper_row, float grad_scale, int tick, void* stream);
 int cc_fill(float* p, long n, float value, void* stream);
 
 #ifdef __cplusplus
