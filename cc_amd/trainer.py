@@ -17,6 +17,7 @@ MI355X-first structure around that body:
 """
 import collections.abc
 import contextlib
+import ctypes
 
 import torch
 import torch.distributed as dist
@@ -37,6 +38,9 @@ class StepConfig:
         self.smoothness_type = "edgeaware"
         self.lr, self.betas = 1e-4, (0.9, 0.999)
         self.weight_decay, self.eps = 0.0, 1e-8                                    # --weight-decay; torch.optim.Adam's default eps
+        # gradient guard inside the step, per network (FlatAdam): None = off; a float > 0 = clip every network's gradient to that
+        # L2 norm and skip a network's update when its gradient holds a NaN / Inf; float('inf') = norms + skip, no clipping
+        self.max_grad_norm = None
         for k, v in kw.items():
             assert hasattr(self, k), k
             setattr(self, k, v)
@@ -244,6 +248,8 @@ class _HyperGroup(collections.abc.MutableMapping):
 
     def __init__(self, opt, net):
         self._opt, self.net = opt, net
+        if opt.guard:                        # (an instance attribute: a guard-off optimizer's groups have exactly today's keys)
+            self.KEYS = self.KEYS[:4] + ("max_grad_norm",) + self.KEYS[4:]
 
     def __getitem__(self, k):
         if k == "amsgrad":
@@ -255,7 +261,7 @@ class _HyperGroup(collections.abc.MutableMapping):
         return self._opt.hyper_of(self.net)[k]
 
     def __setitem__(self, k, v):
-        if k not in ("lr", "betas", "eps", "weight_decay"):
+        if k not in ("lr", "betas", "eps", "weight_decay") + (("max_grad_norm",) if self._opt.guard else ()):
             raise KeyError("param group key %r cannot be assigned (lr, betas, eps, weight_decay can)" % (k,))
         self._opt.set_hyper(self.net, **{k: v})
 
@@ -281,10 +287,17 @@ class FlatAdam:
     with one stream-ordered copy, so a step captured into a hipGraph follows an lr schedule and per-network values without being
     captured again.
 
+    Gradient guard (StepConfig.max_grad_norm, default None = off: not a launch, not a byte more than without it): per network, on
+    the device, in front of its update -- the L2 norm of its (all-reduced) gradient, clipping to the row's max_grad_norm
+    (table slot 5, settable like lr), and no update at all for a network whose gradient holds a NaN / Inf: parameters, moments and
+    that network's effective step count stay as they are (`guard_dev`, `grad_stats()`).  Equals ``clip_grad_norm_(net.parameters(),
+    max_norm)`` once per network plus an ``optimizer.step()`` that leaves that network's group out.
+
     Bucket layout: the parameters in train.py:305's chain order (DispResNet6 | PoseNetB6 | MaskNet6 | Back2Future), every NETWORK's
     range starting on a 256-byte boundary (<= 63 zero floats of padding between two networks: zero gradient, zero update), so that
     each network is a segment that can be exchanged (RCCL), updated (cc_adam_step_segment_hyper with the network's row of the table, float4) and re-imaged on its own."""
     ALIGN = 64          # floats
+    GUARD_BLOCKS = 1024 # CC_GRAD_GUARD_MAX_BLOCKS (include/ccengine.h): fp64 partials per network
 
     def __init__(self, nets, cfg):
         per_net = [([p for p in n.parameters() if p.requires_grad] if n is not None else []) for n in nets]
@@ -332,6 +345,19 @@ class FlatAdam:
         self.bounds_dev = torch.tensor(b, dtype=torch.int64).to(dev)
         self.hyper_dev = torch.zeros(rows, 8, device=dev, dtype=torch.float32)
         self._hyper = [{"lr": cfg.lr, "betas": tuple(cfg.betas), "eps": cfg.eps, "weight_decay": cfg.weight_decay} for _ in range(rows)]
+        # gradient guard (cc_amd/csrc/grad_guard.hip): fixed at construction -- its launches are part of a captured step or they are
+        # not.  On: slot 5 of every row holds max_grad_norm, `guard_dev` [rows, 8] = {norm, coef, finite, skipped, 0, 0, 0, 0} of the
+        # most recent step, and every network has partials of its own (the networks' tails run side by side on different streams).
+        # All of it is allocated here, never during a capture.
+        mgn = getattr(cfg, "max_grad_norm", None)
+        self.guard = mgn is not None
+        self.guard_dev = self._partials = None
+        if self.guard:
+            mgn = self._check_max_norm(mgn)
+            for h in self._hyper:
+                h["max_grad_norm"] = mgn
+            self.guard_dev = torch.zeros(rows, 8, device=dev, dtype=torch.float32)
+            self._partials = [torch.zeros(self.GUARD_BLOCKS, device=dev, dtype=torch.float64) for _ in range(rows)]
         self._hyper_host = torch.zeros(rows, 8, dtype=torch.float32)       # what the upload reads: page-locked on a HIP device
         if dev.type == "cuda":
             self._hyper_host = self._hyper_host.pin_memory()
@@ -429,9 +455,21 @@ class FlatAdam:
             raise IndexError("network index %d out of range (%d networks)" % (i, len(self._hyper)))
         return i
 
-    def set_hyper(self, net=None, *, lr=None, betas=None, eps=None, weight_decay=None):
+    @staticmethod
+    def _check_max_norm(v):
+        v = float(v)
+        if not v > 0.0:          # (NaN included)
+            raise ValueError("max_grad_norm must be > 0 (float('inf'): gradient norms and the NaN / Inf skip without clipping), got %r" % (v,))
+        return v
+
+    def set_hyper(self, net=None, *, lr=None, betas=None, eps=None, weight_decay=None, max_grad_norm=None):
         """Set hyperparameters of one network's row (`net`: an index or one of NET_NAMES) or of all rows (None); arguments left
-        None keep their values.  Takes effect with the next step, captured or not."""
+        None keep their values.  Takes effect with the next step, captured or not.  max_grad_norm (> 0, or float('inf') for no
+        clipping) only on an optimizer built with the gradient guard on (StepConfig.max_grad_norm)."""
+        if max_grad_norm is not None and not self.guard:
+            raise ValueError("FlatAdam: max_grad_norm cannot be set: this optimizer was built with the gradient guard off "
+                             "(StepConfig.max_grad_norm = None), the guard's launches are not part of its (captured) step -- "
+                             "build it with StepConfig(max_grad_norm=float('inf')) and set the value afterwards")
         if _capture_in_progress(self.hyper_dev):
             raise RuntimeError("FlatAdam: hyperparameters cannot be changed while a hipGraph capture is in progress "
                                "(the captured step reads them from device memory: set them before or after the capture)")
@@ -445,12 +483,14 @@ class FlatAdam:
             new["eps"] = float(eps)
         if weight_decay is not None:
             new["weight_decay"] = float(weight_decay)
+        if max_grad_norm is not None:
+            new["max_grad_norm"] = self._check_max_norm(max_grad_norm)
         for i in (range(len(self._hyper)) if net is None else [self._row(net)]):
             self._hyper[i].update(new)
         self._hyper_dirty = True
 
     def hyper_of(self, net):
-        """{'lr', 'betas', 'eps', 'weight_decay'} of one network's row"""
+        """{'lr', 'betas', 'eps', 'weight_decay'} of one network's row (and 'max_grad_norm' with the gradient guard on)"""
         return dict(self._hyper[self._row(net)])
 
     def params_of(self, net):
@@ -484,6 +524,8 @@ class FlatAdam:
         for i, h in enumerate(self._hyper):
             self._hyper_host[i, :5] = torch.tensor([h["lr"], h["betas"][0], h["betas"][1], h["eps"], h["weight_decay"]],
                                                    dtype=torch.float64)
+            if self.guard:
+                self._hyper_host[i, 5] = h["max_grad_norm"]
         self.hyper_dev.copy_(self._hyper_host, non_blocking=True)
         if self.hyper_dev.is_cuda:
             self._hyper_copied = torch.cuda.Event()
@@ -493,8 +535,37 @@ class FlatAdam:
     def step(self, grad_scale=1.0):
         """The update of the whole bucket, every network with its own row."""
         self.flush_hyper()
+        if self.guard:
+            self.tick()
+            for i in self._present():
+                self._guarded_row(i, grad_scale)
+            return
         engine().call("cc_adam_step_hyper", self.flat_p, self.flat_g, self.exp_avg, self.exp_avg_sq, self.step_dev,
                       self.flat_p.numel(), self.hyper_dev, self.bounds_dev, len(self._hyper), float(grad_scale), STREAM)
+
+    def _guarded_row(self, i, grad_scale):
+        """gradient guard + update of network i's whole row on the current stream: sum of squares -> guard row -> guarded Adam"""
+        a, b = self.bounds[i], self.bounds[i + 1]
+        nb = ctypes.c_int(0)
+        engine().call("cc_grad_sumsq", self.flat_g[a:b], b - a, self._partials[i], ctypes.addressof(nb), STREAM)
+        engine().call("cc_grad_guard_finish", self._partials[i], nb.value, self.hyper_dev[i], float(grad_scale), self.guard_dev[i],
+                      STREAM)
+        engine().call("cc_adam_step_segment_guard", self.flat_p[a:b], self.flat_g[a:b], self.exp_avg[a:b], self.exp_avg_sq[a:b],
+                      self.step_dev, b - a, self.hyper_dev[i], self.guard_dev[i], float(grad_scale), STREAM)
+
+    def grad_stats(self, sync=False):
+        """The guard rows of the most recent step: {'disp'|'pose'|'mask'|'flow': {'norm', 'coef', 'finite', 'skipped'}} -- norm: L2
+        norm of the network's gradient as Adam consumed it (mean over the ranks, before clipping); coef: what it was multiplied
+        with; finite: 0 if it held a NaN / Inf (the network was left alone); skipped: how many steps that happened to so far.
+        Values are 0-dim views of the device table (no sync); sync=True: Python numbers after one read-back."""
+        if not self.guard:
+            raise ValueError("FlatAdam.grad_stats: the gradient guard is off (StepConfig.max_grad_norm = None)")
+        tab = self.guard_dev.tolist() if sync else self.guard_dev
+        out = {}
+        for i in self._present():
+            r = tab[i]
+            out[NET_NAMES[i] if i < len(NET_NAMES) else i] = {"norm": r[0], "coef": r[1], "finite": r[2], "skipped": r[3]}
+        return out
 
     def tick(self):
         """advance the step counter alone (the segments of this step then update with tick = 0, from any stream)"""
@@ -503,10 +574,23 @@ class FlatAdam:
     def step_segment(self, lo, hi, tick, grad_scale=1.0):
         """The update of elements [lo, hi) of the bucket (lo % 4 == 0); tick: advance the step counter (first segment only).
         A range may span several networks' rows (the two segments of the legacy data-parallel forms hold two networks each): it
-        becomes one launch per row it touches, each with that row's hyperparameters."""
+        becomes one launch per row it touches, each with that row's hyperparameters.  With the gradient guard on the range has to
+        cover every row it touches COMPLETELY (the norm of a part of a network's gradient is not the network's): ValueError."""
         hi = self.flat_p.numel() if hi is None else hi
         assert lo % 4 == 0 and 0 <= lo < hi <= self.flat_p.numel()
         self.flush_hyper()
+        if self.guard:
+            rows = [i for i in range(len(self._hyper)) if max(lo, self.bounds[i]) < min(hi, self.bounds[i + 1])]
+            for i in rows:
+                if lo > self.bounds[i] or hi < self.bounds[i + 1]:
+                    raise ValueError("FlatAdam.step_segment: [%d, %d) covers only a part of network %d's segment [%d, %d); with the "
+                                     "gradient guard on a network is updated as a whole (its gradient norm is not known before its "
+                                     "last gradient has arrived)" % (lo, hi, i, self.bounds[i], self.bounds[i + 1]))
+            if tick:
+                self.tick()
+            for i in rows:
+                self._guarded_row(i, grad_scale)
+            return
         # one launch per row the range touches (the per-network pipeline's ranges lie inside one network's segment; the two
         # segments of the legacy forms hold two networks each)
         for i in range(len(self._hyper)):
@@ -522,15 +606,22 @@ class FlatAdam:
         the same hyperparameters, else one per network (``params`` = the index range of its parameters), which a
         ``torch.optim.Adam`` built with the same groups loads."""
         state = {}
+        # guard on: a network's step = the counter minus the steps its gradient was not finite (torch's layout has a step per tensor)
+        skipped = self.guard_dev[:, 3].tolist() if self.guard else None
+        net_of = {j: i for i, idx in enumerate(self._param_index) for j in idx}
         for i, (p, off) in enumerate(zip(self.params, self.offsets)):
             k = p.numel()
-            state[i] = {"step": self.step_dev.detach().clone().reshape(()),
+            state[i] = {"step": (self.step_dev.detach().clone().reshape(()) if skipped is None else
+                                 (self.step_dev.detach() - skipped[net_of[i]]).reshape(())),
                         "exp_avg": self.exp_avg[off:off + k].view_as(p).clone(),
                         "exp_avg_sq": self.exp_avg_sq[off:off + k].view_as(p).clone()}
         def group(i, params):
             h = self._hyper[i]
-            return {"lr": h["lr"], "betas": tuple(h["betas"]), "eps": h["eps"], "weight_decay": h["weight_decay"], "amsgrad": False,
-                    "params": params}
+            g = {"lr": h["lr"], "betas": tuple(h["betas"]), "eps": h["eps"], "weight_decay": h["weight_decay"], "amsgrad": False,
+                 "params": params}
+            if self.guard:
+                g["max_grad_norm"] = h["max_grad_norm"]
+            return g
         if self._uniform():
             groups = [group(self._present()[0], list(range(len(self.params))))]
         else:
@@ -558,16 +649,30 @@ class FlatAdam:
                                  "networks' parameters in chain order)" % (list(g["params"])[:4] + ["..."], w[0], w[-1]))
             if g.get("amsgrad", False) or g.get("maximize", False):
                 raise ValueError("FlatAdam.load_state_dict: amsgrad / maximize are not supported")
+        net_step = {}
+        net_of = {j: i for i, idx in enumerate(self._param_index) for j in idx}
         for i, (p, off) in enumerate(zip(self.params, self.offsets)):
             k = p.numel()
             st = sd["state"].get(i)
             if st is not None:
                 self.exp_avg[off:off + k].copy_(st["exp_avg"].reshape(-1))
                 self.exp_avg_sq[off:off + k].copy_(st["exp_avg_sq"].reshape(-1))
-                self.step_dev.fill_(float(st["step"]))
+                if self.guard:
+                    net_step.setdefault(net_of[i], float(st["step"]))
+                else:
+                    self.step_dev.fill_(float(st["step"]))
+        if self.guard and net_step:
+            # the counter = the largest step in the file; a network that is behind it has skipped the difference
+            top = max(net_step.values())
+            self.step_dev.fill_(top)
+            self.guard_dev.zero_()
+            for i, t in net_step.items():
+                self.guard_dev[i, 3] = top - t
         for k, g in enumerate(groups):
+            # (max_grad_norm of a file written with the guard on is not taken over by an optimizer built with the guard off)
             self.set_hyper(None if len(groups) == 1 else present[k], lr=g["lr"], betas=tuple(g["betas"]),
-                           eps=g.get("eps", 1e-8), weight_decay=g.get("weight_decay", 0.0))
+                           eps=g.get("eps", 1e-8), weight_decay=g.get("weight_decay", 0.0),
+                           max_grad_norm=g.get("max_grad_norm") if self.guard else None)
 
     def broadcast_from_rank0(self):
         """Start-up: every rank continues from rank 0's parameters AND buffers (a --resume that only rank 0 read from disk, per-rank
@@ -597,6 +702,11 @@ class CCTrainer:
                       announced on stderr."""
         self.nets, self.cfg = nets, cfg
         self.comm_debug = dict(comm_debug or {})
+        if pipeline is None:
+            pipeline = "per_network" if split_graphs is None else ("staged" if split_graphs else "post")
+        assert pipeline in ("per_network", "post", "staged"), pipeline
+        if getattr(cfg, "max_grad_norm", None) is not None:
+            self._no_chunks_with_guard(pipeline == "per_network" and bool(config.grad_chunks))
         for n in nets:
             if n is not None:
                 n.train()                                                   # train.py:438-441
@@ -617,9 +727,6 @@ class CCTrainer:
         head = [r for r in self.opt.net_ranges[:2] if r is not None]
         self.n_dp = tail[0] if (tail and head) else (self.opt.flat_p.numel() if head else 0)
         two_segments = bool(tail and head)
-        if pipeline is None:
-            pipeline = "per_network" if split_graphs is None else ("staged" if split_graphs else "post")
-        assert pipeline in ("per_network", "post", "staged"), pipeline
         if pipeline == "staged" and not two_segments:     # (MaskNet6 + Back2Future frozen -- README's --fix-masknet --fix-flownet)
             pipeline = "post"
         self.pipeline = pipeline
@@ -675,6 +782,8 @@ class CCTrainer:
         """Change the step form of a live trainer (same bucket, same optimizer state): the captured graphs are dropped and the next
         step captures the new form.  bench.py uses it at N > 1 to time the per-network form against round 5's on the machine at hand."""
         assert pipeline in ("per_network", "post", "staged"), pipeline
+        if self.opt.guard:
+            self._no_chunks_with_guard(pipeline == "per_network" and self.grad_chunks)
         if pipeline == "per_network" and self.opt.comm_active() and self.opt.flat_g.is_cuda:
             self.opt.rccl()
         self.pipeline, self.split_graphs = pipeline, pipeline == "staged"
@@ -686,8 +795,17 @@ class CCTrainer:
     def set_grad_chunks(self, on):
         """config.grad_chunks for a live trainer (per-network form; the captured graph is dropped): bench.py times the form with and
         without the chunks at N > 1, where DispResNet6's exchange is what they start early."""
+        if self.opt.guard:
+            self._no_chunks_with_guard(self.pipeline == "per_network" and bool(on))
         self.grad_chunks = bool(on)
         self.switch_pipeline(self.pipeline)
+
+    @staticmethod
+    def _no_chunks_with_guard(chunks):
+        if chunks:
+            raise ValueError("gradient chunks (config.grad_chunks / set_grad_chunks(True)) cannot be combined with the gradient guard "
+                             "(StepConfig.max_grad_norm): a chunk's Adam update starts before the rest of DispResNet6's gradient "
+                             "exists, so the network's norm -- and whether it is finite -- is not known yet")
 
     def _fall_back(self, why):
         """Data-parallel only: the per-network form needs ncclAllReduce on the networks' streams (cc_amd/rccl.py).  If that path is
@@ -942,8 +1060,8 @@ class CCTrainer:
         # pipelined step contains the optimizer, so parameters, moments and step counter are put back as well
         bn_state = [(b, b.detach().clone()) for n in self.nets if n is not None for b in n.buffers()]
         pipelined = self.pipeline == "per_network"
-        opt_state = [(t, t.detach().clone()) for t in (self.opt.flat_p, self.opt.exp_avg, self.opt.exp_avg_sq, self.opt.step_dev)] \
-            if pipelined else []
+        opt_state = [(t, t.detach().clone()) for t in (self.opt.flat_p, self.opt.exp_avg, self.opt.exp_avg_sq, self.opt.step_dev) +
+                     ((self.opt.guard_dev,) if self.opt.guard else ())] if pipelined else []      # (guard_dev: the skip counts)
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s):
@@ -987,6 +1105,12 @@ class CCTrainer:
     def check_finite(self):
         """Deferred NaN assert of the most recent step (one host sync); works in eager and in hipGraph mode."""
         LF.check_finite(self.nan_flags)
+
+    def grad_stats(self, sync=False):
+        """Gradient guard (StepConfig.max_grad_norm): per network {'norm', 'coef', 'finite', 'skipped'} of the most recent step, as
+        0-dim device views (no sync: log them every N steps) or, with sync=True, as Python numbers after one read-back.
+        ValueError with the guard off."""
+        return self.opt.grad_stats(sync)
 
     def grad_norms(self):
         """L2 norm of the most recent step's (all-reduced, unscaled) gradient per network, from the flat bucket

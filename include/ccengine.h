@@ -577,6 +577,27 @@ int cc_adam_step_segment_hyper(float* params, const float* grads, float* exp_avg
                                const float* hyper_row, float grad_scale, int tick, void* stream);
 int cc_fill(float* p, long n, float value, void* stream);
 
+/* ---------------------------------------------------------------- gradient guard of the in-graph Adam step (grad_guard.hip)
+ * Per network, three launches on the network's stream between its all-reduce and its weight images: no host sync, no atomics,
+ * nothing to clear, capturable.  Equals torch.nn.utils.clip_grad_norm_(net.parameters(), max_norm) + "skip optimizer.step() for
+ * this network when its gradient is not finite".
+ * cc_grad_sumsq: stage 1 of a deterministic two-stage sum of squares (fp64) over g[0, n) (g 16-byte aligned): a grid of
+ * min(CC_GRAD_GUARD_MAX_BLOCKS, ceil(n / 4096)) workgroups, each storing one fp64 partial; partials: room for
+ * CC_GRAD_GUARD_MAX_BLOCKS doubles; nblocks_out: HOST int that receives the grid (a function of n alone), or NULL. */
+#define CC_GRAD_GUARD_MAX_BLOCKS 1024
+int cc_grad_sumsq(const float* g, long n, double* partials, int* nblocks_out, void* stream);
+/* One workgroup sums the partials in a fixed order and writes the network's guard row, 8 floats
+ * {norm, coef, finite, skipped, 0, 0, 0, 0}:  norm = grad_scale * sqrt(sumsq) (of the gradient Adam consumes);  finite = 1 / 0;
+ * max_norm = hyper_row[5];  coef = finite ? (0 < max_norm < inf ? min(1, max_norm / (norm + 1e-6)) : 1) : 0;
+ * skipped += finite ? 0 : 1 (a running count: the caller zeroes the row once, at allocation). */
+int cc_grad_guard_finish(const double* partials, int nblocks, const float* hyper_row, float grad_scale, float* guard_row,
+                         void* stream);
+/* cc_adam_step_segment_hyper's update of a range inside one row, with the gradient (g * grad_scale) * coef (weight decay is added
+ * after the clipping, as in torch), the bias corrections at t = step_dev[0] - skipped, and no store at all when finite == 0.
+ * Never advances the counter (cc_adam_tick does).  coef == 1 and skipped == 0: the bits of cc_adam_step_segment_hyper. */
+int cc_adam_step_segment_guard(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, const float* step_dev, long n,
+                               const float* hyper_row, const float* guard_row, float grad_scale, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
