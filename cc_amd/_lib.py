@@ -40,6 +40,19 @@ def parse_header(path=HEADER):
     return out
 
 
+_constants = {}
+
+
+def header_constant(name, path=HEADER):
+    """the integer value of `#define <name> <integer>` in the header (every such define is collected in one pass, once per path)"""
+    if path not in _constants:
+        with open(path) as f:
+            _constants[path] = {m.group(1): int(m.group(2)) for m in re.finditer(r"^#define\s+(\w+)\s+(\d+)\s*$", f.read(), flags=re.M)}
+    if name not in _constants[path]:
+        raise KeyError("%s: no integer #define in %s" % (name, path))
+    return _constants[path][name]
+
+
 def image_dense(t):
     """True for a 4-D NCHW tensor whose images are dense ([C,H,W] contiguous) but whose batch stride may be wider: a channel
     slice of a concat buffer / of a concat gradient.  Entry points that take a batch stride (x_bs, gy_bs, a_bs ...) read such

@@ -126,7 +126,12 @@ def take_nan_flags():
     return out
 
 
+step_nan_flags = None     # a list while a CCTrainer step with the ledger on runs: the flags that step registers (cc_amd/ledger.py)
+
+
 def _register_nan_flag(flag):
+    if step_nan_flags is not None:
+        step_nan_flags.append(flag)
     if config.strict_nan_checks:
         assert flag.item() == 0, "NaN encountered in a photometric loss term"
     else:

@@ -15,6 +15,7 @@ MI355X-first structure around that body:
     passes.  Only the last finisher's exchange is exposed; on one GPU the optimizer and the weight-image refresh leave the
     critical path the same way.
 """
+import collections
 import collections.abc
 import contextlib
 import ctypes
@@ -24,8 +25,9 @@ import torch.distributed as dist
 
 from . import config, models, ops, tape
 from . import loss_functions as LF
-from ._lib import engine, STREAM
+from ._lib import engine, header_constant, STREAM
 from .inverse_warp import pose2flow
+from .ledger import Ledger
 
 
 class StepConfig:
@@ -41,6 +43,9 @@ class StepConfig:
         # gradient guard inside the step, per network (FlatAdam): None = off; a float > 0 = clip every network's gradient to that
         # L2 norm and skip a network's update when its gradient holds a NaN / Inf; float('inf') = norms + skip, no clipping
         self.max_grad_norm = None
+        # step ledger (cc_amd/ledger.py): None = off (not a launch more); an int = on, with that many rows in the device ring (a power
+        # of two): the step's last launch records its losses, NaN flags, learning rates and guard rows on the device
+        self.ledger = None
         for k, v in kw.items():
             assert hasattr(self, k), k
             setattr(self, k, v)
@@ -278,6 +283,29 @@ class _HyperGroup(collections.abc.MutableMapping):
         return "_HyperGroup(%s: %r)" % (self.net, self._opt.hyper_of(self.net))
 
 
+class _ParamStats(collections.abc.Mapping):
+    """What FlatAdam.param_stats(sync=False) returns: an ordered read-only mapping "<net>.<parameter name>" -> {'grad_norm',
+    'weight_norm', 'grad_maxabs', 'nonfinite'} over the device table [P, 4].  The 0-dim views are made when an entry is looked
+    up, so the call itself costs the host its two launches and nothing per parameter; `table` is the whole table."""
+    FIELDS = ("grad_norm", "weight_norm", "grad_maxabs", "nonfinite")
+
+    def __init__(self, names, table):
+        self.names, self.table = names, table
+        self._row = None
+
+    def __getitem__(self, name):
+        if self._row is None:
+            self._row = {n: j for j, n in enumerate(self.names)}
+        r = self.table[self._row[name]]
+        return {k: r[i] for i, k in enumerate(self.FIELDS)}
+
+    def __iter__(self):
+        return iter(self.names)
+
+    def __len__(self):
+        return len(self.names)
+
+
 class FlatAdam:
     """train.py:307-310 ``torch.optim.Adam(chain(all params), lr, betas, weight_decay)`` as ONE flat bucket + fused kernels.
 
@@ -298,11 +326,15 @@ class FlatAdam:
     each network is a segment that can be exchanged (RCCL), updated (cc_adam_step_segment_hyper with the network's row of the table, float4) and re-imaged on its own."""
     ALIGN = 64          # floats
     GUARD_BLOCKS = 1024 # CC_GRAD_GUARD_MAX_BLOCKS (include/ccengine.h): fp64 partials per network
+    PARAM_STATS_CHUNK = header_constant("CC_PARAM_STATS_CHUNK")      # floats one workgroup of cc_param_stats_chunks sweeps
 
     def __init__(self, nets, cfg):
         per_net = [([p for p in n.parameters() if p.requires_grad] if n is not None else []) for n in nets]
         params = [p for ps in per_net for p in ps]
         self.params = params
+        # "<net>.<parameter name>" per entry of `params` (param_stats)
+        self.param_names = ["%s.%s" % (NET_NAMES[i] if i < len(NET_NAMES) else i, name) for i, n in enumerate(nets) if n is not None
+                            for name, p in n.named_parameters() if p.requires_grad]
         # module buffers (BatchNorm running statistics / counters) and frozen parameters: not in the bucket, but part of what rank 0
         # hands to the other ranks at start-up (train.py:300-303: DataParallel replicates the whole module from device 0)
         self.extra_state = [b for n in nets if n is not None for b in n.buffers()] + \
@@ -373,6 +405,7 @@ class FlatAdam:
         self.comm_probe = ""
         self._rccl = None
         self.n_comms = 1            # RCCL communicators of the captured form: one per issuing stream (rccl())
+        self._pstats = None         # param_stats(): chunk table, partials and outputs, built on first use
 
     def zero_grad(self):
         engine().call("cc_fill", self.flat_g, self.flat_g.numel(), 0.0, STREAM)
@@ -566,6 +599,53 @@ class FlatAdam:
             r = tab[i]
             out[NET_NAMES[i] if i < len(NET_NAMES) else i] = {"norm": r[0], "coef": r[1], "finite": r[2], "skipped": r[3]}
         return out
+
+    def _param_stats_tables(self):
+        """the chunk table of cc_param_stats_chunks, built once: every parameter cut into chunks of at most PARAM_STATS_CHUNK floats
+        (a chunk never crosses a parameter boundary; the alignment padding between two networks belongs to no chunk)"""
+        if self._pstats is None:
+            C, chunks, first = self.PARAM_STATS_CHUNK, [], [0]
+            for p, off in zip(self.params, self.offsets):
+                k = p.numel()
+                chunks += [(off + a, min(C, k - a)) for a in range(0, k, C)]
+                first.append(len(chunks))
+            dev = self.flat_p.device
+            self._pstats = {"chunks": torch.tensor(chunks, dtype=torch.int64).reshape(-1, 2).to(dev),
+                            "first": torch.tensor(first, dtype=torch.int64).to(dev),
+                            "partials": torch.full((max(1, len(chunks)), 4), float("nan"), dtype=torch.float64).to(dev),
+                            "stats": torch.full((len(self.params), 4), float("nan"), dtype=torch.float64).to(dev)}
+        return self._pstats
+
+    def param_stats(self, grad_scale=None, sync=False):
+        """Per parameter tensor, from the flat buckets as they are now (after a step: flat_g holds that step's gradient until the
+        next step zeroes it): ordered mapping "<net>.<parameter name>" -> {'grad_norm': grad_scale * ||g||, 'weight_norm': ||p||,
+        'grad_maxabs': max |g| (unscaled; a NaN does not enter it, an Inf does), 'nonfinite': how many elements of g are NaN / Inf}.
+        Two launches on the current stream (cc_amd/csrc/param_stats.hip), fp64, no host sync: the values are 0-dim views of one
+        device table that the next call overwrites, made when an entry is looked up (_ParamStats; `.table` is the [P, 4] table) --
+        or, with sync=True, an OrderedDict of Python numbers after one read-back.  grad_scale: what the
+        gradient guard's norms are scaled with (None: grad_scale(), 1 / world size).  An eager call; not part of a captured step."""
+        if _capture_in_progress(self.flat_p):
+            raise RuntimeError("FlatAdam.param_stats: a hipGraph capture is in progress (an eager call between two steps)")
+        t = self._param_stats_tables()
+        scale = self.grad_scale() if grad_scale is None else float(grad_scale)
+        if t["chunks"].shape[0]:
+            engine().call("cc_param_stats_chunks", self.flat_g, self.flat_p, self.flat_p.numel(), t["chunks"], t["chunks"].shape[0],
+                          t["partials"], STREAM)
+        engine().call("cc_param_stats_finish", t["partials"], t["first"], len(self.params), scale, t["stats"], STREAM)
+        if not sync:
+            return _ParamStats(self.param_names, t["stats"])
+        return collections.OrderedDict((name, dict(zip(_ParamStats.FIELDS, r))) for name, r in zip(self.param_names, t["stats"].tolist()))
+
+    def first_nonfinite(self, sync=True):
+        """The first parameter in chain order whose gradient holds a NaN / Inf: its name or None (sync=True, one read-back), or its
+        index into `param_names` as a 0-dim device tensor, -1 for none (sync=False)."""
+        self.param_stats()
+        bad = self._pstats["stats"][:, 3] > 0
+        idx = torch.where(bad.any(), bad.to(torch.int64).argmax(), torch.full((), -1, dtype=torch.int64, device=bad.device))
+        if not sync:
+            return idx
+        i = int(idx)
+        return None if i < 0 else self.param_names[i]
 
     def tick(self):
         """advance the step counter alone (the segments of this step then update with tick = 0, from any stream)"""
@@ -772,6 +852,10 @@ class CCTrainer:
         self.losses = None
         self.nan_flags = []
         self.opt.n_comms = 1 + (len(self.net_streams) if self.net_streams else 0)
+        # step ledger (StepConfig.ledger): its device state is allocated here, before any capture; survives switch_pipeline / a re-capture
+        cap = getattr(cfg, "ledger", None)
+        self.ledger = Ledger(dev0, cap) if cap is not None else None
+        self._step_flags = []            # the NaN flags the most recent (or the captured) step registered: a source of the ledger's row
         if self.pipeline == "per_network" and self.opt.comm_active():
             try:
                 self.opt.rccl()          # the communicators must exist before any capture
@@ -832,6 +916,9 @@ class CCTrainer:
             self.opt.zero_grad()                                            # :566  (with side streams: behind their forks, cc_forward)
         ops.grad_sinks = self.opt.sinks
         LF.scalar_pool.begin(batch[0].device)
+        if self.ledger is not None:
+            LF.step_nan_flags = self._step_flags = []
+            self._ledger_n = int(batch[0].shape[0])
 
     def _loss_grads(self, batch):
         """forward of the four nets + losses (train.py:454-509) and d loss / d (network outputs) -> (losses, dp pairs, mf pairs)"""
@@ -904,6 +991,7 @@ class CCTrainer:
     def _stage_end(self, failed=False):
         tape.BN_COUNTERS = None
         tape.NET_DONE = tape.NET_MARK = None
+        LF.step_nan_flags = None
         if failed:
             # a stage raised part-way: the parked launches' operands belong to the failed step and no fork / join is in place for
             # the side streams -- drop them instead of launching
@@ -1017,10 +1105,21 @@ class CCTrainer:
             for i in range(len(self.nets)):     # networks that are not on the tape (alternative architectures) or received no gradient
                 if i not in self._done:
                     self._finish_network(i)
+            # (the side streams were joined above, every tail is ordered in front of this point of the step's own stream: the guard
+            # rows and the counter the row reads are final)
+            self._ledger_append(losses)
             ok = True
         finally:
             self._stage_end(failed=not ok)
         return losses
+
+    def _ledger_append(self, losses):
+        """the step's last launch with the ledger on (StepConfig.ledger), on the current stream: a node of the graph when the step is
+        being captured, the same call when it runs eagerly or -- the legacy forms -- behind the eager optimizer"""
+        if self.ledger is None:
+            return
+        self.ledger.append(losses, self._ledger_n, step=self.opt.step_dev, nan_flags=self._step_flags, hyper=self.opt.hyper_dev,
+                           guard=self.opt.guard_dev)
 
     def _weights_touched(self):
         """did anybody but this trainer write the parameters since the weight images were built?  (torch in-place ops bump the
@@ -1061,7 +1160,8 @@ class CCTrainer:
         bn_state = [(b, b.detach().clone()) for n in self.nets if n is not None for b in n.buffers()]
         pipelined = self.pipeline == "per_network"
         opt_state = [(t, t.detach().clone()) for t in (self.opt.flat_p, self.opt.exp_avg, self.opt.exp_avg_sq, self.opt.step_dev) +
-                     ((self.opt.guard_dev,) if self.opt.guard else ())] if pipelined else []      # (guard_dev: the skip counts)
+                     ((self.opt.guard_dev,) if self.opt.guard else ()) +      # (guard_dev: the skip counts)
+                     ((self.ledger.state,) if self.ledger is not None else ())] if pipelined else []   # (a warm-up leaves no row)
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s):
@@ -1111,6 +1211,16 @@ class CCTrainer:
         0-dim device views (no sync: log them every N steps) or, with sync=True, as Python numbers after one read-back.
         ValueError with the guard off."""
         return self.opt.grad_stats(sync)
+
+    def param_stats(self, sync=False):
+        """Per parameter tensor {'grad_norm', 'weight_norm', 'grad_maxabs', 'nonfinite'} of the most recent step's gradient and the
+        current weights, keyed "<disp|pose|mask|flow>.<parameter name>" in chain order (FlatAdam.param_stats): an eager call
+        between two steps, two launches, no host sync unless sync=True."""
+        return self.opt.param_stats(sync=sync)
+
+    def first_nonfinite(self, sync=True):
+        """the name of the first parameter in chain order whose gradient holds a NaN / Inf, or None (FlatAdam.first_nonfinite)"""
+        return self.opt.first_nonfinite(sync)
 
     def grad_norms(self):
         """L2 norm of the most recent step's (all-reduced, unscaled) gradient per network, from the flat bucket
@@ -1243,6 +1353,11 @@ class CCTrainer:
         return self._step_legacy(batch)
 
     def _step_legacy(self, batch):
+        losses = self._step_legacy_update(batch)
+        self._ledger_append(losses)          # behind the eager optimizer
+        return losses
+
+    def _step_legacy_update(self, batch):
         opt = self.opt
         works = []
 

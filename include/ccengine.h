@@ -598,6 +598,49 @@ int cc_grad_guard_finish(const double* partials, int nblocks, const float* hyper
 int cc_adam_step_segment_guard(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, const float* step_dev, long n,
                                const float* hyper_row, const float* guard_row, float grad_scale, void* stream);
 
+/* ---------------------------------------------------------------- step ledger (ledger.hip)
+ * One row of 32 floats per training step, appended on the device as the last launch of the step (a node of the captured graph):
+ * what train.py:563,574-576 reads back with .item() every iteration, without a host sync between two replays.
+ * cc_ledger_append: ONE launch of one 64-work-item workgroup on `stream`; no atomics (one work-item of one workgroup on one stream
+ * does the read-modify-write of head and agg).  It writes row (head % capacity) of ring [capacity, CC_LEDGER_SLOTS], folds slots
+ * 1..7 of the row into agg with weight n, then stores head + 1.
+ * sources_host: HOST array of nsources device addresses (CC_LEDGER_SRC_FLAGS <= nsources <= CC_LEDGER_MAX_SOURCES), copied into
+ * the kernel's arguments by value; an address of 0 = absent:
+ *   [0]      step counter, 1 float                          -> slot 0
+ *   [1..6]   loss, loss_1 .. loss_5, 1 float each           -> slots 1..6, bit copies (absent: 0)
+ *   [7]      hyperparameter table [hyper_rows, 8] floats    -> slots 8..8+hyper_rows-1 = column 0 (lr) of rows 0.. (hyper_rows <= 4)
+ *   [8]      guard table [hyper_rows, 8] floats             -> slots 12.., 16.., 20.. = norm, coef, finite per row; absent: all
+ *                                                              twelve slots are NaN ("not measured")
+ *   [9..]    NaN flags, 1 float each                        -> slot 7 = 1.0 if any of them is not 0, else 0.0
+ * Every slot not named is 0.
+ * agg: [CC_LEDGER_AGG_ROWS, 4] doubles = {sum of n * value, sum of n, min, max} of slots 1..7 (AverageMeter.update(value, n) in
+ * fp64; a NaN value makes its sum NaN and leaves min / max as they are).  capacity: a power of two.  head: 1 long (a count of rows
+ * ever appended).  cc_ledger_reset_agg: agg = {0, 0, +inf, -inf} per row, ordered on `stream`. */
+#define CC_LEDGER_SLOTS 32
+#define CC_LEDGER_AGG_ROWS 7
+#define CC_LEDGER_SRC_FLAGS 9
+#define CC_LEDGER_MAX_SOURCES 32
+int cc_ledger_append(const long* sources_host, int nsources, int hyper_rows, int n, float* ring, int capacity, long* head,
+                     double* agg, void* stream);
+int cc_ledger_reset_agg(double* agg, void* stream);
+
+/* ---------------------------------------------------------------- per-parameter statistics of the flat buckets (param_stats.hip)
+ * For every parameter tensor of the bucket, in one sweep over flat_g and flat_p: L2 norm of its gradient and of its weights, the
+ * largest |gradient| and the number of gradient elements that are NaN / Inf.  Two launches, no host sync, nothing cleared
+ * beforehand, no atomics, the same bits on every call for the same input.
+ * cc_param_stats_chunks: one workgroup per row of chunks [nchunks, 2] longs = {first element in the bucket, length <=
+ * CC_PARAM_STATS_CHUNK}; a chunk lies inside ONE parameter, at any offset (16-byte loads on the aligned interior, scalar loads
+ * on the <= 3 elements in front of and behind it).  flat_g, flat_p: 16-byte aligned, n elements each; a chunk that does not lie
+ * inside [0, n) is not read and yields NaN.  partials: [nchunks, 4] doubles = {sum g^2, sum p^2, max |g|, count of non-finite g}
+ * (fp64 accumulation; NaN does not enter the maximum, Inf does).
+ * cc_param_stats_finish: parameter j owns chunks [param_first[j], param_first[j + 1]) (param_first: nparams + 1 longs, device),
+ * summed in chunk order -> stats [nparams, 4] doubles = {grad_scale * sqrt(sum g^2), sqrt(sum p^2), max |g|, non-finite count}. */
+#define CC_PARAM_STATS_CHUNK 16384
+int cc_param_stats_chunks(const float* flat_g, const float* flat_p, long n, const long* chunks, int nchunks, double* partials,
+                          void* stream);
+int cc_param_stats_finish(const double* partials, const long* param_first, int nparams, float grad_scale, double* stats,
+                          void* stream);
+
 #ifdef __cplusplus
 }
 #endif
