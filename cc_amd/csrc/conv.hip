@@ -2,8 +2,8 @@
 // exact fp32, bit-equal to an fmaf chain, 157 TFLOP/s peak).  Replaces cuDNN/MIOpen's conv2d,
 // conv_transpose2d and convolution_backward (219 forward + 297 backward calls per step).
 //
-// ONE implicit-GEMM "gather-GEMM" kernel covers conv forward, conv data-gradient, transposed-conv forward
-// and transposed-conv data-gradient:
+// Every problem here is ONE implicit GEMM, described by a GG: conv forward, conv data-gradient, transposed-conv forward and
+// transposed-conv data-gradient are
 //      Y[n, m, P(t)] = epilogue( sum_{c, i, j}  A[m, (c,i,j)] * X[n, c, si*ty + dy(i), si*tx + dx(j)] )
 //   * output pixels t = (ty, tx) live on a lattice  P(t) = (oy0 + so*ty, ox0 + so*tx)   (so = 2 selects one
 //     parity class of a stride-2 transposed conv / stride-2 data-gradient, so no MFMA work is spent on
@@ -13,12 +13,22 @@
 //     their transpose/flip for data-gradients, and ConvTranspose2d's [Cin,Cout,R,S] layout without repacking.
 // GEMM view: M = output channels, N = B*OHt*OWt lattice pixels (contiguous in NCHW -> coalesced stores, and
 // MFMA D columns map to lanes = pixels), K = Cin*Rt*St gathered on the fly (im2col never materialised).
-// Tile: BM x 128 pixels x 16 (K) per 256-thread workgroup, 4 waves of (BM/2 or 32) x (64 or 32) built from
-// 32x32x2 MFMAs; register-staged double-buffered LDS, one barrier per K chunk.  B-tile loads are
-// lane = pixel (coalesced along x) with a wave-uniform k so the (c,i,j) decode runs on the scalar unit.
-// Epilogue fuses bias, residual add, ReLU / LeakyReLU(0.2) / a*sigmoid+b.
+// The epilogue fuses bias, residual add, ReLU / LeakyReLU(0.2) / a*sigmoid+b and the activation backward (conv_tail.h).
 //
-// Weight gradients: conv_wgrad.hip (and the kernels it dispatches to); activation backward / bias gradients: conv_act.hip.
+// Map of this file, in its order:
+//   kernels   k_gather_gemm        the FALLBACK (index math per element, no workspace): a patch beyond the LDS, a call without
+//                                  workspace, a misaligned Winograd input
+//             k_repack_w / _table  weight images [tap][c][m], per call / all of a network's in one launch
+//             k_conv_patch*        the MAIN path, patch-staged; _stk = stacked tiny maps, _multi = up to MAXCLS problems per launch
+//             k_splitk_epilogue*   deterministic second stage of split-K (also of wino.hip's launches); k_pad_rows is next to its launch
+//   planning  plan_conv            one ConvPlan per problem, in named steps (plan_wino_padded ... plan_balance)
+//   launch    launch_gg            one problem: head kernels (conv_heads.hip), Winograd (wino.hip), patch kernel, fallback
+//             classes_form, launch_classes   several problems in one launch: the form decided (nothing launched), then run
+//             kernel_name          the one place that formats a kernel's name: timing scopes and name queries
+//   C ABI     forward; TProblem / for_each_class (the transposed arithmetic and its parity classes), data-gradient; lists; name queries
+//
+// Weight gradients: conv_wgrad.hip (and the kernels it dispatches to); activation backward / bias gradients: conv_act.hip;
+// the timing registry behind cctiming::Scope: timing.hip.
 #include <stdio.h>
 #include <stdlib.h>
 #include <stddef.h>
@@ -30,33 +40,6 @@
 #include "wino_weights.h"
 #include "../../include/ccengine.h"
 #include <vector>
-#include <string>
-#include <mutex>
-
-// ---- per-kernel timing (measurement aid for bench.py's roofline line; off unless cc_timing_enable(1) was called on this
-// process; autograd runs the backward pass on its own threads): the MAIN device kernel of every conv / weight-gradient call is bracketed with HIP events on its own stream, so the
-// reported duration is the kernel's (what rocprofv3 --kernel-trace shows), not the C-ABI call's.  The registry lives here;
-// cctiming::Scope (conv_internal.h) is what the convolution units bracket their launches with.
-#ifdef CC_TOOLS
-namespace cctiming {
-struct Rec { std::string name; double gflop; hipEvent_t e0, e1; };
-static std::vector<Rec>* recs = nullptr;
-static std::mutex mtx;
-Scope::Scope(const char* name, double gflop, hipStream_t st, bool active) : s(st) {
-    if (!recs || !active) return;
-    hipEvent_t e0 = nullptr;
-    (void)hipEventCreate(&e0);
-    (void)hipEventCreate(&e1);
-    {
-        std::lock_guard<std::mutex> lk(mtx);
-        if (!recs) return;
-        recs->push_back(Rec{name, gflop, e0, e1});
-    }
-    (void)hipEventRecord(e0, s);
-}
-Scope::~Scope() { if (e1) (void)hipEventRecord(e1, s); }
-}  // namespace cctiming
-#endif
 
 namespace {
 
@@ -904,7 +887,7 @@ __global__ __launch_bounds__(256) void k_splitk_epilogue_multi(EPM a) {
                                           c.add ? c.add[(long)n * c.add_bs + o] : 0.f);
 }
 
-
+// ------------------------------------------------------------------ planning (host)
 struct ConvPlan {
     bool use_patch;
     int wino;                  // Winograd F(2x2, 3x3) kernel (wino.hip): wn holds its plan, wp_floats the size of the U image
@@ -918,11 +901,29 @@ struct ConvPlan {
     size_t pad_floats;         // ... and size (behind the partial slabs in the workspace)
 };
 
-
 // pixel tiles of a problem (grid.x of its launch): stacked tiny maps take one tile per ipt images
 inline long conv_tiles(const GG& g, const ConvPlan& p) { return (long)((g.B + p.ipt - 1) / p.ipt) * p.tiles_x * p.tiles_y; }
 
-// mult: number of same-shaped problems that share the launch (split-K only has to fill what they leave empty)
+// workgroups before split-K; mult: number of same-shaped problems that share the launch (split-K only has to fill what they leave empty)
+inline long conv_blocks(const GG& g, const ConvPlan& p, int mult) { return conv_tiles(g, p) * (p.Mpad / p.bm) * (mult > 1 ? mult : 1); }
+
+// dynamic LDS of a patch-kernel workgroup with `tps` taps per stage: A buffers [2][tps][ck][bm] + patch buffers [2][ck][PS]; the
+// epilogue transposes one 32x32 tile per wave through LDS (4 KB per wave)
+inline size_t patch_smem(const ConvPlan& p, int tps) {
+    const size_t b = (size_t)(2 * tps * p.ck * p.bm + 2 * p.ck * p.PS) * sizeof(float);
+    return (p.bm >= 32 && b < 16384) ? 16384 : b;
+}
+
+// split-K over the nchunk channel chunks into (about) `want` slices; the slabs are padded to whole tiles (p.Hp x p.Wp)
+inline void set_split(ConvPlan& p, const GG& g, int nchunk, long want) {
+    p.nsplit = 1; p.cps = nchunk;
+    if (want >= 2) {
+        p.cps = (int)((nchunk + want - 1) / want);
+        p.nsplit = (nchunk + p.cps - 1) / p.cps;
+    }
+    p.part_floats = p.nsplit > 1 ? (size_t)p.nsplit * g.B * g.M * p.Hp * p.Wp : 0;
+}
+
 // 3x3 / stride 1 / pad 1 on the full lattice, taps forwards (conv2d) or backwards (its data-gradient)
 inline bool wino_geometry(const GG& g) {
     return g.Rt == 3 && g.St == 3 && g.si == 1 && g.so == 1 && g.oy0 == 0 && g.ox0 == 0 && (g.dstep == 1 || g.dstep == -1) &&
@@ -930,74 +931,65 @@ inline bool wino_geometry(const GG& g) {
            (long)g.B * g.Cin * g.IH * g.IW < (1l << 26);
 }
 
-inline ConvPlan plan_conv(const GG& g, int mult = 1) {
-    ConvPlan p = {};
-    p.ipt = 1;
-    if (wino_geometry(g)) {
-        // the algorithm is a function of the geometry alone (the per-step weight image is laid out for it); `mult` only moves split-K
-        const ccint::WinoPlan w = ccint::wino_plan(g.B, g.Cin, g.IH, g.IW, g.M, mult);
-        if (w.ok) {
-            p.wino = 1;
-            p.wn = w;
-            p.use_patch = true;
-            p.bm = ccwino::WBM; p.ck = ccwino::WCK; p.tps = 1;
-            p.Mpad = w.Mpad; p.Cpad = w.Cpad;
-            p.nsplit = w.nsplit; p.cps = w.cps;
-            p.Hp = w.Hp; p.Wp = w.Wp;
-            p.wp_floats = w.u_floats;
-            p.part_floats = w.part_floats;
-            return p;
-        }
-        // Maps whose width is not a multiple of 4 (the 8x26 level of DispResNet6: 512- / 1024-channel layers, 4 GFLOP each on the direct
-        // kernel + a split-K epilogue): the Winograd kernel stages aligned 16-byte row pieces, so the input is first copied into rows
-        // padded with zeros to the next width it takes (k_pad_rows; zero columns ARE the convolution's padding) and the launch is
-        // always split-K: the partial slabs have the padded pitch, and the deterministic epilogue kernel that sums them writes the
-        // real output.  Large layers only (the copy, 23 % empty tile columns and the forced second pass have to pay), never for the
-        // grouped launches of parallel branches (they share one direct launch today).
-        if (!cctools::env_flag("CC_NO_WINO_PAD") && (g.IW % 4) != 0 && g.IH >= 2 && g.M >= cctools::env_int("CC_WINOP_MINM", 256) &&
-            g.Cin >= cctools::env_int("CC_WINOP_MINC", 256)) {
-            int wp = (g.IW + 3) & ~3;
-            while (!(wp / 2 >= 16 || wp / 2 == 8)) wp += 4;
-            if (4 * (wp - g.IW) <= wp && (long)g.B * ((g.IH + 1) / 2) * (wp / 2) >= cctools::env_int("CC_WINOP_MINQ", 64)) {
-                ccint::WinoPlan wq = ccint::wino_plan(g.B, g.Cin, g.IH, wp, g.M, mult);
-                if (wq.ok) {
-                    if (wq.nsplit < 2) {                    // the epilogue pass is what un-pads the output
-                        if (wq.tile == 2) wq.tile = 1;      // (the eight-wave instance halves the reduction itself: no slices across workgroups)
-                        wq.cps = (wq.nchunk + 1) / 2;
-                        wq.nsplit = (wq.nchunk + wq.cps - 1) / wq.cps;
-                        wq.part_floats = (size_t)wq.nsplit * g.B * g.M * wq.Hp * wq.Wp;
-                    }
-                    if (wq.nsplit >= 2) {
-                        p.wino = 1;
-                        p.wn = wq;
-                        p.use_patch = true;
-                        p.bm = ccwino::WBM; p.ck = ccwino::WCK; p.tps = 1;
-                        p.Mpad = wq.Mpad; p.Cpad = wq.Cpad;
-                        p.nsplit = wq.nsplit; p.cps = wq.cps;
-                        p.Hp = wq.Hp; p.Wp = wq.Wp;
-                        p.wp_floats = wq.u_floats;
-                        p.part_floats = wq.part_floats;
-                        p.wpad = wp;
-                        p.pad_floats = ((size_t)g.B * g.Cin * g.IH * wp + 3) & ~(size_t)3;
-                        return p;
-                    }
-                }
-            }
-        }
+// the plan of the Winograd kernel as the problem's plan; wpad: row pitch of the zero-padded input copy it runs over (0: the input itself)
+inline void adopt_wino(ConvPlan& p, const ccint::WinoPlan& w, const GG& g, int wpad = 0) {
+    p.wino = 1;
+    p.wn = w;
+    p.use_patch = true;
+    p.bm = ccwino::WBM; p.ck = ccwino::WCK; p.tps = 1;
+    p.Mpad = w.Mpad; p.Cpad = w.Cpad;
+    p.nsplit = w.nsplit; p.cps = w.cps;
+    p.Hp = w.Hp; p.Wp = w.Wp;
+    p.wp_floats = w.u_floats;
+    p.part_floats = w.part_floats;
+    p.wpad = wpad;
+    p.pad_floats = wpad ? ((size_t)g.B * g.Cin * g.IH * wpad + 3) & ~(size_t)3 : 0;
+}
+
+// step 2, Winograd over a padded copy.  Maps whose width is not a multiple of 4 (the 8x26 level of DispResNet6: 512- / 1024-channel
+// layers, 4 GFLOP each on the direct kernel + a split-K epilogue): the Winograd kernel stages aligned 16-byte row pieces, so the input
+// is first copied into rows padded with zeros to the next width it takes (k_pad_rows; zero columns ARE the convolution's padding) and
+// the launch is always split-K: the partial slabs have the padded pitch, and the deterministic epilogue kernel that sums them writes
+// the real output.  Large layers only (the copy, 23 % empty tile columns and the forced second pass have to pay), never for the
+// grouped launches of parallel branches (they share one direct launch today).
+inline bool plan_wino_padded(ConvPlan& p, const GG& g, int mult) {
+    if (cctools::env_flag("CC_NO_WINO_PAD") || (g.IW % 4) == 0 || g.IH < 2 || g.M < cctools::env_int("CC_WINOP_MINM", 256) ||
+        g.Cin < cctools::env_int("CC_WINOP_MINC", 256))
+        return false;
+    int wp = (g.IW + 3) & ~3;
+    while (!(wp / 2 >= 16 || wp / 2 == 8)) wp += 4;
+    if (!(4 * (wp - g.IW) <= wp && (long)g.B * ((g.IH + 1) / 2) * (wp / 2) >= cctools::env_int("CC_WINOP_MINQ", 64))) return false;
+    ccint::WinoPlan wq = ccint::wino_plan(g.B, g.Cin, g.IH, wp, g.M, mult);
+    if (!wq.ok) return false;
+    if (wq.nsplit < 2) {                    // the epilogue pass is what un-pads the output
+        if (wq.tile == 2) wq.tile = 1;      // (the eight-wave instance halves the reduction itself: no slices across workgroups)
+        wq.cps = (wq.nchunk + 1) / 2;
+        wq.nsplit = (wq.nchunk + wq.cps - 1) / wq.cps;
+        wq.part_floats = (size_t)wq.nsplit * g.B * g.M * wq.Hp * wq.Wp;
     }
+    if (wq.nsplit < 2) return false;
+    adopt_wino(p, wq, g, wp);
+    return true;
+}
+
+// step 3, channel tile
+inline void plan_channel_tile(ConvPlan& p, const GG& g) {
     p.bm = pick_bm_fwd(g.M);
-    {   // a narrower channel tile when it saves >= 25 % of the PADDED output channels: M = 65 / 96 -> 3 x 32 instead of 128,
-        // 129 -> 3 x 64 instead of 256, 260 -> 9 x 32 instead of 384 (concatenations with a 1-2 channel map, the 96-channel
-        // decoder layers): -0.33 ms/step (r3s3 A/B; thresholds 12-25 % equal, 35 % loses it)
-        const int thr = cctools::env_int("CC_CONV_BM_PADSAVE", 25);
-        if (thr > 0 && p.bm > 32) {
-            const int cur = ((g.M + p.bm - 1) / p.bm) * p.bm;
-            for (int b2 = p.bm / 2; b2 >= 32; b2 /= 2) {
-                const int m2 = ((g.M + b2 - 1) / b2) * b2;
-                if ((cur - m2) * 100 >= thr * cur) { p.bm = b2; break; }
-            }
+    // a narrower channel tile when it saves >= 25 % of the PADDED output channels: M = 65 / 96 -> 3 x 32 instead of 128,
+    // 129 -> 3 x 64 instead of 256, 260 -> 9 x 32 instead of 384 (concatenations with a 1-2 channel map, the 96-channel
+    // decoder layers): -0.33 ms/step (r3s3 A/B; thresholds 12-25 % equal, 35 % loses it)
+    const int thr = cctools::env_int("CC_CONV_BM_PADSAVE", 25);
+    if (thr > 0 && p.bm > 32) {
+        const int cur = ((g.M + p.bm - 1) / p.bm) * p.bm;
+        for (int b2 = p.bm / 2; b2 >= 32; b2 /= 2) {
+            const int m2 = ((g.M + b2 - 1) / b2) * b2;
+            if ((cur - m2) * 100 >= thr * cur) { p.bm = b2; break; }
         }
     }
+}
+
+// step 4, pixel tile / stacking (and the channel tile once more, now that the tile count is known)
+inline void plan_pixel_tile(ConvPlan& p, const GG& g) {
     {   // tile shape: 4 x 32 or 8 x 16 lattice pixels, whichever covers the map with fewer padded pixels
         const long a32 = (long)((g.OWt + 31) / 32) * 32 * (((g.OHt + 3) / 4) * 4);
         const long a16 = (long)((g.OWt + 15) / 16) * 16 * (((g.OHt + 7) / 8) * 8);
@@ -1013,14 +1005,24 @@ inline ConvPlan plan_conv(const GG& g, int mult = 1) {
         p.ipt = 8 / g.OHt < g.B ? 8 / g.OHt : g.B;
     }
     const int th = p.tw16 ? 8 : TH, tw = p.tw16 ? 16 : TW;
+    p.tiles_x = (g.OWt + tw - 1) / tw;
+    p.tiles_y = (g.OHt + th - 1) / th;
+    // partial slabs are padded to whole tiles (16-byte stores without guards): [split][n][m][tiles_y * th][tiles_x * tw]
+    p.Hp = p.tiles_y * th;
+    p.Wp = p.tiles_x * tw;
     {   // few pixel tiles: shrink the channel tile (more workgroups, every one over the whole reduction) before resorting to
         // split-K (partial slabs + an epilogue launch); CC_CONV_BM_MINBLOCKS: block count below which the tile is halved
-        const long tiles = (long)g.B * ((g.OWt + tw - 1) / tw) * ((g.OHt + th - 1) / th);
+        const long tiles = (long)g.B * p.tiles_x * p.tiles_y;
         const int thr = cctools::env_int("CC_CONV_BM64_BELOW", 0);
         if (p.bm == 128 && tiles * ((g.M + 127) / 128) < thr) p.bm = 64;
         const int minb = cctools::env_int("CC_CONV_BM_MINBLOCKS", 0);
         while (p.bm > 32 && tiles * ((g.M + p.bm - 1) / p.bm) < minb) p.bm /= 2;
     }
+}
+
+// step 5, patch geometry and LDS
+inline void plan_patch(ConvPlan& p, const GG& g) {
+    const int th = p.tw16 ? 8 : TH, tw = p.tw16 ? 16 : TW;
     const int ylast = g.dy0 + (g.Rt - 1) * g.dstep, xlast = g.dx0 + (g.St - 1) * g.dstep;
     p.ymin = g.dy0 < ylast ? g.dy0 : ylast;
     p.xmin = g.dx0 < xlast ? g.dx0 : xlast;
@@ -1044,68 +1046,81 @@ inline ConvPlan plan_conv(const GG& g, int mult = 1) {
     // 8-channel chunks: 20-40 KB of LDS per workgroup -> 3 (BM = 128, register-limited) to 7 workgroups per CU.  Measured
     // against 16-channel chunks (80 KB, two per CU, half as many barriers): -0.8 ms/step in total (r02g-r02i A/Bs);
     // CC_CONV_CK16=1 restores the round-1 plan (16 wherever one stage fits in 64 KB).
-    p.ck = 8;
-    auto smem_of = [&](int ck, int tps) { return (size_t)(2 * tps * ck * p.bm + 2 * ck * p.PS) * sizeof(float); };
-    if (cctools::env_flag("CC_CONV_CK16") && smem_of(16, 1) <= 64 * 1024) p.ck = 16;
+    p.ck = 16;
+    if (!(cctools::env_flag("CC_CONV_CK16") && patch_smem(p, 1) <= 64 * 1024)) p.ck = 8;
     // three taps per pipeline stage when the extra weight buffers still leave two workgroups per CU (2 x 80 KB)
-    p.tps = (g.Rt * g.St >= 3 && smem_of(p.ck, 3) <= 80 * 1024 && !cctools::env_flag("CC_CONV_TPS1")) ? 3 : 1;
-    p.smem = smem_of(p.ck, p.tps);
-    if (p.bm >= 32 && p.smem < 16384) p.smem = 16384;        // the epilogue transposes one 32x32 tile per wave through LDS
+    p.tps = (g.Rt * g.St >= 3 && patch_smem(p, 3) <= 80 * 1024 && !cctools::env_flag("CC_CONV_TPS1")) ? 3 : 1;
+    p.smem = patch_smem(p, p.tps);
     p.use_patch = (p.smem <= 150 * 1024) && g.Cin > 0;
     p.Mpad = ((g.M + p.bm - 1) / p.bm) * p.bm;
     p.Cpad = ((g.Cin + p.ck - 1) / p.ck) * p.ck;
-    p.tiles_x = (g.OWt + tw - 1) / tw;
-    p.tiles_y = (g.OHt + th - 1) / th;
     p.wp_floats = (size_t)g.Rt * g.St * p.Cpad * p.Mpad;
-    const long blocks = conv_tiles(g, p) * (p.Mpad / p.bm) * (mult > 1 ? mult : 1);
+}
+
+// step 6, split-K: launches that leave the chip empty slice the reduction
+inline void plan_split(ConvPlan& p, const GG& g, int mult) {
+    const long blocks = conv_blocks(g, p, mult);
     const int nchunk = p.Cpad / p.ck;
-    p.nsplit = 1;
-    p.cps = nchunk;
+    long want = 1;
     if (blocks < cctools::env_int("CC_CONV_SPLIT_BELOW", 384) && nchunk >= 4 && !(g.so != 1 && cctools::env_flag("CC_DBG_NO_PARITY_SPLIT"))) {
-        long want = (cctools::env_int("CC_CONV_SPLIT_TARGET", 512) + blocks - 1) / blocks;
+        want = (cctools::env_int("CC_CONV_SPLIT_TARGET", 512) + blocks - 1) / blocks;
         if (want > nchunk / cctools::env_int("CC_CONV_MINCHUNKS", 1)) want = nchunk / cctools::env_int("CC_CONV_MINCHUNKS", 1);
         if (want > cctools::env_int("CC_CONV_MAXSPLIT", 32)) want = cctools::env_int("CC_CONV_MAXSPLIT", 32);
-        if (want >= 2) {
-            p.cps = (int)((nchunk + want - 1) / want);
-            p.nsplit = (nchunk + p.cps - 1) / p.cps;
-        }
     }
-    // Wave quantisation (round 3): a launch of 257..~1000 workgroups runs as ceil(blocks / 256) "rounds" on the 256 CUs -- the
-    // MFMA pipes of a CU are saturated by one workgroup, so k co-resident workgroups take k times as long -- e.g. the 336
-    // workgroups of Back2Future's level-3 decoder groups (32x104 maps, G = 3) cost two rounds for 1.3 rounds of work.  A modest
-    // split-K re-balances them when the reduction is long enough to pay for the partial slabs.  Cost model (microseconds):
-    //   T(ns) = ceil(blocks * ns / 256) * (stages / ns) * t_stage(BM) + 2.5  [+ 2 * ns * out_bytes / 3 TB/s + 5 when ns > 1]
-    // calibrated on the split-K launches of the step (512->512 on 8x26: model 59 us, measured 63).
-    if (blocks >= 256 && nchunk >= 8 && cctools::env_int("CC_CONV_BALANCE", 1)) {
-        const int T = g.Rt * g.St;
-        const double mfma_cyc = (p.bm == 128 ? 3072.0 : p.bm == 64 ? 1536.0 : p.bm == 32 ? 768.0 : 384.0) * (p.tps == 3 ? 1.0 : 1.0 / 3.0);
-        const double t_stage = mfma_cyc / 2100.0;
-        const double stages = (double)nchunk * ((T + p.tps - 1) / p.tps);
-        const double out_bytes = 4.0 * g.B * g.M * g.OHt * g.OWt * (mult > 1 ? mult : 1);
-        auto cost = [&](int ns) {
-            const double k = (double)((blocks * ns + 255) / 256);
-            double t = k * (stages / ns) * t_stage + 2.5;
-            if (ns > 1) t += 2.0 * ns * out_bytes / 3.0e6 + 5.0;
-            return t;
-        };
-        int best = 1;
-        const int cap = nchunk / 4 < 8 ? nchunk / 4 : 8;
-        for (int ns = 2; ns <= cap; ns++)
-            if (cost(ns) < cost(best)) best = ns;
-        if (best > 1 && cost(best) < 0.01 * cctools::env_int("CC_CONV_BALANCE_PCT", 97) * cost(1)) {
-            p.cps = (nchunk + best - 1) / best;
-            p.nsplit = (nchunk + p.cps - 1) / p.cps;
-        }
+    set_split(p, g, nchunk, want);
+}
+
+// step 7, balance.  Wave quantisation (round 3): a launch of 257..~1000 workgroups runs as ceil(blocks / 256) "rounds" on the 256 CUs
+// -- the MFMA pipes of a CU are saturated by one workgroup, so k co-resident workgroups take k times as long -- e.g. the 336
+// workgroups of Back2Future's level-3 decoder groups (32x104 maps, G = 3) cost two rounds for 1.3 rounds of work.  A modest
+// split-K re-balances them when the reduction is long enough to pay for the partial slabs.  Cost model (microseconds):
+//   T(ns) = ceil(blocks * ns / 256) * (stages / ns) * t_stage(BM) + 2.5  [+ 2 * ns * out_bytes / 3 TB/s + 5 when ns > 1]
+// calibrated on the split-K launches of the step (512->512 on 8x26: model 59 us, measured 63).
+inline void plan_balance(ConvPlan& p, const GG& g, int mult) {
+    const long blocks = conv_blocks(g, p, mult);
+    const int nchunk = p.Cpad / p.ck;
+    if (!(blocks >= 256 && nchunk >= 8 && cctools::env_int("CC_CONV_BALANCE", 1))) return;
+    const int T = g.Rt * g.St;
+    const double mfma_cyc = (p.bm == 128 ? 3072.0 : p.bm == 64 ? 1536.0 : p.bm == 32 ? 768.0 : 384.0) * (p.tps == 3 ? 1.0 : 1.0 / 3.0);
+    const double t_stage = mfma_cyc / 2100.0;
+    const double stages = (double)nchunk * ((T + p.tps - 1) / p.tps);
+    const double out_bytes = 4.0 * g.B * g.M * g.OHt * g.OWt * (mult > 1 ? mult : 1);
+    auto cost = [&](int ns) {
+        const double k = (double)((blocks * ns + 255) / 256);
+        double t = k * (stages / ns) * t_stage + 2.5;
+        if (ns > 1) t += 2.0 * ns * out_bytes / 3.0e6 + 5.0;
+        return t;
+    };
+    int best = 1;
+    const int cap = nchunk / 4 < 8 ? nchunk / 4 : 8;
+    for (int ns = 2; ns <= cap; ns++)
+        if (cost(ns) < cost(best)) best = ns;
+    if (best > 1 && cost(best) < 0.01 * cctools::env_int("CC_CONV_BALANCE_PCT", 97) * cost(1)) set_split(p, g, nchunk, best);
+}
+
+inline ConvPlan plan_conv(const GG& g, int mult = 1) {
+    ConvPlan p = {};
+    p.ipt = 1;
+    if (wino_geometry(g)) {     // step 1, Winograd: a function of the geometry alone (the weight image is laid out for it); `mult` only moves split-K
+        const ccint::WinoPlan w = ccint::wino_plan(g.B, g.Cin, g.IH, g.IW, g.M, mult);
+        if (w.ok) adopt_wino(p, w, g);
+        if (w.ok || plan_wino_padded(p, g, mult)) return p;
     }
-    // partial slabs are padded to whole tiles (16-byte stores without guards): [split][n][m][tiles_y * th][tiles_x * tw]
-    p.Hp = p.tiles_y * th;
-    p.Wp = p.tiles_x * tw;
-    p.part_floats = p.nsplit > 1 ? (size_t)p.nsplit * g.B * g.M * p.Hp * p.Wp : 0;
+    plan_channel_tile(p, g);
+    plan_pixel_tile(p, g);
+    plan_patch(p, g);
+    plan_split(p, g, mult);
+    plan_balance(p, g, mult);
     return p;
 }
 
+// ---- workspace area of one problem: [64 zeros][weight image (unless the call brings a prepacked one)][partial slabs][padded input
+// copy]; sized by conv_ws_floats.  A prepacked image has the same head: [64 zeros][weight image(s)].
 inline size_t conv_ws_floats(const ConvPlan& p) { return 64 + p.wp_floats + p.part_floats + p.pad_floats; }
+template <class F> inline F* ws_image(F* area) { return area + 64; }
+inline float* ws_slabs(float* area, size_t image_floats) { return area + 64 + image_floats; }
 
+// ------------------------------------------------------------------ launch (host)
 inline void launch_gg_flat(const GG& g, hipStream_t s) {
     const long Ntot = (long)g.B * g.OHt * g.OWt;
     const int bm = pick_bm(g.M);
@@ -1115,27 +1130,17 @@ inline void launch_gg_flat(const GG& g, hipStream_t s) {
     else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_gather_gemm<32>), grid, dim3(256), 0, s, g);
 }
 
-template <class K, class ARGS>
-inline void launch_patch_kernel(K kern, bool& big_lds_enabled, const ARGS& c, dim3 grid, size_t smem, hipStream_t s) {
-    if (smem > 64 * 1024 && !big_lds_enabled) {            // > 64 KB of dynamic LDS has to be requested once per kernel
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+// one launch of the kernel instance KERN; > 64 KB of dynamic LDS has to be requested once per kernel (the flag is per instance)
+template <auto KERN, class ARGS>
+inline void launch_instance(const ARGS& c, dim3 grid, size_t smem, hipStream_t s) {
+    static bool big_lds_enabled = false;
+    if (smem > 64 * 1024 && !big_lds_enabled) {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(KERN), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         big_lds_enabled = true;
     }
-    hipLaunchKernelGGL(kern, grid, dim3(256), smem, s, c);
+    hipLaunchKernelGGL(KERN, grid, dim3(256), smem, s, c);
 }
 
-template <int BM, int CK, int TPS, int SPLIT>
-inline void launch_patch1(const CP& c, dim3 grid, size_t smem, hipStream_t s) {
-    static bool big = false;
-    launch_patch_kernel(&k_conv_patch<BM, CK, TPS, SPLIT>, big, c, grid, smem, s);
-}
-template <int BM, int TPS, int SPLIT>
-inline void launch_patch1_stk(const CP& c, dim3 grid, size_t smem, hipStream_t s) {
-    static bool big = false;
-    launch_patch_kernel(&k_conv_patch_stk<BM, TPS, SPLIT>, big, c, grid, smem, s);
-}
-
-inline bool stacked(const CP& c) { return c.ipt > 1; }
 inline bool stacked(const CPM& a) {
     for (int k = 0; k < a.n; k++)
         if (a.c[k].ipt > 1) return true;
@@ -1145,54 +1150,37 @@ inline bool stacked(const CPM& a) {
 template <int BM, int CK, int TPS>
 inline void launch_patch(const CP& c, dim3 grid, size_t smem, hipStream_t s) {
     if constexpr (CK == 8) {
-        if (stacked(c)) {
-            if (c.nsplit > 1) launch_patch1_stk<BM, TPS, 1>(c, grid, smem, s);
-            else launch_patch1_stk<BM, TPS, 0>(c, grid, smem, s);
+        if (c.ipt > 1) {
+            if (c.nsplit > 1) launch_instance<&k_conv_patch_stk<BM, TPS, 1>>(c, grid, smem, s);
+            else launch_instance<&k_conv_patch_stk<BM, TPS, 0>>(c, grid, smem, s);
             return;
         }
     }
-    if (c.nsplit > 1) launch_patch1<BM, CK, TPS, 1>(c, grid, smem, s);
-    else launch_patch1<BM, CK, TPS, 0>(c, grid, smem, s);
+    if (c.nsplit > 1) launch_instance<&k_conv_patch<BM, CK, TPS, 1>>(c, grid, smem, s);
+    else launch_instance<&k_conv_patch<BM, CK, TPS, 0>>(c, grid, smem, s);
 }
 
 template <int BM, int CK, int TPS>
 inline void launch_patch(const CPM& c, dim3 grid, size_t smem, hipStream_t s) {
     if constexpr (CK == 8) {
-        if (stacked(c)) {
-            static bool big = false;
-            launch_patch_kernel(&k_conv_patch_multi_stk<BM, TPS>, big, c, grid, smem, s);
-            return;
-        }
+        if (stacked(c)) { launch_instance<&k_conv_patch_multi_stk<BM, TPS>>(c, grid, smem, s); return; }
     }
-    static bool big = false;
-    launch_patch_kernel(&k_conv_patch_multi<BM, CK, TPS>, big, c, grid, smem, s);
+    launch_instance<&k_conv_patch_multi<BM, CK, TPS>>(c, grid, smem, s);
 }
 
+template <int CK, int TPS, class ARGS>
+inline void dispatch_bm(int bm, const ARGS& c, dim3 grid, size_t smem, hipStream_t s) {
+    if (bm == 128) launch_patch<128, CK, TPS>(c, grid, smem, s);
+    else if (bm == 64) launch_patch<64, CK, TPS>(c, grid, smem, s);
+    else if (bm == 32) launch_patch<32, CK, TPS>(c, grid, smem, s);
+    else launch_patch<16, CK, TPS>(c, grid, smem, s);
+}
 template <class ARGS>
 inline void dispatch_patch(int bm, int ck, int tps, const ARGS& c, dim3 grid, size_t smem, hipStream_t s) {
-    if (tps == 3) {
-        if (ck == 16) {
-            if (bm == 128) launch_patch<128, 16, 3>(c, grid, smem, s);
-            else if (bm == 64) launch_patch<64, 16, 3>(c, grid, smem, s);
-            else if (bm == 32) launch_patch<32, 16, 3>(c, grid, smem, s);
-            else launch_patch<16, 16, 3>(c, grid, smem, s);
-        } else {
-            if (bm == 128) launch_patch<128, 8, 3>(c, grid, smem, s);
-            else if (bm == 64) launch_patch<64, 8, 3>(c, grid, smem, s);
-            else if (bm == 32) launch_patch<32, 8, 3>(c, grid, smem, s);
-            else launch_patch<16, 8, 3>(c, grid, smem, s);
-        }
-    } else if (ck == 16) {
-        if (bm == 128) launch_patch<128, 16, 1>(c, grid, smem, s);
-        else if (bm == 64) launch_patch<64, 16, 1>(c, grid, smem, s);
-        else if (bm == 32) launch_patch<32, 16, 1>(c, grid, smem, s);
-        else launch_patch<16, 16, 1>(c, grid, smem, s);
-    } else {
-        if (bm == 128) launch_patch<128, 8, 1>(c, grid, smem, s);
-        else if (bm == 64) launch_patch<64, 8, 1>(c, grid, smem, s);
-        else if (bm == 32) launch_patch<32, 8, 1>(c, grid, smem, s);
-        else launch_patch<16, 8, 1>(c, grid, smem, s);
-    }
+    if (tps == 3 && ck == 16) dispatch_bm<16, 3>(bm, c, grid, smem, s);
+    else if (tps == 3) dispatch_bm<8, 3>(bm, c, grid, smem, s);
+    else if (ck == 16) dispatch_bm<16, 1>(bm, c, grid, smem, s);
+    else dispatch_bm<8, 1>(bm, c, grid, smem, s);
 }
 
 inline CP make_cp(const GG& g, const ConvPlan& p, const float* zeros, const float* wp, float* part) {
@@ -1207,7 +1195,7 @@ inline CP make_cp(const GG& g, const ConvPlan& p, const float* zeros, const floa
     c.y_bs = g.y_bs; c.res_bs = g.res_bs;
     c.tiles_x = p.tiles_x; c.tiles_y = p.tiles_y;
     c.nsplit = p.nsplit; c.cps = p.cps;
-    c.part_stride = (long)g.B * g.M * (p.tiles_y * (p.tw16 ? 8 : TH)) * (p.tiles_x * (p.tw16 ? 16 : TW));      // padded slabs
+    c.part_stride = (long)g.B * g.M * p.Hp * p.Wp;      // padded slabs
     c.act = g.act; c.act_a = g.act_a; c.act_b = g.act_b; c.res_mul = g.res_mul;
     c.add = g.add; c.add_bs = g.add_bs;
 #ifndef CC_CONV_WMAJOR
@@ -1220,20 +1208,36 @@ inline CP make_cp(const GG& g, const ConvPlan& p, const float* zeros, const floa
     return c;
 }
 
+// ---- second stage of split-K.  The epilogue record of a problem whose partial slabs are at `part`; a class no tap reaches
+// (g.Cin == 0) has no slabs: its result is the epilogue of zero (nsplit 0, dense rows)
+inline EPC fill_epc(const GG& g, const ConvPlan& p, const float* part) {
+    const bool empty = g.Cin == 0;
+    EPC c = {};
+    c.part = empty ? nullptr : part; c.bias = g.bias; c.res = g.res; c.add = g.add; c.y = g.y;
+    c.Hp = empty ? g.OHt : p.Hp;
+    c.Wp = empty ? g.OWt : p.Wp;
+    c.part_stride = (long)g.B * g.M * c.Hp * c.Wp;
+    c.nsplit = empty ? 0 : p.nsplit;
+    c.OHt = g.OHt; c.OWt = g.OWt; c.oy0 = g.oy0; c.ox0 = g.ox0;
+    c.total = (empty || p.nsplit > 1) ? (long)g.B * g.M * g.OHt * g.OWt : 0;
+    c.M = g.M; c.so = g.so; c.OH = g.OH; c.OW = g.OW; c.y_bs = g.y_bs; c.res_bs = g.res_bs; c.add_bs = g.add_bs;
+    c.act = g.act; c.act_a = g.act_a; c.act_b = g.act_b; c.res_mul = g.res_mul;
+    return c;
+}
+
+// ... of ONE problem as a launch of its own (a split single-problem launch, or the epilogue of zero)
+inline void launch_splitk_epilogue(const EPC& c, hipStream_t s) {
+    hipLaunchKernelGGL(k_splitk_epilogue, dim3((unsigned)((c.total + 255) / 256)), dim3(256), 0, s, c.part, c.nsplit, c.part_stride, c.bias,
+                       c.res, c.y, c.M, c.OHt, c.OWt, c.so, c.oy0, c.ox0, c.OH, c.OW, c.y_bs, c.res_bs, c.total, c.act, c.act_a, c.act_b,
+                       c.res_mul, c.add, c.add_bs, c.Hp, c.Wp);
+}
+
 // ---- Winograd path (wino.hip): nprob same-shaped problems of geometry g[0] in one launch
 inline ccint::WinoGeom wino_geom(const GG& g) {
     ccint::WinoGeom w = {};
     w.B = g.B; w.Cin = g.Cin; w.H = g.IH; w.W = g.IW; w.x_bs = g.x_bs; w.M = g.M; w.y_bs = g.y_bs; w.res_bs = g.res_bs; w.add_bs = g.add_bs;
     w.act = g.act; w.act_a = g.act_a; w.act_b = g.act_b; w.res_mul = g.res_mul;
     return w;
-}
-
-inline void wino_scope_name(const GG& g, const ConvPlan& p, int nprob, char* nm, int cap) {
-    int nl = p.wn.tile ? snprintf(nm, cap, "k_wino_f2x3_s<%d, %d>", p.wn.tile, p.nsplit > 1 ? 1 : 0)
-                       : snprintf(nm, cap, "k_wino_f2x3<%d>", p.nsplit > 1 ? 1 : 0);
-    if (cctools::env_flag("CC_TIMING_DETAIL"))
-        snprintf(nm + nl, cap - nl, " %dx[B%d M%d C%d %dx%d%s t9 k%d] wg%d", nprob, g.B, g.M, g.Cin, g.OH, g.OW, p.wpad ? "(pad)" : "", p.nsplit,
-                 nprob * p.wn.nqb * p.wn.nmb * p.nsplit);
 }
 
 // MFMA FLOPs the Winograd kernel executes: 16 multiply-adds per 2x2 output tile and channel pair (the direct form: 36)
@@ -1286,21 +1290,35 @@ void ccint::pad_rows_launch(const PadJob* jobs, int n, int B, int W, int Wp, hip
 
 namespace {
 
-// Winograd over a zero-padded copy of the input (ConvPlan::wpad): the copy goes behind the problem's partial slabs; pr / wg are
-// re-pointed at it (rows of wpad floats, dense [B][Cin][H][wpad])
-inline void wino_pad_input(const GG& g, const ConvPlan& p, float* part, hipStream_t s, ccint::WinoProb& pr, ccint::WinoGeom& wg) {
-    float* xpad = part + p.part_floats;
-    const ccint::PadJob job = {g.x, xpad, g.x_bs, g.Cin * g.IH};
-    ccint::pad_rows_launch(&job, 1, g.B, g.IW, p.wpad, s);
-    if (cctools::env_flag("CC_WINO_TRACE"))
-        fprintf(stderr, "wino padded input: B%d M%d C%d %dx%d -> pitch %d, nsplit %d dstep %d\n", g.B, g.M, g.Cin, g.IH, g.IW, p.wpad, p.nsplit, g.dstep);
-    pr.x = xpad;
+// n problems in ONE conv launch (+ ONE split-K epilogue launch): the parity classes of a stride-2 data-gradient, the
+// same-shaped convolutions of parallel branches, and (round 3, cc_conv2d_list) independent layers of DIFFERENT networks --
+// every class carries its own geometry, channel count and epilogue; what the classes of a launch share is the tile
+// configuration (BM, CK) of the kernel instance.  Needs prepacked weight images.  zeros / wp / part: the 64-float zero block,
+// weight image and partial-slab area of the class.
+struct ClsIn { GG g; ConvPlan p; const float* zeros; const float* wp; float* part; };
+
+// Winograd over zero-padded copies of the inputs (ConvPlan::wpad) of n same-shaped problems: each copy goes behind its problem's
+// partial slabs (rows of wpad floats, dense [B][Cin][H][wpad]), 2 * MAXGRP jobs per copy launch; pr / wg are re-pointed at them
+inline void wino_pad_inputs(const ClsIn* cs, int n, hipStream_t s, ccint::WinoProb* pr, ccint::WinoGeom& wg) {
+    const GG& g0 = cs[0].g;
+    const ConvPlan& p = cs[0].p;
+    for (int k0 = 0; k0 < n; k0 += 2 * MAXGRP) {
+        ccint::PadJob jobs[2 * MAXGRP];
+        int nj = 0;
+        for (int k = k0; k < n && k < k0 + 2 * MAXGRP; k++) {
+            float* xpad = cs[k].part + p.part_floats;
+            jobs[nj++] = ccint::PadJob{cs[k].g.x, xpad, cs[k].g.x_bs, g0.Cin * g0.IH};
+            pr[k].x = xpad;
+        }
+        ccint::pad_rows_launch(jobs, nj, g0.B, g0.IW, p.wpad, s);
+    }
     wg.W = p.wpad;
-    wg.x_bs = (long)g.Cin * g.IH * p.wpad;
+    wg.x_bs = (long)g0.Cin * g0.IH * p.wpad;
+    if (cctools::env_flag("CC_WINO_TRACE"))
+        fprintf(stderr, "wino padded input, %d problems: B%d M%d C%d %dx%d -> pitch %d, nsplit %d dstep %d\n", n, g0.B, g0.M, g0.Cin, g0.IH,
+                g0.IW, p.wpad, p.nsplit, g0.dstep);
 }
 
-// ws: [64 zeros][repacked weights][split-K partial slabs]; sized by conv_ws_floats(plan_conv(g))
-// prepacked (optional): {64 zeros, wp} produced earlier by k_repack_table -> no repack launch here
 // A 3x3 / stride-1 / pad-1 problem with <= 4 channels on one side (a prediction head or its data-gradient, a layer with <= 4 inputs)
 // as the conv_heads.hip description: 1 = few reduction channels (k_conv_thinc), 2 = few output channels (k_conv_thinm), 0 = neither
 inline int head_kernel_of(const GG& g, ccint::HeadConv& h) {
@@ -1316,87 +1334,95 @@ inline int head_kernel_of(const GG& g, ccint::HeadConv& h) {
     return 0;
 }
 
-inline void launch_gg(const GG& g, float* ws, hipStream_t s, const float* prepacked = nullptr, const float* pre_zeros = nullptr) {
-    {
-        ccint::HeadConv h;
-        const int hk = head_kernel_of(g, h);
-        if (hk) {
-            char nm[96];
-            int nl = snprintf(nm, sizeof nm, hk == 1 ? "k_conv_thinc<%d>" : "k_conv_thinm<%d>", hk == 1 ? g.Cin : g.M);
-            if (cctools::env_flag("CC_TIMING_DETAIL"))
-                snprintf(nm + nl, sizeof nm - nl, " B%d M%d C%d %dx%d t9", g.B, g.M, g.Cin, g.OHt, g.OWt);
-            cctiming::Scope tsc(nm, 2e-9 * g.B * g.OHt * g.OWt * (double)g.M * g.Cin * 9, s);
-            if (cctools::env_flag("CC_HEAD_TRACE"))
-                fprintf(stderr, "head kernel %d: B%d M%d C%d %dx%d dstep %d\n", hk, g.B, g.M, g.Cin, g.OHt, g.OWt, g.dstep);
-            if (hk == 1 ? ccint::head_conv_thinc_launch(h, s) : ccint::head_conv_thinm_launch(h, s)) return;
-        }
+// What launch_classes does with a list of classes, decided without launching anything (the launch and the name query read it)
+struct ClassForm {
+    bool ok;                   // false: the classes do not share a launch (the caller launches them one by one)
+    bool wino;                 // all of them Winograd problems of one shape: one wino.hip launch
+    int ref;                   // first class with taps: its (bm, ck) are the kernel instance's (-1: no class has taps)
+    int tps, maxy, maxsplit;   // launch-wide: taps per stage, grid y / z (the maxima over the classes)
+    int nc;                    // classes of the conv launch (those with taps)
+    bool stk;                  // the stacked instance (a class stacks tiny maps)
+    bool epi;                  // an epilogue launch follows: a class is split, or no tap reaches it
+    size_t smem;
+};
+
+// ---- kernel names: the strings the timing scopes record (bench.py groups its timings by them, profiles/ is compared across rounds
+// by them) and the cc_conv2d_*_kernel queries answer, formatted HERE only.  hk: the head kernel of head_kernel_of (0: none);
+// f: the merged form whose reference class (g, p) is (nullptr: a launch of its own)
+inline int kernel_name(int hk, const GG& g, const ConvPlan& p, const ClassForm* f, char* nm, int cap) {
+    const int split = p.nsplit > 1 ? 1 : 0;
+    if (hk) return snprintf(nm, cap, hk == 1 ? "k_conv_thinc<%d>" : "k_conv_thinm<%d>", hk == 1 ? g.Cin : g.M);
+    if (f && !f->wino && f->nc == 0) return snprintf(nm, cap, "k_splitk_epilogue_multi");      // no class has taps: the epilogue is all there is
+    if (g.Cin == 0) return snprintf(nm, cap, "k_splitk_epilogue");                             // a class no tap reaches, on its own
+    if (!p.use_patch) return snprintf(nm, cap, "k_gather_gemm<%d>", pick_bm(g.M));
+    if (p.wino) return p.wn.tile ? snprintf(nm, cap, "k_wino_f2x3_s<%d, %d>", p.wn.tile, split) : snprintf(nm, cap, "k_wino_f2x3<%d>", split);
+    if (f) return f->stk ? snprintf(nm, cap, "k_conv_patch_multi_stk<%d, %d>", p.bm, f->tps)
+                         : snprintf(nm, cap, "k_conv_patch_multi<%d, %d, %d>", p.bm, p.ck, f->tps);
+    return p.ipt > 1 ? snprintf(nm, cap, "k_conv_patch_stk<%d, %d, %d>", p.bm, p.tps, split)
+                     : snprintf(nm, cap, "k_conv_patch<%d, %d, %d, %d>", p.bm, p.ck, p.tps, split);
+}
+
+// scope name of a Winograd launch of nprob problems of geometry g
+inline void wino_scope_name(const GG& g, const ConvPlan& p, int nprob, char* nm, int cap) {
+    const int nl = kernel_name(0, g, p, nullptr, nm, cap);
+    if (cctools::env_flag("CC_TIMING_DETAIL"))
+        snprintf(nm + nl, cap - nl, " %dx[B%d M%d C%d %dx%d%s t9 k%d] wg%d", nprob, g.B, g.M, g.Cin, g.OH, g.OW, p.wpad ? "(pad)" : "", p.nsplit,
+                 nprob * p.wn.nqb * p.wn.nmb * p.nsplit);
+}
+
+// ws: the problem's workspace area (ws_image / ws_slabs), sized by conv_ws_floats(plan_conv(g)); plan: plan_conv(g) where the caller has
+// it; prepacked (optional): weight image produced earlier by k_repack_table, pre_zeros its 64 zeros -> no repack launch here
+inline void launch_gg(const GG& g, float* ws, hipStream_t s, const float* prepacked = nullptr, const float* pre_zeros = nullptr,
+                      const ConvPlan* plan = nullptr) {
+    ccint::HeadConv h;
+    const int hk = head_kernel_of(g, h);
+    if (hk) {
+        char nm[96];
+        const int nl = kernel_name(hk, g, ConvPlan(), nullptr, nm, sizeof nm);
+        if (cctools::env_flag("CC_TIMING_DETAIL"))
+            snprintf(nm + nl, sizeof nm - nl, " B%d M%d C%d %dx%d t9", g.B, g.M, g.Cin, g.OHt, g.OWt);
+        cctiming::Scope tsc(nm, 2e-9 * g.B * g.OHt * g.OWt * (double)g.M * g.Cin * 9, s);
+        if (cctools::env_flag("CC_HEAD_TRACE"))
+            fprintf(stderr, "head kernel %d: B%d M%d C%d %dx%d dstep %d\n", hk, g.B, g.M, g.Cin, g.OHt, g.OWt, g.dstep);
+        if (hk == 1 ? ccint::head_conv_thinc_launch(h, s) : ccint::head_conv_thinm_launch(h, s)) return;
     }
-    const ConvPlan p = plan_conv(g);
+    const ConvPlan p = plan ? *plan : plan_conv(g);
     if (!p.use_patch || ws == nullptr) { launch_gg_flat(g, s); return; }
-    const float* zeros = ws;
-    const float* wp = ws + 64;
-    float* part = ws + 64 + (prepacked ? 0 : p.wp_floats);
-    const int T = g.Rt * g.St;
+    float* part = ws_slabs(ws, prepacked ? 0 : p.wp_floats);
+    char nm[128];
     if (p.wino) {
         if (!prepacked)
-            ccint::wino_weights_launch(g.w, ws + 64, g.M, g.Cin, p.Cpad, p.Mpad, g.w_sm, g.w_sc, g.w0, g.w_ri, g.w_sj, wino_flip(g), s);
-        ccint::WinoProb pr = {g.x, prepacked ? prepacked : wp, g.bias, g.res, g.add, g.y, part};
+            ccint::wino_weights_launch(g.w, ws_image(ws), g.M, g.Cin, p.Cpad, p.Mpad, g.w_sm, g.w_sc, g.w0, g.w_ri, g.w_sj, wino_flip(g), s);
+        ccint::WinoProb pr = {g.x, prepacked ? prepacked : ws_image(ws), g.bias, g.res, g.add, g.y, part};
         ccint::WinoGeom wg = wino_geom(g);
-        if (p.wpad) wino_pad_input(g, p, part, s, pr, wg);
+        const ClsIn one = {g, p, nullptr, pr.U, part};
+        if (p.wpad) wino_pad_inputs(&one, 1, s, &pr, wg);
         bool ok;
         {
-            char nm[128];
             wino_scope_name(g, p, 1, nm, sizeof nm);
             cctiming::Scope tsc(nm, wino_gflop(g, p), s);
             ok = ccint::wino_launch(wg, p.wn, &pr, 1, s);
         }
         if (!ok) { launch_gg_flat(g, s); return; }      // x not 16-byte aligned (an odd view): the gather kernel reads the weights as they lie
-        if (p.nsplit > 1) {
-            const long total = (long)g.B * g.M * g.OHt * g.OWt;
-            hipLaunchKernelGGL(k_splitk_epilogue, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, (const float*)part,
-                               p.nsplit, (long)g.B * g.M * p.Hp * p.Wp, g.bias, g.res, g.y, g.M, g.OHt, g.OWt, g.so, g.oy0, g.ox0, g.OH,
-                               g.OW, g.y_bs, g.res_bs, total, g.act, g.act_a, g.act_b, g.res_mul, g.add, g.add_bs, p.Hp, p.Wp);
-        }
+        if (p.nsplit > 1) launch_splitk_epilogue(fill_epc(g, p, part), s);
         return;
     }
-    if (prepacked) {
-        zeros = pre_zeros;
-        wp = prepacked;
-    } else {
-        hipLaunchKernelGGL(k_repack_w, dim3((unsigned)((p.wp_floats + 255) / 256)), dim3(256), 0, s, g.w, ws + 64, ws, g.M, g.Cin,
-                           p.Mpad, p.Cpad, T, g.St, g.w_sm, g.w_sc, g.w0, g.w_ri, g.w_sj);
-    }
+    const float* zeros = prepacked ? pre_zeros : ws;
+    const float* wp = prepacked ? prepacked : ws_image(ws);
+    if (!prepacked)
+        hipLaunchKernelGGL(k_repack_w, dim3((unsigned)((p.wp_floats + 255) / 256)), dim3(256), 0, s, g.w, ws_image(ws), ws, g.M, g.Cin,
+                           p.Mpad, p.Cpad, g.Rt * g.St, g.St, g.w_sm, g.w_sc, g.w0, g.w_ri, g.w_sj);
     const CP c = make_cp(g, p, zeros, wp, part);
     dim3 grid((unsigned)conv_tiles(g, p), (unsigned)(p.Mpad / p.bm), (unsigned)p.nsplit);
     {
-        char nm[96];
-        int nl = p.ipt > 1 ? snprintf(nm, sizeof nm, "k_conv_patch_stk<%d, %d, %d>", p.bm, p.tps, p.nsplit > 1 ? 1 : 0)
-                           : snprintf(nm, sizeof nm, "k_conv_patch<%d, %d, %d, %d>", p.bm, p.ck, p.tps, p.nsplit > 1 ? 1 : 0);
+        const int nl = kernel_name(0, g, p, nullptr, nm, sizeof nm);
         if (cctools::env_flag("CC_TIMING_DETAIL"))
             snprintf(nm + nl, sizeof nm - nl, " B%d M%d C%d %dx%d t%d k%d wg%d", g.B, g.M, g.Cin, g.OHt, g.OWt, g.Rt * g.St, p.nsplit,
                      (int)(grid.x * grid.y * grid.z));
         cctiming::Scope tsc(nm, 2e-9 * g.B * g.OHt * g.OWt * (double)g.M * g.Cin * g.Rt * g.St, s);
         dispatch_patch(p.bm, p.ck, p.tps, c, grid, p.smem, s);
     }
-    if (p.nsplit > 1) {
-        const long total = (long)g.B * g.M * g.OHt * g.OWt;
-        hipLaunchKernelGGL(k_splitk_epilogue, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, (const float*)part,
-                           p.nsplit, c.part_stride, g.bias, g.res, g.y, g.M, g.OHt, g.OWt, g.so, g.oy0, g.ox0, g.OH, g.OW,
-                           g.y_bs, g.res_bs, total, g.act, g.act_a, g.act_b, g.res_mul, g.add, g.add_bs,
-                           p.Hp, p.Wp);
-    }
-}
-
-// n problems in ONE conv launch (+ ONE split-K epilogue launch): the parity classes of a stride-2 data-gradient, the
-// same-shaped convolutions of parallel branches, and (round 3, cc_conv2d_list) independent layers of DIFFERENT networks --
-// every class carries its own geometry, channel count and epilogue; what the classes of a launch share is the tile
-// configuration (BM, CK) of the kernel instance.  Needs prepacked weight images.  zeros / wp / part: the 64-float zero block,
-// weight image and partial-slab area of the class.
-struct ClsIn { GG g; ConvPlan p; const float* zeros; const float* wp; float* part; };
-
-inline size_t smem_cls(const ConvPlan& p, int tps) {
-    const size_t b = (size_t)(2 * tps * p.ck * p.bm + 2 * p.ck * p.PS) * sizeof(float);
-    return (p.bm >= 32 && b < 16384) ? 16384 : b;            // epilogue transpose: 4 KB per wave
+    if (p.nsplit > 1) launch_splitk_epilogue(fill_epc(g, p, part), s);
 }
 
 // same geometry and epilogue form (the Winograd launch shares them between its problems)
@@ -1406,134 +1432,111 @@ inline bool same_problem_shape(const GG& a, const GG& b) {
            a.res_mul == b.res_mul && a.dstep == b.dstep;
 }
 
-inline bool launch_classes(const ClsIn* cs, int n, hipStream_t s, bool idle_taps = false) {
-    if (n < 1 || n > MAXCLS) return false;
-    {   // Winograd problems: all of the launch or none (a mixed list goes back to the caller, which launches one by one)
-        int nw = 0;
-        for (int k = 0; k < n; k++) nw += cs[k].p.wino ? 1 : 0;
-
-        if (nw) {
-            if (nw != n) return false;
-            ccint::WinoProb pr[MAXCLS];
-            EPM e = {};
-            e.n = n;
-            int ebx = 0;
-            const ConvPlan& p = cs[0].p;
-            for (int k = 0; k < n; k++) {
-                const GG& g = cs[k].g;
-                if (!cs[k].wp || !same_problem_shape(g, cs[0].g) || cs[k].p.nsplit != p.nsplit || cs[k].p.cps != p.cps) {
-                    if (cctools::env_flag("CC_WINO_TRACE"))
-                        fprintf(stderr, "wino classes declined: k %d wp %p same %d nsplit %d/%d cps %d/%d\n", k, (const void*)cs[k].wp,
-                                (int)same_problem_shape(g, cs[0].g), cs[k].p.nsplit, p.nsplit, cs[k].p.cps, p.cps);
-                    return false;
-                }
-                pr[k] = ccint::WinoProb{g.x, cs[k].wp, g.bias, g.res, g.add, g.y, cs[k].part};
-                EPC& c = e.c[k];
-                c.part = cs[k].part; c.bias = g.bias; c.res = g.res; c.add = g.add; c.y = g.y;
-                c.Hp = p.Hp; c.Wp = p.Wp;
-                c.part_stride = (long)g.B * g.M * c.Hp * c.Wp;
-                c.nsplit = p.nsplit;
-                c.OHt = g.OHt; c.OWt = g.OWt; c.oy0 = g.oy0; c.ox0 = g.ox0;
-                c.total = p.nsplit > 1 ? (long)g.B * g.M * g.OHt * g.OWt : 0;
-                c.M = g.M; c.so = g.so; c.OH = g.OH; c.OW = g.OW; c.y_bs = g.y_bs; c.res_bs = g.res_bs; c.add_bs = g.add_bs;
-                c.act = g.act; c.act_a = g.act_a; c.act_b = g.act_b; c.res_mul = g.res_mul;
-                ebx += (int)((c.total + 255) / 256);
-                e.bx_end[k] = ebx;
-            }
-            ccint::WinoGeom wg = wino_geom(cs[0].g);
-            if (p.wpad) {
-                // zero-padded input copies of all n problems (same shape: same plan), 2 * MAXGRP jobs per copy launch
-                for (int k = 0; k < n; k++)
-                    if (cs[k].p.wpad != p.wpad || cs[k].p.part_floats != p.part_floats || !cs[k].part) return false;
-                for (int k0 = 0; k0 < n; k0 += 2 * MAXGRP) {
-                    ccint::PadJob jobs[2 * MAXGRP];
-                    int nj = 0;
-                    for (int k = k0; k < n && k < k0 + 2 * MAXGRP; k++) {
-                        const GG& g = cs[k].g;
-                        float* xpad = cs[k].part + p.part_floats;
-                        jobs[nj++] = ccint::PadJob{g.x, xpad, g.x_bs, g.Cin * g.IH};
-                        pr[k].x = xpad;
-                    }
-                    ccint::pad_rows_launch(jobs, nj, cs[0].g.B, cs[0].g.IW, p.wpad, s);
-                }
-                wg.W = p.wpad;
-                wg.x_bs = (long)cs[0].g.Cin * cs[0].g.IH * p.wpad;
+inline ClassForm classes_form(const ClsIn* cs, int n, bool idle_taps) {
+    ClassForm f = {};
+    f.ref = -1;
+    if (n < 1 || n > MAXCLS) return f;
+    // Winograd problems: all of the launch or none (a mixed list goes back to the caller, which launches one by one)
+    int nw = 0;
+    for (int k = 0; k < n; k++) nw += cs[k].p.wino ? 1 : 0;
+    if (nw) {
+        if (nw != n) return f;
+        const ConvPlan& p = cs[0].p;
+        for (int k = 0; k < n; k++) {
+            const GG& g = cs[k].g;
+            if (!cs[k].wp || !same_problem_shape(g, cs[0].g) || cs[k].p.nsplit != p.nsplit || cs[k].p.cps != p.cps) {
                 if (cctools::env_flag("CC_WINO_TRACE"))
-                    fprintf(stderr, "wino padded input, %d problems: B%d M%d C%d %dx%d -> pitch %d, nsplit %d\n", n, cs[0].g.B, cs[0].g.M,
-                            cs[0].g.Cin, cs[0].g.IH, cs[0].g.IW, p.wpad, p.nsplit);
+                    fprintf(stderr, "wino classes declined: k %d wp %p same %d nsplit %d/%d cps %d/%d\n", k, (const void*)cs[k].wp,
+                            (int)same_problem_shape(g, cs[0].g), cs[k].p.nsplit, p.nsplit, cs[k].p.cps, p.cps);
+                return f;
             }
-            {
-                char nm[128];
-                wino_scope_name(cs[0].g, p, n, nm, sizeof nm);
-                cctiming::Scope tsc(nm, n * wino_gflop(cs[0].g, p), s);
-                if (!ccint::wino_launch(wg, p.wn, pr, n, s)) return false;
-            }
-            if (p.nsplit > 1) hipLaunchKernelGGL(k_splitk_epilogue_multi, dim3((unsigned)ebx), dim3(256), 0, s, e);
-            return true;
+            // zero-padded input copies (same shape: same plan) live behind each problem's slabs
+            if (p.wpad && (cs[k].p.wpad != p.wpad || cs[k].p.part_floats != p.part_floats || !cs[k].part)) return f;
         }
+        f.ok = f.wino = true;
+        f.nc = n; f.maxsplit = p.nsplit; f.epi = p.nsplit > 1;
+        return f;
     }
-    size_t smem = 0;
-    int tps = 3, maxsplit = 1, maxy = 1, ref = -1;
+    f.tps = 3; f.maxsplit = 1; f.maxy = 1;
     if (cctools::env_int("CC_CONV_IDLE_TAPS", 1)) idle_taps = true;
     for (int k = 0; k < n; k++) {
         const ConvPlan& p = cs[k].p;
         // a class no tap reaches (the odd output parities of a 1x1 stride-2 data-gradient: DispResNet6's shortcut convolutions):
         // its result is the epilogue of zero -- it takes no workgroup of the conv launch, only a slot of the epilogue launch
-        if (cs[k].g.Cin == 0) continue;
-        if (ref < 0) ref = k;
-        if (!p.use_patch || p.bm != cs[ref].p.bm || p.ck != cs[ref].p.ck || !cs[k].wp) return false;
+        if (cs[k].g.Cin == 0) { f.epi = true; continue; }
+        if (f.ref < 0) f.ref = k;
+        if (!p.use_patch || p.bm != cs[f.ref].p.bm || p.ck != cs[f.ref].p.ck || !cs[k].wp) return f;
         // three taps per stage launch-wide unless a class's patch does not leave room (a class with fewer taps idles the slots)
-        if (p.tps != 3 && !(idle_taps && cs[k].g.Rt * cs[k].g.St < 3 && smem_cls(p, 3) <= 80 * 1024)) tps = 1;
-        if (p.nsplit > maxsplit) maxsplit = p.nsplit;
-        if (p.Mpad / p.bm > maxy) maxy = p.Mpad / p.bm;
+        if (p.tps != 3 && !(idle_taps && cs[k].g.Rt * cs[k].g.St < 3 && patch_smem(p, 3) <= 80 * 1024)) f.tps = 1;
+        if (p.nsplit > f.maxsplit) f.maxsplit = p.nsplit;
+        if (p.Mpad / p.bm > f.maxy) f.maxy = p.Mpad / p.bm;
+        if (p.nsplit > 1) f.epi = true;
+        if (p.ipt > 1) f.stk = true;
+        f.nc++;
     }
+    for (int k = 0; k < n; k++) {
+        if (cs[k].g.Cin == 0) continue;
+        const size_t sm = patch_smem(cs[k].p, f.tps);          // A buffers follow the launch-wide TPS, the patch buffers this class's PS
+        if (sm > f.smem) f.smem = sm;
+    }
+    f.ok = f.smem <= 80 * 1024;
+    return f;
+}
+
+inline bool launch_wino_classes(const ClsIn* cs, int n, hipStream_t s) {
+    ccint::WinoProb pr[MAXCLS];
+    EPM e = {};
+    e.n = n;
+    int ebx = 0;
+    const ConvPlan& p = cs[0].p;
+    for (int k = 0; k < n; k++) {
+        const GG& g = cs[k].g;
+        pr[k] = ccint::WinoProb{g.x, cs[k].wp, g.bias, g.res, g.add, g.y, cs[k].part};
+        e.c[k] = fill_epc(g, p, cs[k].part);
+        ebx += (int)((e.c[k].total + 255) / 256);
+        e.bx_end[k] = ebx;
+    }
+    ccint::WinoGeom wg = wino_geom(cs[0].g);
+    if (p.wpad) wino_pad_inputs(cs, n, s, pr, wg);
+    {
+        char nm[128];
+        wino_scope_name(cs[0].g, p, n, nm, sizeof nm);
+        cctiming::Scope tsc(nm, n * wino_gflop(cs[0].g, p), s);
+        if (!ccint::wino_launch(wg, p.wn, pr, n, s)) return false;
+    }
+    if (p.nsplit > 1) hipLaunchKernelGGL(k_splitk_epilogue_multi, dim3((unsigned)ebx), dim3(256), 0, s, e);
+    return true;
+}
+
+inline bool launch_classes(const ClsIn* cs, int n, const ClassForm& f, hipStream_t s) {
+    if (!f.ok) return false;
+    if (f.wino) return launch_wino_classes(cs, n, s);
     CPM a = {};        // ~3 KB + ~1.5 KB of host stack, passed to the launches by value
     EPM e = {};
     e.n = n;
-    int bx = 0, ebx = 0, epi_any = 0, nc = 0;
-    double gf = 0;
+    int bx = 0, ebx = 0, nc = 0;
+    double gf = 0, wf = 0, xf = 0;
     for (int k = 0; k < n; k++) {
         const GG& g = cs[k].g;
         const ConvPlan& p = cs[k].p;
-        const bool empty = g.Cin == 0;
-        EPC& c = e.c[k];
-        c.part = empty ? nullptr : cs[k].part; c.bias = g.bias; c.res = g.res; c.add = g.add; c.y = g.y;
-        c.Hp = empty ? g.OHt : p.Hp;
-        c.Wp = empty ? g.OWt : p.Wp;
-        c.part_stride = (long)g.B * g.M * c.Hp * c.Wp;
-        c.nsplit = empty ? 0 : p.nsplit;
-        c.OHt = g.OHt; c.OWt = g.OWt; c.oy0 = g.oy0; c.ox0 = g.ox0;
-        c.total = (empty || p.nsplit > 1) ? (long)g.B * g.M * g.OHt * g.OWt : 0;
-        c.M = g.M; c.so = g.so; c.OH = g.OH; c.OW = g.OW; c.y_bs = g.y_bs; c.res_bs = g.res_bs; c.add_bs = g.add_bs;
-        c.act = g.act; c.act_a = g.act_a; c.act_b = g.act_b; c.res_mul = g.res_mul;
-        ebx += (int)((c.total + 255) / 256);
+        e.c[k] = fill_epc(g, p, cs[k].part);
+        ebx += (int)((e.c[k].total + 255) / 256);
         e.bx_end[k] = ebx;
-        if (c.total) epi_any = 1;
-        if (empty) continue;
-        const size_t sm = smem_cls(p, tps);          // A buffers follow the launch-wide TPS, the patch buffers this class's PS
-        if (sm > smem) smem = sm;
+        if (g.Cin == 0) continue;
         a.c[nc] = make_cp(g, p, cs[k].zeros, cs[k].wp, cs[k].part);
         bx += (int)conv_tiles(g, p);
         a.bx_end[nc] = bx;
         nc++;
         gf += 2e-9 * g.B * g.OHt * g.OWt * (double)g.M * g.Cin * g.Rt * g.St;
+        wf += (double)g.M * g.Cin * g.Rt * g.St;
+        xf += (double)g.B * g.Cin * g.IH * g.IW;
     }
     a.n = nc;
-    {   // launch-wide XCD order: weight-major when the classes' weights outweigh their inputs
-        double wf = 0, xf = 0;
-        for (int k = 0; k < nc; k++) {
-            const CP& c = a.c[k];
-            wf += (double)c.M * c.Cin * c.Rt * c.St;
-            xf += (double)c.B * c.Cin * c.IH * c.IW;
-        }
-        a.wmajor = (CC_CONV_WMAJOR && wf > xf) ? 1 : 0;
-    }
-    if (smem > 80 * 1024) return false;
+    a.wmajor = (CC_CONV_WMAJOR && wf > xf) ? 1 : 0;      // launch-wide XCD order: weight-major when the classes' weights outweigh their inputs
     if (nc > 0) {
-        dim3 grid((unsigned)bx, (unsigned)maxy, (unsigned)maxsplit);
+        dim3 grid((unsigned)bx, (unsigned)f.maxy, (unsigned)f.maxsplit);
         char nm[224];
-        int nl = stacked(a) ? snprintf(nm, sizeof nm, "k_conv_patch_multi_stk<%d, %d>", cs[ref].p.bm, tps)
-                            : snprintf(nm, sizeof nm, "k_conv_patch_multi<%d, %d, %d>", cs[ref].p.bm, cs[ref].p.ck, tps);
+        int nl = kernel_name(0, cs[f.ref].g, cs[f.ref].p, &f, nm, sizeof nm);
         if (cctools::env_flag("CC_TIMING_DETAIL")) {
             // classes with the same geometry are counted, not repeated
             for (int k = 0; k < n && nl < (int)sizeof nm - 48; k++) {
@@ -1553,27 +1556,100 @@ inline bool launch_classes(const ClsIn* cs, int n, hipStream_t s, bool idle_taps
             snprintf(nm + nl, sizeof nm - nl, " wg%d", (int)(grid.x * grid.y * grid.z));
         }
         cctiming::Scope tsc(nm, gf, s);
-        dispatch_patch(cs[ref].p.bm, cs[ref].p.ck, tps, a, grid, smem, s);
+        dispatch_patch(cs[f.ref].p.bm, cs[f.ref].p.ck, f.tps, a, grid, f.smem, s);
     }
-    if (epi_any) hipLaunchKernelGGL(k_splitk_epilogue_multi, dim3((unsigned)ebx), dim3(256), 0, s, e);
+    if (f.epi) hipLaunchKernelGGL(k_splitk_epilogue_multi, dim3((unsigned)ebx), dim3(256), 0, s, e);
     return true;
 }
 
-// the G (x parity classes) same-shaped problems of the *_group entry points: split-K planned for the whole launch (mult)
-inline bool launch_gg_classes(const GG* gs, int n, int mult, const float* const* zeros, const float* const* wps,
-                              float* const* parts, hipStream_t s) {
-    if (n < 2 || n > MAXCLS || cctools::env_flag("CC_NO_CLASS_MERGE")) return false;
-    ClsIn cs[MAXCLS];
-    for (int k = 0; k < n; k++) {
-        cs[k].g = gs[k];
-        cs[k].p = plan_conv(gs[k], mult);
-        cs[k].zeros = zeros[k]; cs[k].wp = wps[k]; cs[k].part = parts[k];
+inline bool launch_classes(const ClsIn* cs, int n, hipStream_t s, bool idle_taps = false) {
+    return launch_classes(cs, n, classes_form(cs, n, idle_taps), s);
+}
+
+// ---- the transposed arithmetic and its parity classes
+/* Transposed-convolution arithmetic  gx[n, c, iy, ix] = sum_{k,r,s} wT(k,c,r,s) * gy[n, k, oy, ox],  iy = oy*stride - pad + r: the
+ * data-gradient of conv2d and the forward of ConvTranspose2d (include/ccengine.h: cc_conv2d_dgrad, cc_conv2d_dgrad_group[_add]),
+ * one output parity class at a time so that no structurally-zero tap is multiplied.  gy: [B,K,OH,OW]; gx: [B,C,IH,IW]. */
+struct TProblem {
+    const float* gy; const float* w; const float* bias; float* gx; const float* mul; const float* add;
+    int B, K, OH, OW; long gy_bs;
+    int C, R, S, stride, pad, IH, IW; long gx_bs, mul_bs, add_bs;
+    long w_k_stride, w_c_stride;
+    int act; float act_a, act_b;
+};
+
+// a transposed problem without its operands; the host-only queries plan with the geometry alone
+inline TProblem tr_problem(int B, int K, int OH, int OW, int C, int R, int S, int stride, int pad, int IH, int IW, long w_k_stride,
+                           long w_c_stride, long gy_bs = 0, long gx_bs = 0, long mul_bs = 0, long add_bs = 0, int act = 0, float act_a = 1.f,
+                           float act_b = 0.f) {
+    TProblem t = {};
+    t.B = B; t.K = K; t.OH = OH; t.OW = OW; t.C = C; t.R = R; t.S = S; t.stride = stride; t.pad = pad; t.IH = IH; t.IW = IW;
+    t.w_k_stride = w_k_stride; t.w_c_stride = w_c_stride;
+    t.gy_bs = gy_bs; t.gx_bs = gx_bs; t.mul_bs = mul_bs; t.add_bs = add_bs;
+    t.act = act; t.act_a = act_a; t.act_b = act_b;
+    return t;
+}
+
+// output parity class (py, px) of t as a gather-GEMM problem; false: the class has no output pixel
+inline bool make_dgrad_class(GG& g, const TProblem& t, int py, int px) {
+    const int stride = t.stride, pad = t.pad, R = t.R, S = t.S;
+    // taps r with (py + pad - r) % stride == 0, r ascending: r = r0 + stride*i
+    const int r0 = (py + pad) % stride, s0 = (px + pad) % stride;
+    const int Rt = (r0 < R) ? (R - r0 + stride - 1) / stride : 0;
+    const int St = (s0 < S) ? (S - s0 + stride - 1) / stride : 0;
+    const int OHt = (t.IH - py + stride - 1) / stride, OWt = (t.IW - px + stride - 1) / stride;
+    if (OHt <= 0 || OWt <= 0) return false;
+    g = GG();
+    g.x = t.gy; g.w = t.w; g.bias = t.bias; g.y = t.gx;
+    g.res = t.mul; g.res_bs = t.mul_bs; g.res_mul = t.mul ? 1 : 0;
+    if (t.add) {        // the epilogue's `add` operand exists next to mul only; alone it is a plain residual: gx = act(sum + add)
+        if (t.mul) { g.add = t.add; g.add_bs = t.add_bs; }
+        else { g.res = t.add; g.res_bs = t.add_bs; g.res_mul = 0; }
     }
-    return launch_classes(cs, n, s);
+    g.B = t.B; g.Cin = t.K; g.IH = t.OH; g.IW = t.OW; g.x_bs = t.gy_bs;
+    g.M = t.C; g.w_sm = t.w_c_stride; g.w_sc = t.w_k_stride;
+    g.w0 = r0 * S + s0; g.w_ri = stride * S; g.w_sj = stride;
+    g.Rt = Rt > 0 ? Rt : 1; g.St = St > 0 ? St : 1;
+    // oy = (iy + pad - r)/stride with iy = py + stride*ty, r = r0 + stride*i  ->  oy = ty + (py + pad - r0)/stride - i
+    g.dy0 = (py + pad - r0) / stride; g.dx0 = (px + pad - s0) / stride; g.dstep = -1; g.si = 1;
+    if (Rt == 0 || St == 0) g.Cin = 0;   // no tap reaches this parity class: output = act(bias)
+    g.OHt = OHt; g.OWt = OWt; g.so = stride; g.oy0 = py; g.ox0 = px; g.OH = t.IH; g.OW = t.IW; g.y_bs = t.gx_bs;
+    g.act = t.act; g.act_a = t.act_a; g.act_b = t.act_b;
+    return true;
+}
+
+// The parity classes of a transposed problem, in the order every caller walks them (py, then px), with the plan for `mult` problems
+// per launch.  Two rules every caller keeps:
+//   * a class no tap reaches (g.Cin == 0: the odd parities of a 1x1 stride 2) takes no weight image and no slabs, but it is a class
+//     of the problem: it is counted, and its result is the epilogue of zero;
+//   * a class without output pixels (`lattice` false: IH or IW smaller than the stride) is skipped -- except by the merged launch,
+//     which declines: its class list is the stride^2 classes of every problem.
+struct TClass {
+    GG g; ConvPlan p;
+    bool lattice;              // the class has output pixels (g / p are valid)
+    long img_off;              // its weight image inside the problem's prepacked image, floats (the 64 zeros come first)
+    long slab_off;             // its partial slabs (+ padded input copy) inside the problem's slab area when all classes are live at once
+};
+template <class F>             // f(const TClass&) -> bool: false stops the walk (and is what for_each_class returns)
+inline bool for_each_class(const TProblem& t, int mult, F&& f) {
+    TClass c = {};
+    c.img_off = 64;
+    for (int py = 0; py < t.stride; py++)
+        for (int px = 0; px < t.stride; px++) {
+            c.lattice = make_dgrad_class(c.g, t, py, px);
+            if (c.lattice) c.p = plan_conv(c.g, mult);
+            if (!f(c)) return false;
+            if (c.lattice) {
+                c.img_off += (long)c.p.wp_floats;
+                c.slab_off += (long)(c.p.part_floats + c.p.pad_floats);
+            }
+        }
+    return true;
 }
 
 }  // namespace
 
+// ------------------------------------------------------------------ C ABI
 extern "C" {
 
 static GG make_fwd(const float* x, const float* w, const float* bias, const float* res, float* y, int B, int Cin, int IH,
@@ -1589,34 +1665,30 @@ static GG make_fwd(const float* x, const float* w, const float* bias, const floa
     return g;
 }
 
+// the geometry of a forward problem (what the host-only queries plan with)
+static GG fwd_shape(int B, int Cin, int IH, int IW, int Cout, int R, int S, int stride, int pad, int OH, int OW) {
+    return make_fwd(nullptr, nullptr, nullptr, nullptr, nullptr, B, Cin, IH, IW, 0, Cout, R, S, stride, pad, OH, OW, 0, 0, 0, 1.f, 0.f);
+}
+
 static void fill_desc(const GG& g, const ConvPlan& p, long src, long dst, long* d) {
-    if (p.wino) {        // U = G g G^T (wino_weights.h); d[6] marks the descriptor, the sign of d[7] the tap direction
-        d[0] = src; d[1] = dst; d[2] = g.M; d[3] = g.Cin; d[4] = p.Mpad; d[5] = p.Cpad; d[6] = ccwino::WINO_T; d[7] = wino_flip(g) ? -3 : 3;
-        d[8] = g.w_sm; d[9] = g.w_sc; d[10] = g.w0; d[11] = g.w_ri; d[12] = g.w_sj; d[13] = (long)p.wp_floats; d[14] = 0;
-        d[15] = ccwino::wino_weight_blocks(p.Mpad, p.Cpad);
-        return;
-    }
     d[0] = src; d[1] = dst; d[2] = g.M; d[3] = g.Cin; d[4] = p.Mpad; d[5] = p.Cpad; d[6] = (long)g.Rt * g.St; d[7] = g.St;
     d[8] = g.w_sm; d[9] = g.w_sc; d[10] = g.w0; d[11] = g.w_ri; d[12] = g.w_sj; d[13] = (long)p.wp_floats; d[14] = 0;
     d[15] = repack_blocks(p.Mpad, p.Cpad, g.Rt * g.St);
+    if (p.wino) {        // U = G g G^T (wino_weights.h); d[6] marks the descriptor, the sign of d[7] the tap direction
+        d[6] = ccwino::WINO_T; d[7] = wino_flip(g) ? -3 : 3;
+        d[15] = ccwino::wino_weight_blocks(p.Mpad, p.Cpad);
+    }
 }
 
-/* Per-step weight prepack (optional fast path).  *_pack_desc fill 16-long descriptors ({src, dst, ...}; dst = where the
- * [tap][c][m] image of this layer goes: pack_base + 64 floats (+ the images of earlier parity classes for dgrad)) and
- * return the number of descriptors (0: this geometry does not use the patch kernel); cc_repack_table runs all of them in
- * one launch after the caller has filled d[14] = first block of each descriptor (cumulative sum of d[15] = its block count).
- * Buffers passed as `prepacked` to the conv entry points must start with 64 zero floats. */
+/* Per-step weight prepack (include/ccengine.h): an image is [64 zeros][tap][c][m], for dgrad one [tap][c][m] per parity class with taps */
 size_t cc_conv2d_fwd_pack_floats(int B, int Cin, int IH, int IW, int Cout, int R, int S, int stride, int pad, int OH, int OW) {
-    GG g = make_fwd(nullptr, nullptr, nullptr, nullptr, nullptr, B, Cin, IH, IW, 0, Cout, R, S, stride, pad, OH, OW, 0, 0, 0,
-                    1.f, 0.f);
-    const ConvPlan p = plan_conv(g);
+    const ConvPlan p = plan_conv(fwd_shape(B, Cin, IH, IW, Cout, R, S, stride, pad, OH, OW));
     return (p.use_patch && R * S <= 136) ? 64 + p.wp_floats : 0;      // 136 = tile rows of k_repack_table
 }
 
 int cc_conv2d_fwd_pack_desc(int B, int Cin, int IH, int IW, int Cout, int R, int S, int stride, int pad, int OH, int OW,
                             long src_ptr, long pack_base_ptr, long* desc_out_host) {
-    GG g = make_fwd(nullptr, nullptr, nullptr, nullptr, nullptr, B, Cin, IH, IW, 0, Cout, R, S, stride, pad, OH, OW, 0, 0, 0,
-                    1.f, 0.f);
+    const GG g = fwd_shape(B, Cin, IH, IW, Cout, R, S, stride, pad, OH, OW);
     const ConvPlan p = plan_conv(g);
     if (!p.use_patch) return 0;
     fill_desc(g, p, src_ptr, pack_base_ptr + 64 * (long)sizeof(float), desc_out_host);
@@ -1624,30 +1696,24 @@ int cc_conv2d_fwd_pack_desc(int B, int Cin, int IH, int IW, int Cout, int R, int
 }
 
 size_t cc_conv2d_fwd_ws_bytes(int B, int Cin, int IH, int IW, int Cout, int R, int S, int stride, int pad, int OH, int OW) {
-    GG g = make_fwd(nullptr, nullptr, nullptr, nullptr, nullptr, B, Cin, IH, IW, 0, Cout, R, S, stride, pad, OH, OW, 0, 0, 0,
-                    1.f, 0.f);
-    return conv_ws_floats(plan_conv(g)) * sizeof(float);
+    return conv_ws_floats(plan_conv(fwd_shape(B, Cin, IH, IW, Cout, R, S, stride, pad, OH, OW))) * sizeof(float);
 }
 
-/* y = act(conv2d(x, w, stride, pad) + bias + res).  x: [B,Cin,IH,IW] (batch stride x_bs), w: [Cout,Cin,R,S],
- * y: [B,Cout,OH,OW] (batch stride y_bs; may be a channel slice of a wider tensor).  ws: cc_conv2d_fwd_ws_bytes(). */
 int cc_conv2d_fwd(const float* x, const float* w, const float* bias_or_null, const float* res_or_null, float* y, float* ws,
                   const float* prepacked_or_null, int B, int Cin, int IH, int IW, long x_bs, int Cout, int R, int S, int stride,
                   int pad, int OH, int OW, long y_bs, long res_bs, int act, float act_a, float act_b, void* stream) {
     if (B <= 0 || Cin <= 0 || Cout <= 0 || R <= 0 || S <= 0 || stride <= 0) return CC_ERR_ARG;
     GG g = make_fwd(x, w, bias_or_null, res_or_null, y, B, Cin, IH, IW, x_bs, Cout, R, S, stride, pad, OH, OW, y_bs, res_bs,
                     act, act_a, act_b);
-    launch_gg(g, ws, (hipStream_t)stream, prepacked_or_null ? prepacked_or_null + 64 : nullptr, prepacked_or_null);
+    launch_gg(g, ws, (hipStream_t)stream, prepacked_or_null ? ws_image(prepacked_or_null) : nullptr, prepacked_or_null);
     CC_CHECK_LAUNCH();
     return CC_OK;
 }
 
-/* G same-shaped convolutions (parallel branches of a network) in one launch.  x / w / bias / res / y / prepacked: HOST arrays
- * of G device addresses (0 = null); ws: G consecutive areas of cc_conv2d_fwd_group_ws_bytes() / G bytes each. */
+/* G same-shaped convolutions (parallel branches of a network) in one launch; ws: G consecutive areas of *_group_ws_bytes / G */
 size_t cc_conv2d_fwd_group_ws_bytes(int G, int B, int Cin, int IH, int IW, int Cout, int R, int S, int stride, int pad, int OH,
                                     int OW) {
-    GG g = make_fwd(nullptr, nullptr, nullptr, nullptr, nullptr, B, Cin, IH, IW, 0, Cout, R, S, stride, pad, OH, OW, 0, 0, 0,
-                    1.f, 0.f);
+    const GG g = fwd_shape(B, Cin, IH, IW, Cout, R, S, stride, pad, OH, OW);
     const size_t a = conv_ws_floats(plan_conv(g, G)), b = conv_ws_floats(plan_conv(g));
     return (size_t)G * (a > b ? a : b) * sizeof(float);
 }
@@ -1658,97 +1724,53 @@ int cc_conv2d_fwd_group(int G, const long* x, const long* w, const long* bias, c
     if (G <= 0 || G > MAXCLS || B <= 0 || Cin <= 0 || Cout <= 0 || R <= 0 || S <= 0 || stride <= 0) return CC_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
     const size_t stride_f = cc_conv2d_fwd_group_ws_bytes(G, B, Cin, IH, IW, Cout, R, S, stride, pad, OH, OW) / sizeof(float) / G;
-    GG gs[MAXCLS];
-    const float *zeros[MAXCLS], *wps[MAXCLS];
-    float* parts[MAXCLS];
+    ClsIn cs[MAXCLS];
     bool packed = true;
     for (int k = 0; k < G; k++) {
-        gs[k] = make_fwd((const float*)x[k], (const float*)w[k], bias ? (const float*)bias[k] : nullptr,
-                         res ? (const float*)res[k] : nullptr, (float*)y[k], B, Cin, IH, IW, x_bs, Cout, R, S, stride, pad, OH,
-                         OW, y_bs, res_bs, act, act_a, act_b);
+        cs[k].g = make_fwd((const float*)x[k], (const float*)w[k], bias ? (const float*)bias[k] : nullptr,
+                           res ? (const float*)res[k] : nullptr, (float*)y[k], B, Cin, IH, IW, x_bs, Cout, R, S, stride, pad, OH,
+                           OW, y_bs, res_bs, act, act_a, act_b);
         const float* pk = prepacked ? (const float*)prepacked[k] : nullptr;
         if (!pk) packed = false;
-        zeros[k] = pk;
-        wps[k] = pk ? pk + 64 : nullptr;
-        parts[k] = ws + k * stride_f + 64;
+        cs[k].zeros = pk;
+        cs[k].wp = pk ? ws_image(pk) : nullptr;
+        cs[k].part = ws_slabs(ws + k * stride_f, 0);
     }
-    if (!(G > 1 && packed && ws && launch_gg_classes(gs, G, G, zeros, wps, parts, s))) {
-        for (int k = 0; k < G; k++) launch_gg(gs[k], ws ? ws + k * stride_f : nullptr, s, wps[k], zeros[k]);
+    // one launch for the group (split-K planned for all of it), or one problem after the other
+    bool merged = false;
+    if (G > 1 && packed && ws && !cctools::env_flag("CC_NO_CLASS_MERGE")) {
+        for (int k = 0; k < G; k++) cs[k].p = plan_conv(cs[k].g, G);
+        merged = launch_classes(cs, G, s);
     }
+    if (!merged)
+        for (int k = 0; k < G; k++) launch_gg(cs[k].g, ws ? ws + k * stride_f : nullptr, s, cs[k].wp, cs[k].zeros);
     CC_CHECK_LAUNCH();
     return CC_OK;
 }
 
-/* Transposed-convolution arithmetic  gx[n, c, iy, ix] = sum_{k,r,s} wT(k,c,r,s) * gy[n, k, oy, ox],  iy = oy*stride - pad + r.
- * Used for (a) the data-gradient of conv2d (w: [K,C,R,S] -> w_k_stride = C*R*S, w_c_stride = R*S) and
- * (b) ConvTranspose2d forward (w: [Cin=K, Cout=C, R, S] -> w_k_stride = C*R*S, w_c_stride = R*S as well),
- * one launch per output parity class so that no structurally-zero tap is multiplied.
- * gy: [B,K,OH,OW]; gx: [B,C,IH,IW]. */
-static bool make_dgrad_class(GG& g, int py, int px, const float* gy, const float* w, const float* bias, float* gx, int B,
-                             int K, int OH, int OW, long gy_bs, int C, int R, int S, int stride, int pad, int IH, int IW,
-                             long gx_bs, long w_k_stride, long w_c_stride, int act, float act_a, float act_b,
-                             const float* mul = nullptr, long mul_bs = 0) {
-    // taps r with (py + pad - r) % stride == 0, r ascending: r = r0 + stride*i
-    const int r0 = (py + pad) % stride, s0 = (px + pad) % stride;
-    const int Rt = (r0 < R) ? (R - r0 + stride - 1) / stride : 0;
-    const int St = (s0 < S) ? (S - s0 + stride - 1) / stride : 0;
-    const int OHt = (IH - py + stride - 1) / stride, OWt = (IW - px + stride - 1) / stride;
-    if (OHt <= 0 || OWt <= 0) return false;
-    g = GG();
-    g.x = gy; g.w = w; g.bias = bias; g.res = mul; g.res_bs = mul_bs; g.res_mul = mul ? 1 : 0; g.y = gx;
-    g.B = B; g.Cin = K; g.IH = OH; g.IW = OW; g.x_bs = gy_bs;
-    g.M = C; g.w_sm = w_c_stride; g.w_sc = w_k_stride;
-    g.w0 = r0 * S + s0; g.w_ri = stride * S; g.w_sj = stride;
-    g.Rt = Rt > 0 ? Rt : 1; g.St = St > 0 ? St : 1;
-    // oy = (iy + pad - r)/stride with iy = py + stride*ty, r = r0 + stride*i  ->  oy = ty + (py + pad - r0)/stride - i
-    g.dy0 = (py + pad - r0) / stride; g.dx0 = (px + pad - s0) / stride; g.dstep = -1; g.si = 1;
-    if (Rt == 0 || St == 0) g.Cin = 0;   // no tap reaches this parity class: output = act(bias)
-    g.OHt = OHt; g.OWt = OWt; g.so = stride; g.oy0 = py; g.ox0 = px; g.OH = IH; g.OW = IW; g.y_bs = gx_bs;
-    g.act = act; g.act_a = act_a; g.act_b = act_b;
-    return true;
-}
-
-size_t cc_conv2d_dgrad_group_ws_bytes(int G, int B, int K, int OH, int OW, int C, int R, int S, int stride, int pad, int IH, int IW);
-size_t cc_conv2d_dgrad_ws_bytes(int B, int K, int OH, int OW, int C, int R, int S, int stride, int pad, int IH, int IW) {
-    return cc_conv2d_dgrad_group_ws_bytes(1, B, K, OH, OW, C, R, S, stride, pad, IH, IW);
-}
-
 size_t cc_conv2d_dgrad_pack_floats(int B, int K, int OH, int OW, int C, int R, int S, int stride, int pad, int IH, int IW,
                                    long w_k_stride, long w_c_stride) {
-    size_t tot = 64;
     if (R * S > 136) return 0;
-    for (int py = 0; py < stride; py++)
-        for (int px = 0; px < stride; px++) {
-            GG g;
-            if (!make_dgrad_class(g, py, px, nullptr, nullptr, nullptr, nullptr, B, K, OH, OW, 0, C, R, S, stride, pad, IH, IW, 0,
-                                  w_k_stride, w_c_stride, 0, 1.f, 0.f))
-                continue;
-            if (g.Cin == 0) continue;                    // no tap reaches this parity class (1x1 stride 2): epilogue only, no image
-            const ConvPlan p = plan_conv(g);
-            if (!p.use_patch) return 0;
-            tot += p.wp_floats;
-        }
-    return tot;
+    size_t tot = 64;
+    const bool ok = for_each_class(tr_problem(B, K, OH, OW, C, R, S, stride, pad, IH, IW, w_k_stride, w_c_stride), 1, [&](const TClass& c) {
+        if (!c.lattice || c.g.Cin == 0) return true;
+        if (!c.p.use_patch) return false;
+        tot += c.p.wp_floats;
+        return true;
+    });
+    return ok ? tot : 0;
 }
 
 int cc_conv2d_dgrad_pack_desc(int B, int K, int OH, int OW, int C, int R, int S, int stride, int pad, int IH, int IW,
                               long w_k_stride, long w_c_stride, long src_ptr, long pack_base_ptr, long* desc_out_host) {
     int n = 0;
-    long off = 64;
-    for (int py = 0; py < stride; py++)
-        for (int px = 0; px < stride; px++) {
-            GG g;
-            if (!make_dgrad_class(g, py, px, nullptr, nullptr, nullptr, nullptr, B, K, OH, OW, 0, C, R, S, stride, pad, IH, IW, 0,
-                                  w_k_stride, w_c_stride, 0, 1.f, 0.f))
-                continue;
-            if (g.Cin == 0) continue;
-            const ConvPlan p = plan_conv(g);
-            if (!p.use_patch) return 0;
-            fill_desc(g, p, src_ptr, pack_base_ptr + off * (long)sizeof(float), desc_out_host + 16 * n);
-            off += (long)p.wp_floats;
-            n++;
-        }
-    return n;
+    const bool ok = for_each_class(tr_problem(B, K, OH, OW, C, R, S, stride, pad, IH, IW, w_k_stride, w_c_stride), 1, [&](const TClass& c) {
+        if (!c.lattice || c.g.Cin == 0) return true;
+        if (!c.p.use_patch) return false;
+        fill_desc(c.g, c.p, src_ptr, pack_base_ptr + c.img_off * (long)sizeof(float), desc_out_host + 16 * n++);
+        return true;
+    });
+    return ok ? n : 0;
 }
 
 int cc_repack_table(const long* table_dev, int ndesc, long total_blocks, void* stream) {
@@ -1758,104 +1780,77 @@ int cc_repack_table(const long* table_dev, int ndesc, long total_blocks, void* s
     return CC_OK;
 }
 
-/* G same-shaped problems of the transposed-convolution arithmetic in one launch (all parity classes of all problems).
- * mul (optional, per problem): tensor of gx's shape (batch stride mul_bs); gx = act_grad(sum (+ bias), mul) = the gradient
- * w.r.t. the pre-activation of the layer whose OUTPUT `mul` is (act / act_a / act_b then describe THAT activation);
- * without it gx = act(sum + bias) (ConvTranspose2d forward).  Host pointer arrays as in cc_conv2d_fwd_group. */
 size_t cc_conv2d_dgrad_group_ws_bytes(int G, int B, int K, int OH, int OW, int C, int R, int S, int stride, int pad, int IH, int IW) {
+    const TProblem t = tr_problem(B, K, OH, OW, C, R, S, stride, pad, IH, IW, (long)C * R * S, (long)R * S);
     size_t best = 0;
     for (int mult = 1; mult <= G; mult += (G > 1 ? G - 1 : 1)) {
         size_t wmax = 0, psum = 0;        // the merged launch keeps every class's partial slabs alive at once
-        for (int py = 0; py < stride; py++)
-            for (int px = 0; px < stride; px++) {
-                GG g;
-                if (!make_dgrad_class(g, py, px, nullptr, nullptr, nullptr, nullptr, B, K, OH, OW, 0, C, R, S, stride, pad, IH, IW,
-                                      0, (long)C * R * S, (long)R * S, 0, 1.f, 0.f))
-                    continue;
-                const ConvPlan p = plan_conv(g, mult);
-                if (p.wp_floats > wmax) wmax = p.wp_floats;
-                psum += p.part_floats + p.pad_floats;
-            }
-        const size_t t = 64 + wmax + psum;
-        if (t > best) best = t;
+        for_each_class(t, mult, [&](const TClass& c) {
+            if (!c.lattice) return true;
+            if (c.p.wp_floats > wmax) wmax = c.p.wp_floats;
+            psum += c.p.part_floats + c.p.pad_floats;
+            return true;
+        });
+        const size_t tot = 64 + wmax + psum;
+        if (tot > best) best = tot;
     }
     return (size_t)G * best * sizeof(float);
 }
 
+size_t cc_conv2d_dgrad_ws_bytes(int B, int K, int OH, int OW, int C, int R, int S, int stride, int pad, int IH, int IW) {
+    return cc_conv2d_dgrad_group_ws_bytes(1, B, K, OH, OW, C, R, S, stride, pad, IH, IW);
+}
+
+// The merged form of a call: every parity class of its G problems in ONE launch (launch_classes).  -> the number of classes put
+// into cs (and their launch form in f), or 0: the call runs class by class.  Merged when every problem brings a prepacked image
+// (pk) and a workspace, there are 2 .. MAXCLS classes, each with output pixels, and launch_classes takes them.
+// ws: G consecutive areas of stride_f floats.
+static int dgrad_merged(const TProblem* ts, int G, const float* const* pk, float* ws, size_t stride_f, ClsIn* cs, ClassForm& f) {
+    const int ncls = ts[0].stride * ts[0].stride;
+    if (!ws || G * ncls < 2 || G * ncls > MAXCLS || cctools::env_flag("CC_NO_CLASS_MERGE")) return 0;
+    int n = 0;
+    for (int k = 0; k < G; k++) {
+        if (!pk[k]) return 0;
+        float* slabs = ws_slabs(ws + k * stride_f, 0);
+        const bool all = for_each_class(ts[k], G, [&](const TClass& c) {
+            if (!c.lattice) return false;
+            cs[n++] = ClsIn{c.g, c.p, pk[k], pk[k] + c.img_off, slabs + c.slab_off};
+            return true;
+        });
+        if (!all) return 0;
+    }
+    f = classes_form(cs, n, false);
+    return f.ok ? n : 0;
+}
+
 static int dgrad_group_impl(int G, const long* gy, const long* w, const long* bias, const long* gx, const long* mul,
-                            const long* add, float* ws, const long* prepacked, int B, int K, int OH, int OW, long gy_bs, int C,
-                            int R, int S, int stride, int pad, int IH, int IW, long gx_bs, long mul_bs, long add_bs,
-                            long w_k_stride, long w_c_stride, int act, float act_a, float act_b, void* stream) {
-    if (G <= 0 || G > MAXCLS || B <= 0 || K <= 0 || C <= 0 || stride <= 0) return CC_ERR_ARG;
+                            const long* add, float* ws, const long* prepacked, TProblem t, void* stream) {
+    if (G <= 0 || G > MAXCLS || t.B <= 0 || t.K <= 0 || t.C <= 0 || t.stride <= 0) return CC_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
-    const size_t stride_f = cc_conv2d_dgrad_group_ws_bytes(G, B, K, OH, OW, C, R, S, stride, pad, IH, IW) / sizeof(float) / G;
-    bool packed = true;
-    for (int k = 0; k < G; k++)
-        if (!prepacked || !prepacked[k]) packed = false;
-    const int ncls = stride * stride;
-    if (packed && ws && G * ncls >= 2 && G * ncls <= MAXCLS) {
-        GG gs[MAXCLS];
-        const float *zeros[MAXCLS], *wps[MAXCLS];
-        float* parts[MAXCLS];
-        int n = 0;
-        bool all = true;
-        for (int k = 0; k < G && all; k++) {
-            const float* pk = (const float*)prepacked[k];
-            long off = 64;
-            float* part = ws + k * stride_f + 64;
-            for (int py = 0; py < stride && all; py++)
-                for (int px = 0; px < stride; px++) {
-                    if (!make_dgrad_class(gs[n], py, px, (const float*)gy[k], (const float*)w[k],
-                                          bias ? (const float*)bias[k] : nullptr, (float*)gx[k], B, K, OH, OW, gy_bs, C, R, S,
-                                          stride, pad, IH, IW, gx_bs, w_k_stride, w_c_stride, act, act_a, act_b,
-                                          mul ? (const float*)mul[k] : nullptr, mul_bs)) { all = false; break; }
-                    if (add && add[k]) {
-                        if (mul && mul[k]) { gs[n].add = (const float*)add[k]; gs[n].add_bs = add_bs; }
-                        else { gs[n].res = (const float*)add[k]; gs[n].res_bs = add_bs; gs[n].res_mul = 0; }      // gx = act(sum + add)
-                    }
-                    const ConvPlan p = plan_conv(gs[n], G);
-                    zeros[n] = pk;
-                    wps[n] = pk + off;
-                    parts[n] = part;
-                    off += (long)p.wp_floats;
-                    part += p.part_floats;
-                    n++;
-                }
-        }
-        if (all && launch_gg_classes(gs, n, G, zeros, wps, parts, s)) {
-            CC_CHECK_LAUNCH();
-            return CC_OK;
-        }
+    const size_t stride_f = cc_conv2d_dgrad_group_ws_bytes(G, t.B, t.K, t.OH, t.OW, t.C, t.R, t.S, t.stride, t.pad, t.IH, t.IW) / sizeof(float) / G;
+    TProblem ts[MAXCLS];
+    const float* pk[MAXCLS];
+    for (int k = 0; k < G; k++) {
+        auto at = [k](const long* a) { return a ? (const float*)a[k] : nullptr; };       // (array pointer null = all null)
+        ts[k] = t;
+        ts[k].gy = at(gy); ts[k].w = at(w); ts[k].gx = (float*)gx[k]; ts[k].bias = at(bias); ts[k].mul = at(mul); ts[k].add = at(add);
+        pk[k] = at(prepacked);
+    }
+    ClsIn cs[MAXCLS];
+    ClassForm f;
+    const int n = dgrad_merged(ts, G, pk, ws, stride_f, cs, f);
+    if (n && launch_classes(cs, n, f, s)) {
+        CC_CHECK_LAUNCH();
+        return CC_OK;
     }
     for (int k = 0; k < G; k++) {
-        const float* pk = prepacked ? (const float*)prepacked[k] : nullptr;
         float* wk = ws ? ws + k * stride_f : nullptr;
-        long off = 64;
-        for (int py = 0; py < stride; py++) {
-            for (int px = 0; px < stride; px++) {
-                GG g;
-                if (!make_dgrad_class(g, py, px, (const float*)gy[k], (const float*)w[k], bias ? (const float*)bias[k] : nullptr,
-                                      (float*)gx[k], B, K, OH, OW, gy_bs, C, R, S, stride, pad, IH, IW, gx_bs, w_k_stride,
-                                      w_c_stride, act, act_a, act_b, mul ? (const float*)mul[k] : nullptr, mul_bs))
-                    continue;
-                if (add && add[k]) {
-                    if (mul && mul[k]) { g.add = (const float*)add[k]; g.add_bs = add_bs; }
-                    else { g.res = (const float*)add[k]; g.res_bs = add_bs; g.res_mul = 0; }
-                }
-                if (g.Cin == 0) {                       // result = epilogue of zero
-                    const long total = (long)g.B * g.M * g.OHt * g.OWt;
-                    hipLaunchKernelGGL(k_splitk_epilogue, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, (const float*)nullptr,
-                                       0, total, g.bias, g.res, g.y, g.M, g.OHt, g.OWt, g.so, g.oy0, g.ox0, g.OH, g.OW, g.y_bs, g.res_bs,
-                                       total, g.act, g.act_a, g.act_b, g.res_mul, g.add, g.add_bs, g.OHt, g.OWt);
-                } else if (pk) {
-                    const ConvPlan p = plan_conv(g);
-                    launch_gg(g, wk, s, pk + off, pk);
-                    off += (long)p.wp_floats;
-                } else {
-                    launch_gg(g, wk, s);
-                }
-            }
-        }
+        for_each_class(ts[k], 1, [&](const TClass& c) {
+            if (!c.lattice) return true;
+            if (c.g.Cin == 0) launch_splitk_epilogue(fill_epc(c.g, c.p, nullptr), s);       // result = epilogue of zero
+            else launch_gg(c.g, wk, s, pk[k] ? pk[k] + c.img_off : nullptr, pk[k], &c.p);
+            return true;
+        });
     }
     CC_CHECK_LAUNCH();
     return CC_OK;
@@ -1865,18 +1860,18 @@ int cc_conv2d_dgrad_group(int G, const long* gy, const long* w, const long* bias
                           const long* prepacked, int B, int K, int OH, int OW, long gy_bs, int C, int R, int S, int stride,
                           int pad, int IH, int IW, long gx_bs, long mul_bs, long w_k_stride, long w_c_stride, int act, float act_a,
                           float act_b, void* stream) {
-    return dgrad_group_impl(G, gy, w, bias, gx, mul, nullptr, ws, prepacked, B, K, OH, OW, gy_bs, C, R, S, stride, pad, IH, IW, gx_bs,
-                            mul_bs, 0, w_k_stride, w_c_stride, act, act_a, act_b, stream);
+    return dgrad_group_impl(G, gy, w, bias, gx, mul, nullptr, ws, prepacked,
+                            tr_problem(B, K, OH, OW, C, R, S, stride, pad, IH, IW, w_k_stride, w_c_stride, gy_bs, gx_bs, mul_bs, 0, act, act_a, act_b),
+                            stream);
 }
 
-/* ... with `add`: gx = (sum + add) * act'(mul), or act(sum + add) without mul (act 0: plain accumulation) -- the other gradient contributions of a fan-out tensor (a residual
- * shortcut's gradient, what earlier data-gradients left in gx: add may alias gx) are summed in the epilogue. */
 int cc_conv2d_dgrad_group_add(int G, const long* gy, const long* w, const long* gx, const long* mul, const long* add, float* ws,
                               const long* prepacked, int B, int K, int OH, int OW, long gy_bs, int C, int R, int S, int stride,
                               int pad, int IH, int IW, long gx_bs, long mul_bs, long add_bs, long w_k_stride, long w_c_stride,
                               int act, float act_a, float act_b, void* stream) {
-    return dgrad_group_impl(G, gy, w, nullptr, gx, mul, add, ws, prepacked, B, K, OH, OW, gy_bs, C, R, S, stride, pad, IH, IW, gx_bs,
-                            mul_bs, add_bs, w_k_stride, w_c_stride, act, act_a, act_b, stream);
+    return dgrad_group_impl(G, gy, w, nullptr, gx, mul, add, ws, prepacked,
+                            tr_problem(B, K, OH, OW, C, R, S, stride, pad, IH, IW, w_k_stride, w_c_stride, gy_bs, gx_bs, mul_bs, add_bs, act, act_a, act_b),
+                            stream);
 }
 
 int cc_conv2d_dgrad(const float* gy, const float* w, const float* bias_or_null, float* gx, float* ws,
@@ -1888,17 +1883,9 @@ int cc_conv2d_dgrad(const float* gy, const float* w, const float* bias_or_null, 
                                  0, w_k_stride, w_c_stride, act, act_a, act_b, stream);
 }
 
-/* ---- heterogeneous launch lists (round 3) ------------------------------------------------------------------------------
- * n independent convolution problems -- layers of different networks, or a layer's forward next to another layer's
- * data-gradient -- in as few launches as their tile configurations allow: problems whose kernel instance (BM, CK) agrees
- * share ONE k_conv_patch_multi launch (+ one split-K epilogue launch), <= 12 classes per launch; split-K is planned for
- * the launch as a whole (the chip is filled by all of its problems together).  desc_host: n records of CC_CL_LONGS longs:
- *   0 kind (0: conv2d forward arithmetic, 1: transposed arithmetic = data-gradient / ConvTranspose2d forward)
- *   1 x (kind 1: gy)  2 w  3 bias  4 res (kind 0: added before act; kind 1: `mul`, see cc_conv2d_dgrad_group)  5 y (gx)
- *   6 prepacked weight image (required)  7 add (kind 1 with mul: (sum + add) * act'(mul); may alias y)
- *   8 B  9 Cin (K)  10 IH (OH)  11 IW (OW)  12 x_bs  13 Cout (C)  14 R  15 S  16 stride  17 pad  18 OH (IH)  19 OW (IW)
- *   20 y_bs  21 res_bs  22 add_bs  23 act  24 act_a (float bits)  25 act_b (float bits)  26 w_k_stride  27 w_c_stride
- * ws: cc_conv2d_list_ws_bytes() bytes (partial slabs of every class). */
+/* ---- heterogeneous launch lists (round 3): n independent problems in as few launches as their tile configurations allow --
+ * problems whose kernel instance (BM, CK) agrees share ONE k_conv_patch_multi launch (+ one split-K epilogue launch), <= MAXCLS
+ * classes per launch, split-K planned for the launch as a whole.  Records of CL_LONGS longs: include/ccengine.h. */
 constexpr int CL_LONGS = 32;
 struct ListCls { ClsIn c; int prob; };
 
@@ -1918,24 +1905,22 @@ static int list_classes(int n, const long* d, std::vector<ListCls>& out) {
             lc.c.g = make_fwd((const float*)r[1], (const float*)r[2], (const float*)r[3], (const float*)r[4], (float*)r[5], B, Ci, H0, W0,
                               r[12], Co, R, S, stride, pad, H1, W1, r[20], r[21], (int)r[23], act_a, act_b);
             lc.c.p = plan_conv(lc.c.g);
-            lc.c.zeros = pk; lc.c.wp = pk + 64; lc.prob = i;
+            lc.c.zeros = pk; lc.c.wp = ws_image(pk); lc.prob = i;
             out.push_back(lc);
         } else {
-            long off = 64;
-            for (int py = 0; py < stride; py++)
-                for (int px = 0; px < stride; px++) {
-                    ListCls lc = {};
-                    if (!make_dgrad_class(lc.c.g, py, px, (const float*)r[1], (const float*)r[2], (const float*)r[3], (float*)r[5], B, Ci, H0,
-                                          W0, r[12], Co, R, S, stride, pad, H1, W1, r[20], r[26], r[27], (int)r[23], act_a, act_b,
-                                          (const float*)r[4], r[21]))
-                        continue;
-                    lc.c.g.add = (const float*)r[7]; lc.c.g.add_bs = r[22];
-                    if (lc.c.g.add && !lc.c.g.res_mul) return -1;          // raw accumulation is res (kind 0 form) or add WITH mul
-                    lc.c.p = plan_conv(lc.c.g);
-                    lc.c.zeros = pk; lc.c.wp = pk + off; lc.prob = i;
-                    off += (long)lc.c.p.wp_floats;
-                    out.push_back(lc);
-                }
+            if (r[7] && !r[4]) return -1;          // raw accumulation is res (kind 0 form) or add WITH mul
+            TProblem t = tr_problem(B, Ci, H0, W0, Co, R, S, stride, pad, H1, W1, r[26], r[27], r[12], r[20], r[21], r[22], (int)r[23], act_a, act_b);
+            t.gy = (const float*)r[1]; t.w = (const float*)r[2]; t.bias = (const float*)r[3]; t.gx = (float*)r[5];
+            t.mul = (const float*)r[4]; t.add = (const float*)r[7];
+            for_each_class(t, 1, [&](const TClass& c) {
+                if (!c.lattice) return true;
+                ListCls lc = {};
+                lc.c.g = c.g; lc.c.p = c.p;
+                lc.c.g.add_bs = r[22];
+                lc.c.zeros = pk; lc.c.wp = pk + c.img_off; lc.prob = i;
+                out.push_back(lc);
+                return true;
+            });
         }
     }
     return (int)out.size();
@@ -1949,7 +1934,7 @@ static void list_plan_splits(ListCls** cls, int n, int target) {
     for (int k = 0; k < n; k++) {
         const ConvPlan& p = cls[k]->c.p;
         const GG& g = cls[k]->c.g;
-        const long blocks = conv_tiles(g, p) * (p.Mpad / p.bm);
+        const long blocks = conv_blocks(g, p, 1);
         fill += blocks;
         work += (double)blocks * (p.Cpad / p.ck) * ((g.Rt * g.St + 2) / 3);
     }
@@ -1969,17 +1954,12 @@ static void list_plan_splits(ListCls** cls, int n, int target) {
         }
         if (want > nchunk / cctools::env_int("CC_CONV_MINCHUNKS", 1)) want = nchunk / cctools::env_int("CC_CONV_MINCHUNKS", 1);
         if (want > cctools::env_int("CC_CONV_MAXSPLIT", 32)) want = cctools::env_int("CC_CONV_MAXSPLIT", 32);
-        p.nsplit = 1; p.cps = nchunk;
-        if (want >= 2) {
-            p.cps = (int)((nchunk + want - 1) / want);
-            p.nsplit = (nchunk + p.cps - 1) / p.cps;
-        }
-        p.part_floats = p.nsplit > 1 ? (size_t)p.nsplit * g.B * g.M * p.Hp * p.Wp : 0;
+        set_split(p, g, nchunk, want);
     }
 }
 
 // groups the classes into launches (same (bm, ck), <= MAXCLS, list order kept inside a launch), plans the splits, assigns the
-// partial-slab areas; launches when s_or_null is a stream (ws != nullptr).  -> floats of workspace needed / used, -1: error
+// partial-slab areas; launches when `launch` (ws != nullptr).  -> floats of workspace needed / used, -1: error
 static long list_run(int n, const long* d, float* ws, int target, bool launch, hipStream_t s) {
     std::vector<ListCls> all;
     if (list_classes(n, d, all) < 0) return -1;
@@ -2031,118 +2011,48 @@ int cc_conv2d_list(int n, const long* desc_host, float* ws, int split_target, vo
     return CC_OK;
 }
 
-/* ---- per-kernel timing (measurement aid): cc_timing_enable(1) starts recording (process-wide), cc_timing_collect
- * waits for the recorded kernels and writes one line per device kernel "name\tlaunches\ttotal_ms\ttotal_gflop\n" into the
- * HOST buffer (returns the number of characters, stops recording). */
-#ifdef CC_TOOLS
-int cc_timing_enable(int on) {
-    std::lock_guard<std::mutex> lk(cctiming::mtx);
-    if (on && !cctiming::recs) cctiming::recs = new std::vector<cctiming::Rec>();
-    if (on) cctiming::recs->reserve(4096);
-    if (!on && cctiming::recs) {
-        for (auto& r : *cctiming::recs) { (void)hipEventDestroy(r.e0); (void)hipEventDestroy(r.e1); }
-        delete cctiming::recs;
-        cctiming::recs = nullptr;
-    }
+/* ---- introspection (bench.py groups its per-call timings by the kernel a call dispatches to): the name the call's timing scope
+ * records (kernel_name of the plan and form the launch itself computes), with "+splitk" appended when a split-K epilogue launch follows.
+ * The queries describe a call whose operands are all present and aligned. */
+// (g, p): the problem of a launch of its own, or the reference class of the merged form f
+static int answer_name(const GG& g, const ConvPlan& p, const ClassForm* f, void* name_out_host, int cap) {
+    ccint::HeadConv h;
+    const int hk = f ? 0 : head_kernel_of(g, h);         // launch_gg: head kernels first, then the plan
+    char nm[128];
+    kernel_name(hk, g, p, f, nm, sizeof nm);
+    const bool epilogue = f ? f->epi : (!hk && g.Cin > 0 && p.use_patch && p.nsplit > 1);
+    snprintf((char*)name_out_host, cap, "%s%s", nm, epilogue ? "+splitk" : "");
     return CC_OK;
-}
-
-int cc_timing_collect(void* out_host, int cap) {
-    char* out = (char*)out_host;
-    int len = 0;
-    if (!cctiming::recs || cap <= 0) return 0;
-    struct Agg { std::string name; int n; double ms, gf; };
-    std::vector<Agg> agg;
-    for (auto& r : *cctiming::recs) {
-        float ms = 0.f;
-        (void)hipEventSynchronize(r.e1);
-        (void)hipEventElapsedTime(&ms, r.e0, r.e1);
-        Agg* a = nullptr;
-        for (auto& x : agg) if (x.name == r.name) { a = &x; break; }
-        if (!a) { agg.push_back(Agg{r.name, 0, 0.0, 0.0}); a = &agg.back(); }
-        a->n++; a->ms += ms; a->gf += r.gflop;
-    }
-    for (auto& a : agg) {
-        const int k = snprintf(out + len, cap - len, "%s\t%d\t%.6f\t%.6f\n", a.name.c_str(), a.n, a.ms, a.gf);
-        if (k < 0 || k >= cap - len) break;
-        len += k;
-    }
-    cc_timing_enable(0);       // (takes the lock itself)
-    return len;
-}
-#else
-/* product build: no timing registry (the library keeps no state); the tools build records */
-int cc_timing_enable(int on) { return on ? CC_ERR_ARG : CC_OK; }
-int cc_timing_collect(void* out_host, int cap) { (void)out_host; (void)cap; return 0; }
-#endif
-
-/* 1 for the tools build (switches + timing compiled in), 0 for the product library */
-int cc_is_tools_build(void) {
-#ifdef CC_TOOLS
-    return 1;
-#else
-    return 0;
-#endif
-}
-
-/* ---- introspection (bench.py groups its per-call timings by the kernel a call dispatches to) */
-static void patch_name(const ConvPlan& p, bool multi, char* out, int cap) {
-    if (p.wino && p.wn.tile) { snprintf(out, cap, "k_wino_f2x3_s<%d, %d>%s", p.wn.tile, p.nsplit > 1 ? 1 : 0, p.nsplit > 1 ? "+splitk" : ""); return; }
-    if (p.wino) { snprintf(out, cap, "k_wino_f2x3<%d>%s", p.nsplit > 1 ? 1 : 0, p.nsplit > 1 ? "+splitk" : ""); return; }
-    if (!p.use_patch) { snprintf(out, cap, "k_gather_gemm<%d>", pick_bm(p.Mpad ? p.Mpad : 32)); return; }
-    const char* sk = p.nsplit > 1 ? "+splitk" : "";
-    if (multi && p.ipt > 1) snprintf(out, cap, "k_conv_patch_multi_stk<%d, %d>%s", p.bm, p.tps, sk);
-    else if (multi) snprintf(out, cap, "k_conv_patch_multi<%d, %d, %d>%s", p.bm, p.ck, p.tps, sk);
-    else if (p.ipt > 1) snprintf(out, cap, "k_conv_patch_stk<%d, %d, %d>%s", p.bm, p.tps, p.nsplit > 1 ? 1 : 0, sk);
-    else snprintf(out, cap, "k_conv_patch<%d, %d, %d, %d>%s", p.bm, p.ck, p.tps, p.nsplit > 1 ? 1 : 0, sk);
 }
 
 int cc_conv2d_fwd_kernel(int B, int Cin, int IH, int IW, int Cout, int R, int S, int stride, int pad, int OH, int OW,
                          void* name_out_host, int cap) {
-    GG g = make_fwd(nullptr, nullptr, nullptr, nullptr, nullptr, B, Cin, IH, IW, 0, Cout, R, S, stride, pad, OH, OW, 0, 0, 0,
-                    1.f, 0.f);
-    ccint::HeadConv h;
-    if (const int hk = head_kernel_of(g, h)) {       // (geometry only: the launch also checks the tensors' alignment)
-        snprintf((char*)name_out_host, cap, hk == 1 ? "k_conv_thinc<%d>" : "k_conv_thinm<%d>", hk == 1 ? g.Cin : g.M);
-        return CC_OK;
-    }
-    patch_name(plan_conv(g), false, (char*)name_out_host, cap);
-    return CC_OK;
+    const GG g = fwd_shape(B, Cin, IH, IW, Cout, R, S, stride, pad, OH, OW);
+    return answer_name(g, plan_conv(g), nullptr, name_out_host, cap);
 }
 
+/* prepacked: the merged launch of all parity classes where cc_conv2d_dgrad makes one (dgrad_merged).  A call that runs one launch
+ * per class (stride > 1 without a prepacked image, or a declined merge) cannot be named by one string: the answer is the kernel of
+ * class (0, 0).  A launch without any conv workgroup is named by its epilogue kernel. */
 int cc_conv2d_dgrad_kernel(int B, int K, int OH, int OW, int C, int R, int S, int stride, int pad, int IH, int IW,
                            int prepacked, void* name_out_host, int cap) {
-    GG gs[4];
-    int n = 0;
-    bool all = true;
-    for (int py = 0; py < stride && all; py++)
-        for (int px = 0; px < stride; px++) {
-            if (n >= 4 || !make_dgrad_class(gs[n], py, px, nullptr, nullptr, nullptr, nullptr, B, K, OH, OW, 0, C, R, S, stride, pad,
-                                            IH, IW, 0, (long)C * R * S, (long)R * S, 0, 1.f, 0.f)) { all = false; break; }
-            n++;
-        }
-    if (n == 0) { ((char*)name_out_host)[0] = 0; return CC_OK; }
-    if (n == 1 && stride == 1) {
-        ccint::HeadConv h;
-        if (const int hk = head_kernel_of(gs[0], h)) {
-            snprintf((char*)name_out_host, cap, hk == 1 ? "k_conv_thinc<%d>" : "k_conv_thinm<%d>", hk == 1 ? gs[0].Cin : gs[0].M);
-            return CC_OK;
+    if (cap > 0) ((char*)name_out_host)[0] = 0;
+    const TProblem t = tr_problem(B, K, OH, OW, C, R, S, stride, pad, IH, IW, (long)C * R * S, (long)R * S);
+    alignas(16) static float operand[64];            // stands for the prepacked image and the workspace: never dereferenced
+    if (prepacked) {
+        ClsIn cs[MAXCLS];
+        ClassForm f;
+        const float* pk = operand;
+        if (dgrad_merged(&t, 1, &pk, operand, 0, cs, f)) {
+            const ClsIn& ref = cs[f.ref < 0 ? 0 : f.ref];
+            return answer_name(ref.g, ref.p, &f, name_out_host, cap);
         }
     }
-    ConvPlan p = plan_conv(gs[0]);
-    bool multi = false;
-    if (stride == 2 && prepacked && all && n >= 2 && !cctools::env_flag("CC_NO_CLASS_MERGE")) {
-        multi = true;
-        int tps = 3, maxsplit = 1;
-        for (int k = 0; k < n; k++) {
-            const ConvPlan q = plan_conv(gs[k]);
-            if (!q.use_patch || q.bm != p.bm || q.ck != p.ck) multi = false;
-            if (q.tps != 3) tps = 1;
-            if (q.nsplit > maxsplit) maxsplit = q.nsplit;
-        }
-        if (multi) { p.tps = tps; p.nsplit = maxsplit; }
-    }
-    patch_name(p, multi, (char*)name_out_host, cap);
+    for_each_class(t, 1, [&](const TClass& c) {
+        if (!c.lattice) return true;
+        answer_name(c.g, c.p, nullptr, name_out_host, cap);
+        return false;
+    });
     return CC_OK;
 }
 

@@ -3,7 +3,7 @@
 #include <stddef.h>
 #include <hip/hip_runtime.h>
 
-// ---- per-kernel timing (tools build only; the registry and cc_timing_* are in conv.hip): a Scope brackets the main device kernel
+// ---- per-kernel timing (tools build only; the registry and cc_timing_* are in timing.hip): a Scope brackets the main device kernel
 // of a call with HIP events on its stream.  active = false: nothing is recorded.
 namespace cctiming {
 #ifdef CC_TOOLS

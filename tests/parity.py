@@ -1192,3 +1192,87 @@ def check_wgrad_list(dev, tol=2e-5, shapes=None, groups=None):
     for i, (b, w_) in enumerate(zip(bufs, want)):
         err = float((b.cpu() - w_).abs().max()) / max(float(w_.abs().max()), 1e-30)
         assert err <= tol, ("wgrad_list problem %d" % i, err)
+
+
+# "The query names what runs": (B, Cin, H, W, Cout, k, stride) of a Conv2d layer with pad = k // 2; every geometry is run as the
+# forward call, as its data-gradient without and with a prepacked weight image.  The smallest shapes at which each rule of the
+# launch-form decision (conv.hip classes_form / dgrad_merged / launch_gg) can go wrong.
+KERNEL_NAME_GEOMS = [
+    (1, 16, 8, 26, 64, 1, 2), (2, 48, 16, 32, 16, 1, 2), (2, 96, 2, 7, 136, 1, 2),          # 1x1 stride 2: three parity classes are empty
+    (1, 16, 8, 26, 64, 3, 2), (2, 48, 16, 32, 136, 3, 2), (2, 3, 16, 32, 16, 3, 2),         # 3x3 stride 2: classes of 4 / 2 / 2 / 1 taps,
+    (1, 96, 2, 7, 64, 3, 2),                                                                 # idle tap slots
+    (1, 16, 8, 26, 16, 4, 2), (2, 48, 16, 32, 64, 4, 2),                                     # 4x4 stride 2: four classes of 2 x 2 taps
+    (1, 3, 16, 32, 16, 7, 2), (2, 16, 8, 26, 64, 7, 2),                                      # 7x7 stride 2: 16 / 12 / 12 / 9 taps
+    (2, 16, 2, 7, 64, 3, 2), (2, 48, 2, 7, 16, 3, 1), (2, 16, 2, 7, 16, 4, 2),               # B = 2 on 2x7: stacked tiny maps
+    (1, 3, 2, 7, 136, 3, 2), (2, 3, 2, 7, 136, 3, 1), (1, 96, 2, 7, 136, 3, 2),              # 136 -> 3 on 2x7: split-K
+    (1, 16, 16, 32, 64, 3, 1), (2, 48, 16, 32, 136, 3, 1), (2, 96, 16, 32, 16, 3, 1),        # 3x3 stride 1 on 16x32: Winograd
+    (1, 3, 16, 32, 16, 3, 1), (2, 16, 16, 32, 2, 3, 1), (2, 48, 8, 26, 2, 3, 1),             # <= 4 channels on one side: head kernels
+    (1, 3, 8, 26, 64, 3, 1),
+]
+KERNEL_NAME_GEOMS_PADDED_WINO = [(2, 48, 8, 26, 64, 3, 1), (1, 96, 8, 26, 136, 3, 1)]         # width 26: Winograd over a padded copy
+KERNEL_NAME_CALLS = [("fwd", 0), ("fwd", 1), ("dgrad", 0), ("dgrad", 1)]                      # (call, prepacked)
+# one per rule, for the GPU run: (geometry, call, prepacked)
+KERNEL_NAME_CASES_GPU = [
+    ((1, 16, 8, 26, 64, 1, 2), "dgrad", 1), ((2, 48, 16, 32, 136, 3, 2), "dgrad", 1), ((2, 48, 16, 32, 64, 4, 2), "dgrad", 1),
+    ((2, 16, 8, 26, 64, 7, 2), "dgrad", 0), ((2, 16, 2, 7, 64, 3, 2), "dgrad", 1), ((1, 3, 2, 7, 136, 3, 2), "dgrad", 1),
+    ((2, 48, 16, 32, 136, 3, 1), "fwd", 1), ((2, 16, 16, 32, 2, 3, 1), "fwd", 0),
+]
+
+
+def check_kernel_names(dev, cases):
+    """One engine call per case with the timing registry on (tools build): the set of kernel names its scopes record against the
+    answer of cc_conv2d_{fwd,dgrad}_kernel.  The recorded set equals {answer without "+splitk"}; a stride > 1 data-gradient without
+    a prepacked image runs one launch per parity class, and the answer (class (0, 0)'s kernel) is one of the set.  "+splitk" is in the
+    answer exactly when the kernel's name says it writes partial slabs (the last template argument of the single-problem kernels;
+    the multi-problem kernels decide per class, their names do not say).  -> [(case, answer, recorded)]"""
+    import ctypes
+    import re
+    from cc_amd import ops
+    from cc_amd._lib import engine
+    E = engine()
+    assert E.fn["cc_is_tools_build"]() == 1
+    gen = torch.Generator().manual_seed(0)
+    nbuf, tbuf = ctypes.create_string_buffer(128), ctypes.create_string_buffer(1 << 14)
+    out = []
+    ops.packs.reset()
+    for (B, Cin, H, W, Cout, k, st), call, prepacked in cases:
+        pad = k // 2
+        OH, OW = (H + 2 * pad - k) // st + 1, (W + 2 * pad - k) // st + 1
+        x = torch.randn(B, Cin, H, W, generator=gen).to(dev)
+        gy = torch.randn(B, Cout, OH, OW, generator=gen).to(dev)
+        w = (torch.randn(Cout, Cin, k, k, generator=gen) * 0.2).to(dev)
+        if call == "fwd":
+            geom = (B, Cin, H, W, Cout, k, k, st, pad, OH, OW)
+            src, dst = x, torch.empty_like(gy)
+        else:
+            geom = (B, Cout, OH, OW, Cin, k, k, st, pad, H, W)
+            src, dst = gy, torch.empty_like(x)
+        ws = torch.empty(E.call("cc_conv2d_%s_ws_bytes" % call, *geom) // 4 + 64, device=dev, dtype=torch.float32)
+        pk = None
+        if prepacked:
+            pk = ops.packs.ensure(call, w, geom if call == "fwd" else geom + (Cin * k * k, k * k))
+            ops.packs.prepack_all()
+        E.call("cc_timing_enable", 1)
+        if call == "fwd":
+            E.call("cc_conv2d_fwd", src, w, None, None, dst, ws, pk, B, Cin, H, W, Cin * H * W, Cout, k, k, st, pad, OH, OW,
+                   Cout * OH * OW, Cout * OH * OW, 0, 1.0, 0.0, ops.STREAM)
+        else:
+            E.call("cc_conv2d_dgrad", src, w, None, dst, ws, pk, B, Cout, OH, OW, Cout * OH * OW, Cin, k, k, st, pad, H, W,
+                   Cin * H * W, Cin * k * k, k * k, 0, 1.0, 0.0, ops.STREAM)
+        n = E.fn["cc_timing_collect"](ctypes.addressof(tbuf), 1 << 14)
+        recorded = {ln.split("\t")[0] for ln in tbuf.raw[:n].decode().splitlines()}
+        assert E.fn["cc_conv2d_%s_kernel" % call](*geom, *((1 if pk is not None else 0,) if call == "dgrad" else ()),
+                                                  ctypes.addressof(nbuf), 128) == 0
+        answer = nbuf.value.decode()
+        case = ((B, Cin, H, W, Cout, k, st), call, prepacked, pk is not None)
+        print(case, answer, sorted(recorded))
+        base = answer[:-len("+splitk")] if answer.endswith("+splitk") else answer
+        if call == "dgrad" and st > 1 and pk is None:
+            assert base in recorded, (case, answer, recorded)
+        else:
+            assert recorded == {base}, (case, answer, recorded)
+        if re.match(r"k_conv_patch<|k_conv_patch_stk<|k_wino_f2x3", base):
+            assert (re.search(r"(\d+)>$", base).group(1) == "1") == answer.endswith("+splitk"), (case, answer)
+        out.append((case, answer, recorded))
+    ops.packs.reset()
+    return out

@@ -89,8 +89,10 @@ def test_product_package_reads_no_environment():
 
 def test_conv_planners_answer_the_recorded_plans(golden_dir):
     """The host planners of the product library against tests/golden/conv_plans.json (tools/plan_sweep.py --write-fixture): the
-    weight-gradient workspace and the kernel the weight-gradient, forward and data-gradient calls dispatch to, for every
-    convolution layer of the four networks at the benchmarked sizes and for the geometries of tests/parity.py.  The names are the
+    weight-gradient workspace, the kernel the weight-gradient, forward and data-gradient calls dispatch to, and the workspace
+    bytes (single and G = 3), weight-image floats and repack descriptors of the forward / data-gradient entry points, for every
+    convolution layer of the four networks at the benchmarked sizes and for the geometries of tests/parity.py; the workspace of
+    cc_conv2d_list for windows of 6 network layers (forward and transposed arithmetic alternating).  The names are the
     ones the dispatchers' timing scopes carry -- for the weight gradient: `k_wino_wgrad` also over zero-padded copies (widths that
     are not multiples of 4), `k_wgrad_thinm<M>` for the prediction heads.  A planner edit has to show up as a diff of that file."""
     import json
@@ -100,5 +102,11 @@ def test_conv_planners_answer_the_recorded_plans(golden_dir):
     got = plan_sweep.answers(build.build(), [tuple(r[:10]) for r in fx["rows"]])
     bad = [(r[:10], r[10:], g) for r, g in zip(fx["rows"], got) if r[10:] != g]
     assert not bad, (len(bad), bad[:8])
+    assert fx["list_columns"][1:] == plan_sweep.LIST_COLUMNS and len(fx["lists"]) >= 30
+    wins = [[(j % 2, tuple(fx["rows"][r[0] + j][:10])) for j in range(plan_sweep.LIST_WINDOW)] for r in fx["lists"]]
+    lgot = plan_sweep.list_answers(build.build(), wins)
+    lbad = [(r, g) for r, g in zip(fx["lists"], lgot) if r[1:] != g]
+    assert not lbad, (len(lbad), lbad[:8])
+    assert any(r[1] != r[2] for r in fx["lists"])        # the split target moves the slabs
     names = {r[11] for r in fx["rows"]}
     assert "k_wino_wgrad" in names and any(n.startswith("k_wgrad_thinm<") for n in names)

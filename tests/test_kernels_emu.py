@@ -238,3 +238,19 @@ def test_bias_gradient_table():
 
 def test_sum_strided():
     parity.check_sum_strided("cpu")
+
+
+def test_kernel_queries_name_what_runs(monkeypatch):
+    # cc_conv2d_{fwd,dgrad}_kernel against the names the launches' timing scopes record, per rule of the launch-form decision
+    monkeypatch.setenv("CC_HEAD_MINPIX", "1")            # (the small maps with <= 4 output channels on k_conv_thinm)
+    rep = parity.check_kernel_names("cpu", [(g, c, p) for g in parity.KERNEL_NAME_GEOMS for c, p in parity.KERNEL_NAME_CALLS])
+    names = {a for _, a, _ in rep}
+    for fam in ("k_conv_patch_multi<", "k_conv_patch_multi_stk<", "k_conv_patch<", "k_conv_patch_stk<", "k_wino_f2x3", "k_conv_thinc<",
+                "k_conv_thinm<", "+splitk"):
+        assert any(fam in a for a in names), (fam, sorted(names))
+
+    # width 26 on the Winograd kernel over a zero-padded copy of the input: the thresholds of test_convs_winograd_padded_input
+    for k in ("CC_WINOP_MINM", "CC_WINOP_MINC", "CC_WINOP_MINQ", "CC_WINO_MINM", "CC_WINO_MINC", "CC_WINO_MINQ"):
+        monkeypatch.setenv(k, "1")
+    rep = parity.check_kernel_names("cpu", [(g, c, 1) for g in parity.KERNEL_NAME_GEOMS_PADDED_WINO for c in ("fwd", "dgrad")])
+    assert all(a.startswith("k_wino_f2x3") and a.endswith("+splitk") for _, a, _ in rep), rep

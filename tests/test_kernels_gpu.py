@@ -106,6 +106,17 @@ def test_convs_winograd_padded_input(monkeypatch):
         parity.check_conv_groups("cuda", cases=((2, 12, 5, 26, 40, 16, 1), (1, 16, 4, 13, 24, 24, 1)))      # G = 3 branches per launch
 
 
+def test_kernel_queries_name_what_runs():
+    # cc_conv2d_{fwd,dgrad}_kernel against the names the launches' timing scopes record (tools build: the timing registry), one case
+    # per rule of the launch-form decision; the full case list runs on the emulation build (tests/test_kernels_emu.py)
+    from cc_amd import _lib, build
+    with _lib.use_library(build.build_tools()) as e:
+        assert e.fn["cc_is_tools_build"]() == 1
+        rep = parity.check_kernel_names("cuda", parity.KERNEL_NAME_CASES_GPU)
+    assert len(rep) == 8 and any("multi" in a for _, a, _ in rep)
+    assert _lib.engine().fn["cc_is_tools_build"]() == 0
+
+
 def test_weight_gradient_list():
     # the end-of-stage flush of the weight-gradient queue: groups of different shapes in one cc_conv2d_wgrad_list call
     parity.check_wgrad_list("cuda")
