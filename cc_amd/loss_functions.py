@@ -70,22 +70,24 @@ def _empty(n, ref):
 
 
 class _Jobs:
-    """Host-side job table of a *_jobs entry point: rows of 8 slots (tensors -> device addresses, ints, None) + (H, W)."""
+    """Host-side job table of a *_jobs entry point: rows of 8 slots (tensors -> device addresses, ints, None) + (H, W).
+    `key`: what the row needs of the call's launch-wide arguments (planes, channel counts ...); rows of one call share it."""
 
     def __init__(self):
         self.rows = []
 
-    def add(self, slots, H, W):
-        self.rows.append((list(slots) + [None] * (8 - len(slots)), int(H), int(W)))
+    def add(self, slots, H, W, key=None):
+        self.rows.append((list(slots) + [None] * (8 - len(slots)), int(H), int(W), key))
 
     def __len__(self):
         return len(self.rows)
 
-    def pack(self):
+    def pack(self, j0=0, j1=None):
         import ctypes
         E = engine()
-        arr = (ctypes.c_long * (10 * len(self.rows)))()
-        for j, (slots, H, W) in enumerate(self.rows):
+        rows = self.rows[j0:j1]
+        arr = (ctypes.c_long * (10 * len(rows)))()
+        for j, (slots, H, W, _) in enumerate(rows):
             for k, v in enumerate(slots):
                 if v is None:
                     arr[10 * j + k] = 0
@@ -103,7 +105,29 @@ def _off(t, nfloats):
     return engine()._ptr(t, "job", 0) + 4 * int(nfloats)
 
 
-MAX_JOBS = 24
+MAX_JOBS = 24             # rows of one launch (csrc/jobs.h MAXJOBS: the table travels in the kernel arguments)
+
+
+def _chunk_rows(group=1):
+    """Rows per launch when a table is cut between groups of `group` rows only (the rigid loss: whole levels of R terms)."""
+    return max(MAX_JOBS // group, 1) * group
+
+
+def _launch_jobs(name, jb, args, group=1):
+    """The *_jobs entry point `name` over a table of any length: one call per run of consecutive rows that share their key, of at
+    most MAX_JOBS rows -- whole groups of `group` rows (the reference frames of a pyramid level) -- in row order.  `args`: the
+    arguments behind (jobs, njobs); a callable (j0, j1) -> arguments where they depend on the run [j0, j1): what a kernel indexes
+    by table-local job number (per-job scales, partial-sum areas laid out back to back) is passed from row j0's entry on, and the
+    launch-wide arguments come from the key of row j0.  A table of one key and <= MAX_JOBS rows is one call."""
+    E = engine()
+    rows, step = jb.rows, _chunk_rows(group)
+    j0 = 0
+    while j0 < len(rows):
+        j1 = j0 + 1
+        while j1 < len(rows) and j1 - j0 < step and rows[j1][3] == rows[j0][3]:
+            j1 += 1
+        E.call(name, jb.pack(j0, j1), j1 - j0, *(args(j0, j1) if callable(args) else args))
+        j0 = j1
 
 _nan_flags = []
 _sticky_nan = {}          # device -> 1-element flag: OR of the flags that left the bounded list unchecked
@@ -208,7 +232,7 @@ class _PyramidCache:
                 out = torch.empty(B, 2, h, w, device=lv.device, dtype=torch.float32)
                 ent[2][("ew", h, w)] = out
                 jb.add([lv, out], h, w)
-            engine().call("cc_edge_weights_jobs", jb.pack(), len(jb), B, STREAM)
+            _launch_jobs("cc_edge_weights_jobs", jb, (B, STREAM))
         return {hw: ent[2][("ew",) + hw] for hw in sizes}
 
     def get(self, img, h, w):
@@ -244,13 +268,6 @@ class _PyramidCache:
 
 
 pyramid_cache = _PyramidCache()
-
-
-def _scaled_intrinsics(intrinsics, intrinsics_inv, downscale):
-    """loss_functions.py:91-92."""
-    K_s = torch.cat((intrinsics[:, 0:2] / downscale, intrinsics[:, 2:]), dim=1)
-    Kinv_s = torch.cat((intrinsics_inv[:, :, 0:2] * downscale, intrinsics_inv[:, :, 2:]), dim=2)
-    return K_s, Kinv_s
 
 
 class _HeadGrads:
@@ -368,11 +385,17 @@ class _GradArena:
 # ----------------------------------------------------------------------------- engine extensions: per-scale glue of train.py
 # (not part of the reference's module surface; cc_amd.trainer.cc_forward uses them in place of the per-scale Python list
 # comprehensions of train.py:458,470-471,475-476,488 -- same values, one launch for all scales)
-def _ew_jobs(op, rows, planes, c0=0, nc=0, MC=0):
+def _ew_jobs(op, rows, c0=0, nc=0):
+    """cc_elementwise_jobs over rows (slots, h, w, planes, MC): planes and MC are launch-wide, so a list whose entries differ in
+    (B, C) runs as one launch per run of equal ones."""
     jb = _Jobs()
-    for slots, h, w in rows:
-        jb.add(slots, h, w)
-    engine().call("cc_elementwise_jobs", jb.pack(), len(jb), planes, op, c0, nc, MC, STREAM)
+    for slots, h, w, planes, MC in rows:
+        jb.add(slots, h, w, (planes, MC))
+    _launch_jobs("cc_elementwise_jobs", jb, lambda j0, j1: (jb.rows[j0][3][0], op, c0, nc, jb.rows[j0][3][1], STREAM))
+
+
+def _planes(t):
+    return t.shape[0] * t.shape[1]
 
 
 class _RecipLevelsFn(torch.autograd.Function):
@@ -380,7 +403,7 @@ class _RecipLevelsFn(torch.autograd.Function):
     def forward(ctx, *xs):
         xs = [_f32c(x) for x in xs]
         ys = [torch.empty_like(x) for x in xs]
-        _ew_jobs(0, [([x, y], x.shape[2], x.shape[3]) for x, y in zip(xs, ys)], xs[0].shape[0] * xs[0].shape[1])
+        _ew_jobs(0, [([x, y], x.shape[2], x.shape[3], _planes(x), 0) for x, y in zip(xs, ys)])
         ctx.save_for_backward(*ys)
         ctx.set_materialize_grads(False)
         return tuple(ys)
@@ -393,17 +416,14 @@ class _RecipLevelsFn(torch.autograd.Function):
         for k, (g, y) in enumerate(zip(gs, ys)):
             if g is not None:
                 out[k] = torch.empty_like(y)
-                rows.append(([_f32c(g), y, out[k]], y.shape[2], y.shape[3]))
+                rows.append(([_f32c(g), y, out[k]], y.shape[2], y.shape[3], _planes(y), 0))
         if rows:
-            _ew_jobs(1, rows, ys[0].shape[0] * ys[0].shape[1])
+            _ew_jobs(1, rows)
         return tuple(out)
 
 
 def reciprocal_levels(xs):
-    """[1 / x for x in xs] (train.py:458 depth = 1 / disparity) for same-(B, C) maps of all scales in one launch."""
-    xs = list(xs)
-    if len(xs) > MAX_JOBS or len({(x.shape[0], x.shape[1]) for x in xs}) != 1:
-        return [1 / x for x in xs]
+    """[1 / x for x in xs] (train.py:458 depth = 1 / disparity) for the maps of all scales in one launch."""
     return list(_RecipLevelsFn.apply(*xs))
 
 
@@ -411,11 +431,8 @@ def abs_diff_levels(a_list, b_list):
     """[(a - b).abs() ...] WITHOUT gradient (train.py:475-476: the rigidity masks only ever enter `< THRESH` comparisons)."""
     with torch.no_grad():
         a_list, b_list = [_f32c(a) for a in a_list], [_f32c(b) for b in b_list]
-        if len(a_list) > MAX_JOBS or len({(a.shape[0], a.shape[1]) for a in a_list}) != 1:
-            return [(a - b).abs() for a, b in zip(a_list, b_list)]
         outs = [torch.empty_like(a) for a in a_list]
-        _ew_jobs(2, [([a, b, o], a.shape[2], a.shape[3]) for a, b, o in zip(a_list, b_list, outs)],
-                 a_list[0].shape[0] * a_list[0].shape[1])
+        _ew_jobs(2, [([a, b, o], a.shape[2], a.shape[3], _planes(a), 0) for a, b, o in zip(a_list, b_list, outs)])
         return outs
 
 
@@ -425,7 +442,7 @@ def imagenet_normalize_levels(ims):
     with torch.no_grad():
         ims = [_f32c(im) for im in ims]
         outs = [torch.empty_like(im) for im in ims]
-        _ew_jobs(5, [([im, o], im.shape[2], im.shape[3]) for im, o in zip(ims, outs)], ims[0].shape[0] * 3)
+        _ew_jobs(5, [([im, o], im.shape[2], im.shape[3], im.shape[0] * 3, 0) for im, o in zip(ims, outs)])
         return outs
 
 
@@ -433,32 +450,29 @@ class _ComplementSliceFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, c0, c1, *ms):
         ms = [_f32c(m) for m in ms]
-        B, MC, nc = ms[0].shape[0], ms[0].shape[1], c1 - c0
-        outs = [torch.empty(B, nc, m.shape[2], m.shape[3], device=m.device, dtype=torch.float32) for m in ms]
-        _ew_jobs(3, [([m, o], m.shape[2], m.shape[3]) for m, o in zip(ms, outs)], B * nc, c0, nc, MC)
-        ctx.geom = (c0, nc, MC, B, [tuple(m.shape) for m in ms])
+        nc = c1 - c0
+        outs = [torch.empty(m.shape[0], nc, m.shape[2], m.shape[3], device=m.device, dtype=torch.float32) for m in ms]
+        _ew_jobs(3, [([m, o], m.shape[2], m.shape[3], m.shape[0] * nc, m.shape[1]) for m, o in zip(ms, outs)], c0, nc)
+        ctx.geom = (c0, nc, [tuple(m.shape) for m in ms])
         ctx.set_materialize_grads(False)
         return tuple(outs)
 
     @staticmethod
     def backward(ctx, *gs):
-        c0, nc, MC, B, shapes = ctx.geom
+        c0, nc, shapes = ctx.geom
         out = [None] * len(shapes)
         rows = []
         for k, g in enumerate(gs):
             if g is not None:
                 out[k] = torch.empty(shapes[k], device=g.device, dtype=torch.float32)
-                rows.append(([_f32c(g), out[k]], shapes[k][2], shapes[k][3]))
+                rows.append(([_f32c(g), out[k]], shapes[k][2], shapes[k][3], shapes[k][0] * shapes[k][1], shapes[k][1]))
         if rows:
-            _ew_jobs(4, rows, B * MC, c0, nc, MC)
+            _ew_jobs(4, rows, c0, nc)
         return (None, None) + tuple(out)
 
 
 def complement_slice_levels(masks, c0, c1):
     """[1 - m[:, c0:c1] for m in masks] (train.py:488 flow_exp_mask) for all scales in one launch (and one for the backward)."""
-    masks = list(masks)
-    if len(masks) > MAX_JOBS or len({(m.shape[0], m.shape[1]) for m in masks}) != 1:
-        return [1 - m[:, c0:c1] for m in masks]
     return list(_ComplementSliceFn.apply(int(c0), int(c1), *masks))
 
 
@@ -469,9 +483,7 @@ def rigid_flows_levels(depths, pose, ref_ids, intrinsics, intrinsics_inv):
     import ctypes
     E = engine()
     with torch.no_grad():
-        S, R, B = len(depths), pose.shape[1], pose.shape[0]
-        if S * len(ref_ids) > MAX_JOBS:
-            return [[pose2flow(d.squeeze(1), pose[:, r], intrinsics, intrinsics_inv) for d in depths] for r in ref_ids]
+        R, B = pose.shape[1], pose.shape[0]
         one = (ctypes.c_float * 1)(1.0)
         P = torch.empty(1, R, B, 12, device=pose.device, dtype=torch.float32)
         Kinv_c = _f32c(intrinsics_inv)
@@ -485,7 +497,7 @@ def rigid_flows_levels(depths, pose, ref_ids, intrinsics, intrinsics_inv):
                 jb.add([dd, P[0][r], Kinv_c, f], dd.shape[1], dd.shape[2])
                 fl.append(f)
             out.append(fl)
-        E.call("cc_pose2flow_fwd_jobs", jb.pack(), len(jb), B, 0, STREAM)
+        _launch_jobs("cc_pose2flow_fwd_jobs", jb, (B, 0, STREAM))
         return out
 
 
@@ -516,7 +528,9 @@ def occlusion_masks(flow_bw, flow_fw):
     flow_bw, flow_fw = _f32c(flow_bw.detach()), _f32c(flow_fw.detach())
     B, _, H, W = flow_bw.shape
     no = torch.empty(B, 1, H, W, device=flow_bw.device, dtype=torch.float32)
-    engine().call("cc_flow_noocc", flow_bw, flow_fw, no, B, H, W, STREAM)
+    jb = _Jobs()
+    jb.add([flow_bw, flow_fw, no], H, W)
+    _launch_jobs("cc_flow_noocc_jobs", jb, (B, STREAM))
     occ = (1 - no)[:, 0]
     return occ, occ.clone()
 
@@ -545,23 +559,6 @@ class _PhotoCfg:
         self.__dict__.update(kw)
 
 
-def _photo_term(E, tgt_s, warped, mask_a, a_bs, mask_b, b_bs, gmask, gm_bs, want_grad, cfg, loss_acc, nan_flag, scale=None):
-    """One (scale, reference) term: fused forward (+ adjoint maps).  Returns the scratch needed by the adjoint."""
-    B, _, h, w = tgt_s.shape
-    nblk = E.call("cc_ssim_num_blocks", B, h, w)
-    partials = _empty(nblk * 4, tgt_s)
-    if scale is None:
-        scale = _empty(1, tgt_s)
-    if want_grad:
-        adj = [torch.empty_like(warped) for _ in range(4)]
-    else:
-        adj = [None] * 4
-    E.call("cc_ssim_photo_fwd", tgt_s, warped, mask_a, a_bs, mask_b, b_bs, 0, partials, adj[0], adj[1], adj[2], adj[3],
-           gmask, gm_bs, 1 if want_grad else 0, float(cfg.wssim), float(cfg.qch), float(cfg.lambda_oob), loss_acc,
-           scale, nan_flag, gauss13_ptr(), B, h, w, STREAM)
-    return adj, scale
-
-
 _colscale_cache = {}
 
 
@@ -585,181 +582,162 @@ def _carve(sizes, ref):
     return out
 
 
-def _photo_rigid_jobs(ctx, cfg, tgt_img, intrinsics, intrinsics_inv, pose, refs, depths, masks, need):
-    """loss_functions.py:80-128 with every (scale, reference frame) term of a pass in ONE launch (job tables, csrc/jobs.h):
-    ~10 launches for the 24 terms (pose -> P, occlusion masks, warp, SSIM + robust-L1 + masks, finalize, SSIM adjoint, warp
-    backward, pose gradient, per-scale sums) instead of ~14 per term."""
-    import ctypes
+def _photo_terms_jobs(cfg, B, R, hw, tgt_l, warped, mask_a, a_bs, m, gm, want_grad, loss_acc, nan_flag):
+    """What the two photometric losses share, for the S * R terms (level-major) on their warped frames: fused SSIM + robust-L1 +
+    masks, partial sums, adjoint maps; finalize (loss, per-term normalisers, NaN flag); SSIM adjoint.  mask_a(s, r): the term's
+    occlusion mask (batch stride a_bs * H * W); m[s] / gm[s]: the level's explainability mask [B,MC,h,w] and its gradient, or None.
+    -> (scales [S * R], gwarped per term or None)."""
     E = engine()
-    R, S = cfg.n_refs, cfg.n_scales
-    B = tgt_img.shape[0]
-    want_grad = any(need)
-    loss_acc, nan_flag = _zeros1(tgt_img), _zeros1(tgt_img)
-    arena = _GradArena([pose] + list(refs) + list(depths) + list(masks), [need[4]] + [False] * R + list(need[5 + R:]))
-    hw = []
-    for s in range(S):
-        assert masks[s] is None or depths[s].size()[2:] == masks[s].size()[2:]
-        assert pose.size(1) == R
-        hw.append((depths[s].shape[2], depths[s].shape[3]))
+    S = len(hw)
     px = [h * w for h, w in hw]
-    downs = [tgt_img.size(2) / h for h, _ in hw]
-    pose_c, K_c, Kinv_c = _f32c(pose.detach()), _f32c(intrinsics.detach()), _f32c(intrinsics_inv.detach())
-    kdiv = (ctypes.c_float * (S + 1))(*(downs + [1.0]))
-    P_all = torch.empty(S + 1, R, B, 12, device=tgt_img.device, dtype=torch.float32)
-    E.call("cc_pose_proj_levels", pose_c, K_c, P_all, S + 1, R, B, ctypes.addressof(kdiv), STREAM)
-    Kinv_all = _kinv_levels(Kinv_c, downs)
-    d = [_f32c(depths[s].detach()[:, 0]) for s in range(S)]
-    m = [None if masks[s] is None else _f32c(masks[s].detach()) for s in range(S)]
-    tgt_l = [pyramid_cache.get(tgt_img, h, w) for h, w in hw]
-    ref_l = [[pyramid_cache.get(refs[r], h, w) for h, w in hw] for r in range(R)]
-    # ---- occlusion masks of all scales (full-resolution K at every scale, Q4)
-    no = _carve([B * 4 * n for n in px], tgt_img)
-    jb = _Jobs()
-    for s in range(S):
-        jb.add([d[s], P_all[S], Kinv_c, no[s]], *hw[s])
-    E.call("cc_rigid_noocc_jobs", jb.pack(), len(jb), B, STREAM)
-    # ---- warps
-    warped = _carve([B * 3 * px[s] for s in range(S) for _ in range(R)], tgt_img)
-    jb = _Jobs()
-    for s in range(S):
-        for r in range(R):
-            jb.add([ref_l[r][s], d[s], P_all[s][r], Kinv_all[s], warped[s * R + r]], *hw[s])
-    E.call("cc_inverse_warp_fwd_jobs", jb.pack(), len(jb), B, 3, cfg.border, cfg.ac, STREAM)
-    # ---- fused SSIM + robust-L1 + masks, partial sums, adjoint maps; finalize (loss, per-term normalisers, NaN flag)
+    ref = tgt_l[0]
     nblk = [E.call("cc_ssim_num_blocks", B, h, w) for h, w in hw]
-    partials = _carve([4 * nblk[s] for s in range(S) for _ in range(R)], tgt_img)
-    adj = _carve([4 * B * 3 * px[s] for s in range(S) for _ in range(R)], tgt_img) if want_grad else None
-    gm = [arena.view(1 + R + S + s) if (m[s] is not None and want_grad) else None for s in range(S)]
-    scales = torch.empty(S * R, device=tgt_img.device, dtype=torch.float32)
+    partials = _carve([4 * nblk[s] for s in range(S) for _ in range(R)], ref)
+    adj = _carve([4 * B * 3 * px[s] for s in range(S) for _ in range(R)], ref) if want_grad else None
+    scales = torch.empty(S * R, device=ref.device, dtype=torch.float32)
     jb = _Jobs()
     for s in range(S):
         MC = 0 if m[s] is None else m[s].shape[1]
         for r in range(R):
-            jb.add([tgt_l[s], warped[s * R + r], _off(no[s], r * px[s]),
-                    None if m[s] is None else _off(m[s], r * px[s]),
-                    None if gm[s] is None else _off(gm[s], r * px[s]),
-                    None if adj is None else adj[s * R + r], partials[s * R + r], 4 | (MC << 8) | (MC << 16)], *hw[s])
-    E.call("cc_ssim_photo_fwd_jobs", jb.pack(), len(jb), B, 0, 1 if want_grad else 0, float(cfg.wssim), float(cfg.qch),
-           float(cfg.lambda_oob), loss_acc, scales, nan_flag, gauss13_ptr(), STREAM)
-    if want_grad:
-        gw = _carve([B * 3 * px[s] for s in range(S) for _ in range(R)], tgt_img)
-        jb = _Jobs()
-        for s in range(S):
-            for r in range(R):
-                j = s * R + r
-                jb.add([adj[j], tgt_l[s], warped[j], _off(scales, j), gw[j]], *hw[s])
-        E.call("cc_ssim_photo_bwd_jobs", jb.pack(), len(jb), B, gauss13_ptr(), STREAM)
-        gd_all = _carve([R * B * px[s] for s in range(S)], tgt_img)
-        nb = [(n + 255) // 256 for n in px]
-        gpp = _carve([B * nb[s] * 12 for s in range(S) for _ in range(R)], tgt_img)
-        jb, jp = _Jobs(), _Jobs()
-        for s in range(S):
-            for r in range(R):
-                j = s * R + r
-                jb.add([gw[j], ref_l[r][s], d[s], P_all[s][r], Kinv_all[s], _off(gd_all[s], r * B * px[s]), gpp[j]], *hw[s])
-                jp.add([gpp[j]], *hw[s])
-        E.call("cc_inverse_warp_bwd_jobs", jb.pack(), len(jb), B, 3, cfg.border, cfg.ac, STREAM)
-        if need[4]:
-            E.call("cc_pose_grad_jobs", jp.pack(), len(jp), S, R, B, pose_c, K_c, arena.view(0), ctypes.addressof(kdiv), STREAM)
-        jb = _Jobs()
-        for s in range(S):
-            gdv = arena.view(1 + R + s)
-            if gdv is None and gm[s] is None:
-                continue
-            jb.add([gd_all[s] if gdv is not None else None, gdv, gm[s], _off(scales, s * R)], *hw[s])
-        if len(jb):
-            E.call("cc_sum_refs_scale_jobs", jb.pack(), len(jb), B, R, R, STREAM)
-    _register_nan_flag(nan_flag)
-    ctx.arena = arena
-    ctx.need = need
-    return loss_acc.reshape(())
+            j = s * R + r
+            jb.add([tgt_l[s], warped[j], mask_a(s, r), None if m[s] is None else _off(m[s], r * px[s]),
+                    None if gm[s] is None else _off(gm[s], r * px[s]), None if adj is None else adj[j], partials[j],
+                    a_bs | (MC << 8) | (MC << 16)], *hw[s])
+    _launch_jobs("cc_ssim_photo_fwd_jobs", jb,
+                 lambda j0, j1: (B, 0, 1 if want_grad else 0, float(cfg.wssim), float(cfg.qch), float(cfg.lambda_oob), loss_acc,
+                                 _off(scales, j0), nan_flag, gauss13_ptr(), STREAM), R)
+    if not want_grad:
+        return scales, None
+    gw = _carve([B * 3 * px[s] for s in range(S) for _ in range(R)], ref)
+    jb = _Jobs()
+    for s in range(S):
+        for r in range(R):
+            j = s * R + r
+            jb.add([adj[j], tgt_l[s], warped[j], _off(scales, j), gw[j]], *hw[s])
+    _launch_jobs("cc_ssim_photo_bwd_jobs", jb, (B, gauss13_ptr(), STREAM), R)
+    return scales, gw
+
+
+def _mask_grad_rows(jb, gd_all, gdv, gm, scales, R, hw):
+    """The cc_sum_refs_scale_jobs rows of a photometric loss: per level the sum of the per-frame depth gradients (or None) and the
+    mask gradient times the per-term normalisers, which are known only after the reduction.  A mask may have more channels than
+    the loss has terms per level (the reference reads mask[:, i], i < R): the others get gradient 0."""
+    for s in range(len(hw)):
+        if gdv[s] is None and gm[s] is None:
+            continue
+        MC, sc = R, _off(scales, s * R)
+        if gm[s] is not None and gm[s].shape[1] != R:
+            MC = gm[s].shape[1]
+            gm[s][:, R:] = 0
+            sc = torch.cat([scales[s * R:(s + 1) * R], scales.new_ones(MC - R)])
+        jb.add([gd_all[s] if gdv[s] is not None else None, gdv[s], gm[s], sc], *hw[s], key=MC)
+    return jb
+
+
+def _check_mask_channels(masks, R):
+    for mk in masks:
+        if mk is not None and mk.shape[1] < R:
+            raise IndexError("explainability mask with %d channels for %d reference frames" % (mk.shape[1], R))
 
 
 class _PhotoRigidFn(torch.autograd.Function):
-    """loss_functions.py:80-128 over all scales and reference frames."""
+    """loss_functions.py:80-128 with every (scale, reference frame) term of a pass in ONE launch (job tables, csrc/jobs.h):
+    ~10 launches for the 24 terms (pose -> P, occlusion masks, warp, SSIM + robust-L1 + masks, finalize, SSIM adjoint, warp
+    backward, pose gradient, per-scale sums) instead of ~14 per term.  A longer list of terms runs as chunks of whole levels."""
 
     @staticmethod
     def forward(ctx, cfg, tgt_img, intrinsics, intrinsics_inv, pose, *rest):
-        R, S = cfg.n_refs, cfg.n_scales
-        refs = rest[:R]
-        depths = rest[R:R + S]
-        masks = rest[R + S:]
+        import ctypes
         E = engine()
-        dev = tgt_img.device
+        R, S = cfg.n_refs, cfg.n_scales
+        refs, depths, masks = rest[:R], rest[R:R + S], rest[R + S:]
         need = ctx.needs_input_grad
-        if (cfg.rotation_mode == 'euler' and R * S <= MAX_JOBS and R == 4
-                and all(mk is None or mk.shape[1] == R for mk in masks)):
-            return _photo_rigid_jobs(ctx, cfg, tgt_img, intrinsics, intrinsics_inv, pose, refs, depths, masks, need)
+        B = tgt_img.shape[0]
         want_grad = any(need)
+        euler = cfg.rotation_mode == 'euler'
+        _check_mask_channels(masks, R)
         loss_acc, nan_flag = _zeros1(tgt_img), _zeros1(tgt_img)
-        Kinv_full = _f32c(intrinsics_inv.detach())
-        with torch.enable_grad():
-            pose_l = pose.detach().requires_grad_(bool(need[4]))
-            K_d = intrinsics.detach()
-            P_full = [projection_matrix(pose_l[:, r], K_d, cfg.rotation_mode) for r in range(R)]
-        P_full_c = torch.stack([_f32c(p.detach()) for p in P_full]).contiguous()      # [4,B,3,4], shared by all scales
-        direct_pose = cfg.rotation_mode == 'euler'      # HIP pose->P adjoint instead of a torch graph over 17 tiny ops
         # stash layout = the differentiable inputs: pose, refs (no gradient), depths, masks
         arena = _GradArena([pose] + list(rest), [need[4]] + [False] * R + list(need[5 + R:]))
-        gpose_acc = None
-        if want_grad and need[4] and direct_pose:
-            gpose_acc = arena.view(0).zero_()
-        K_c = _f32c(K_d)
-        gP_all, P_all = [], []
+        hw = []
         for s in range(S):
-            d4 = depths[s]
-            assert masks[s] is None or d4.size()[2:] == masks[s].size()[2:]
+            assert masks[s] is None or depths[s].size()[2:] == masks[s].size()[2:]
             assert pose.size(1) == R
-            B, _, h, w = d4.shape
-            d = _f32c(d4.detach()[:, 0])
-            HW = h * w
-            downscale = tgt_img.size(2) / h
-            tgt_s = pyramid_cache.get(tgt_img, h, w)
-            no = _rigid_noocc(d, P_full_c, Kinv_full)                        # [B,4,h,w]
-            K_s, Kinv_s = _scaled_intrinsics(K_d, intrinsics_inv.detach(), downscale)
-            Kinv_s = _f32c(Kinv_s)
-            m = None if masks[s] is None else _f32c(masks[s].detach())
-            gd_all = torch.empty((R,) + tuple(d.shape), device=dev, dtype=torch.float32) if (want_grad and need[5 + R + s]) else None
-            gm = arena.view(1 + R + S + s) if (m is not None and want_grad) else None
-            scales = _empty(R, tgt_s)
+            hw.append((depths[s].shape[2], depths[s].shape[3]))
+        px = [h * w for h, w in hw]
+        downs = [tgt_img.size(2) / h for h, _ in hw]
+        pose_c, K_c, Kinv_c = _f32c(pose.detach()), _f32c(intrinsics.detach()), _f32c(intrinsics_inv.detach())
+        # ---- P = K_s.[R|t] per level [R,B,12] (K rows 0, 1 / downscale, :91) and with the full-resolution K (occlusion masks, Q4)
+        if euler:
+            # HIP pose -> P (and, below, its adjoint): per chunk of levels, the full-resolution level rides with the last chunk
+            P_lv, kdiv = [], {}
+            step = _chunk_rows(R) // R
+            for s0 in range(0, S, step):
+                kd = downs[s0:s0 + step] + ([1.0] if s0 + step >= S else [])
+                kdiv[s0 * R] = (ctypes.c_float * len(kd))(*kd)
+                Pc = torch.empty(len(kd), R, B, 12, device=tgt_img.device, dtype=torch.float32)
+                E.call("cc_pose_proj_levels", pose_c, K_c, Pc, len(kd), R, B, ctypes.addressof(kdiv[s0 * R]), STREAM)
+                P_lv += list(Pc[:len(downs[s0:s0 + step])])
+            P_full = Pc[-1]
+        else:
+            # any other rotation mode: the reference's algebra as a torch graph over the pose.  The occlusion masks stay on Euler
+            # angles (depth_occlusion_masks calls pose2flow without a rotation mode, :133)
+            with torch.enable_grad():
+                pose_l = pose.detach().requires_grad_(bool(need[4]))
+                P_graph = [projection_matrix(pose_l[:, r], intrinsics.detach(), cfg.rotation_mode, k_div=downs[s])
+                           for s in range(S) for r in range(R)]
+            P_lv = [torch.stack([_f32c(p.detach()) for p in P_graph[s * R:(s + 1) * R]]) for s in range(S)]
+            one = (ctypes.c_float * 1)(1.0)
+            P_full = torch.empty(R, B, 12, device=tgt_img.device, dtype=torch.float32)
+            E.call("cc_pose_proj_levels", pose_c, K_c, P_full, 1, R, B, ctypes.addressof(one), STREAM)
+        Kinv_all = _kinv_levels(Kinv_c, downs)
+        d = [_f32c(depths[s].detach()[:, 0]) for s in range(S)]
+        m = [None if masks[s] is None else _f32c(masks[s].detach()) for s in range(S)]
+        tgt_l = [pyramid_cache.get(tgt_img, h, w) for h, w in hw]
+        ref_l = [[pyramid_cache.get(refs[r], h, w) for h, w in hw] for r in range(R)]
+        # ---- occlusion masks of all scales (full-resolution K at every scale, Q4)
+        no = _carve([B * 4 * n for n in px], tgt_img)
+        jb = _Jobs()
+        for s in range(S):
+            jb.add([d[s], P_full, Kinv_c, no[s]], *hw[s])
+        _launch_jobs("cc_rigid_noocc_jobs", jb, (B, STREAM))
+        # ---- warps
+        warped = _carve([B * 3 * px[s] for s in range(S) for _ in range(R)], tgt_img)
+        jb = _Jobs()
+        for s in range(S):
             for r in range(R):
-                ref_s = pyramid_cache.get(refs[r], h, w)
-                if direct_pose:
-                    with torch.no_grad():
-                        P = projection_matrix(pose_l[:, r], K_d, 'euler', k_div=downscale)
-                else:
-                    with torch.enable_grad():
-                        P = projection_matrix(pose_l[:, r], K_s, cfg.rotation_mode)
-                Pc = _f32c(P.detach())
-                warped = torch.empty_like(ref_s)
-                E.call("cc_inverse_warp_fwd", ref_s, d, Pc, Kinv_s, warped, B, 3, h, w, cfg.border, cfg.ac, STREAM)
-                adj, scale = _photo_term(
-                    E, tgt_s, warped, no.view(-1)[r * HW:], 4 * HW,
-                    None if m is None else m.view(-1)[r * HW:], 4 * HW,
-                    None if gm is None else gm.view(-1)[r * HW:], 4 * HW, want_grad, cfg, loss_acc, nan_flag,
-                    scale=scales[r:r + 1])
-                if want_grad:
-                    gw = torch.empty_like(warped)
-                    E.call("cc_ssim_photo_bwd", adj[0], adj[1], adj[2], adj[3], tgt_s, warped, scale, gw, 0, gauss13_ptr(),
-                           B, h, w, STREAM)
-                    gd_r = gd_all[r] if gd_all is not None else torch.empty_like(d)
-                    gP = torch.empty_like(Pc)
-                    ws = _empty(E.call("cc_warp_partials_bytes", B, h, w) // 4, d)
-                    E.call("cc_inverse_warp_bwd", gw, ref_s, d, Pc, Kinv_s, gd_r, gP, None, ws, B, 3, h, w, cfg.border,
-                           cfg.ac, STREAM)
-                    if gpose_acc is not None:
-                        pv = pose_l.detach()[:, r]
-                        E.call("cc_pose_proj_bwd", gP, pv.data_ptr(), pv.stride(0), K_c, gpose_acc[:, r].data_ptr(),
-                               gpose_acc.stride(0), B, float(downscale), 1, STREAM)
-                    else:
-                        gP_all.append(gP)
-                        P_all.append(P)
-            if gd_all is not None:       # sum over the reference frames in the reference's order (r = 0..3), one launch
-                torch.sum(gd_all, dim=0, out=arena.view(1 + R + s).view(d.shape))
-            if gm is not None:           # the per-reference normaliser (known only after the reduction), one launch
-                gm *= scales.view(1, R, 1, 1)
-        if want_grad and need[4] and gpose_acc is None:
-            arena.view(0).copy_(torch.autograd.grad(P_all, pose_l, gP_all)[0])
+                jb.add([ref_l[r][s], d[s], P_lv[s][r], Kinv_all[s], warped[s * R + r]], *hw[s])
+        _launch_jobs("cc_inverse_warp_fwd_jobs", jb, (B, 3, cfg.border, cfg.ac, STREAM), R)
+        gm = [arena.view(1 + R + S + s) if (m[s] is not None and want_grad) else None for s in range(S)]
+        scales, gw = _photo_terms_jobs(cfg, B, R, hw, tgt_l, warped, lambda s, r: _off(no[s], r * px[s]), 4, m, gm, want_grad,
+                                       loss_acc, nan_flag)
+        if want_grad:
+            gd_all = _carve([R * B * px[s] for s in range(S)], tgt_img)
+            nb = [(n + 255) // 256 for n in px]
+            gpp = _carve([B * nb[s] * 12 for s in range(S) for _ in range(R)], tgt_img)
+            jb, jp = _Jobs(), _Jobs()
+            for s in range(S):
+                for r in range(R):
+                    j = s * R + r
+                    jb.add([gw[j], ref_l[r][s], d[s], P_lv[s][r], Kinv_all[s], _off(gd_all[s], r * B * px[s]), gpp[j]], *hw[s])
+                    jp.add([gpp[j]], *hw[s])
+            _launch_jobs("cc_inverse_warp_bwd_jobs", jb, (B, 3, cfg.border, cfg.ac, STREAM), R)
+            if need[4] and euler:
+                gpose, more = arena.view(0), []
+
+                def pose_grad_args(j0, j1):
+                    if j0:                         # the chunks' pose gradients are added in chunk order
+                        more.append(torch.empty_like(gpose))
+                    return ((j1 - j0) // R, R, B, pose_c, K_c, more[-1] if j0 else gpose, ctypes.addressof(kdiv[j0]), STREAM)
+                _launch_jobs("cc_pose_grad_jobs", jp, pose_grad_args, R)
+                for g in more:
+                    gpose += g
+            elif need[4]:
+                gP = [gpp[s * R + r].view(B, nb[s], 12).sum(1) for s in range(S) for r in range(R)]
+                arena.view(0).copy_(torch.autograd.grad(P_graph, pose_l, gP)[0])
+            jb = _mask_grad_rows(_Jobs(), gd_all, [arena.view(1 + R + s) for s in range(S)], gm, scales, R, hw)
+            if len(jb):
+                _launch_jobs("cc_sum_refs_scale_jobs", jb, lambda j0, j1: (B, R, jb.rows[j0][3], STREAM))
         _register_nan_flag(nan_flag)
         ctx.arena = arena
         ctx.need = need
@@ -791,82 +769,9 @@ def photometric_reconstruction_loss(tgt_img, ref_imgs, intrinsics, intrinsics_in
     return _PhotoRigidFn.apply(cfg, tgt_img, intrinsics, intrinsics_inv, pose, *ref_imgs, *depth, *explainability_mask)
 
 
-def _photo_flow_jobs(ctx, cfg, tgt_img, refs, flows, masks, need, rest):
-    """loss_functions.py:27-77, every (scale, reference frame) term of a pass in one launch (see _photo_rigid_jobs)."""
-    E = engine()
-    R, S = cfg.n_refs, cfg.n_scales
-    B = tgt_img.shape[0]
-    want_grad = any(need)
-    loss_acc, nan_flag = _zeros1(tgt_img), _zeros1(tgt_img)
-    arena = _GradArena(list(rest), [False] * R + list(need[2 + R:]))      # refs (no gradient), flows, masks
-    fl = [[_f32c(flows[i][s].detach()) for s in range(S)] for i in range(R)]
-    hw = [(fl[0][s].shape[2], fl[0][s].shape[3]) for s in range(S)]
-    px = [h * w for h, w in hw]
-    for s in range(S):
-        assert masks[s] is None or fl[0][s].size()[2:] == masks[s].size()[2:]
-    m = [None if masks[s] is None else _f32c(masks[s].detach()) for s in range(S)]
-    tgt_l = [pyramid_cache.get(tgt_img, h, w) for h, w in hw]
-    ref_l = [[pyramid_cache.get(refs[i], h, w) for h, w in hw] for i in range(R)]
-    no = _carve([B * n for n in px], tgt_img)
-    jb = _Jobs()
-    for s in range(S):
-        jb.add([fl[0][s], fl[1][s], no[s]], *hw[s])                        # occlusion_masks(flow[0], flow[1]), :70
-    E.call("cc_flow_noocc_jobs", jb.pack(), len(jb), B, STREAM)
-    warped = _carve([B * 3 * px[s] for s in range(S) for _ in range(R)], tgt_img)
-    jb = _Jobs()
-    for s in range(S):
-        for i in range(R):
-            jb.add([ref_l[i][s], fl[i][s], warped[s * R + i]], *hw[s])
-    E.call("cc_flow_warp_fwd_jobs", jb.pack(), len(jb), B, 3, 0, cfg.ac, STREAM)
-    nblk = [E.call("cc_ssim_num_blocks", B, h, w) for h, w in hw]
-    partials = _carve([4 * nblk[s] for s in range(S) for _ in range(R)], tgt_img)
-    adj = _carve([4 * B * 3 * px[s] for s in range(S) for _ in range(R)], tgt_img) if want_grad else None
-    gm = []
-    for s in range(S):
-        g = arena.view(R + R * S + s) if (m[s] is not None and want_grad) else None
-        if g is None and m[s] is not None and want_grad:
-            g = torch.empty_like(m[s])                 # the mask itself needs no gradient: scratch for the kernel
-        gm.append(g)
-    scales = torch.empty(S * R, device=tgt_img.device, dtype=torch.float32)
-    jb = _Jobs()
-    for s in range(S):
-        MC = 0 if m[s] is None else m[s].shape[1]
-        for i in range(R):
-            jb.add([tgt_l[s], warped[s * R + i], no[s], None if m[s] is None else _off(m[s], i * px[s]),
-                    None if gm[s] is None else _off(gm[s], i * px[s]), None if adj is None else adj[s * R + i],
-                    partials[s * R + i], 1 | (MC << 8) | (MC << 16)], *hw[s])
-    E.call("cc_ssim_photo_fwd_jobs", jb.pack(), len(jb), B, 0, 1 if want_grad else 0, float(cfg.wssim), float(cfg.qch),
-           float(cfg.lambda_oob), loss_acc, scales, nan_flag, gauss13_ptr(), STREAM)
-    if want_grad:
-        gw = _carve([B * 3 * px[s] for s in range(S) for _ in range(R)], tgt_img)
-        jb = _Jobs()
-        for s in range(S):
-            for i in range(R):
-                j = s * R + i
-                jb.add([adj[j], tgt_l[s], warped[j], _off(scales, j), gw[j]], *hw[s])
-        E.call("cc_ssim_photo_bwd_jobs", jb.pack(), len(jb), B, gauss13_ptr(), STREAM)
-        jb = _Jobs()
-        for s in range(S):
-            for i in range(R):
-                gf = arena.view(R + i * S + s)
-                if gf is not None:
-                    jb.add([gw[s * R + i], ref_l[i][s], fl[i][s], gf], *hw[s])
-        if len(jb):
-            E.call("cc_flow_warp_bwd_jobs", jb.pack(), len(jb), B, 3, 0, cfg.ac, STREAM)
-        jb = _Jobs()
-        for s in range(S):
-            if gm[s] is not None:
-                jb.add([None, None, gm[s], _off(scales, s * R)], *hw[s])
-        if len(jb):
-            E.call("cc_sum_refs_scale_jobs", jb.pack(), len(jb), B, R, R, STREAM)      # per-reference normalisers
-    _register_nan_flag(nan_flag)
-    ctx.arena = arena
-    ctx.need = need
-    return loss_acc.reshape(())
-
-
 class _PhotoFlowFn(torch.autograd.Function):
-    """loss_functions.py:27-77 over all scales; flows = [flow list of ref 0, flow list of ref 1]."""
+    """loss_functions.py:27-77 over all scales, every (scale, reference frame) term of a pass in one launch (see _PhotoRigidFn);
+    flows = [flow list of ref 0, flow list of ref 1]."""
 
     @staticmethod
     @_on_forward_stream
@@ -875,48 +780,50 @@ class _PhotoFlowFn(torch.autograd.Function):
         refs = rest[:R]
         flows = [rest[R + i * S:R + (i + 1) * S] for i in range(R)]
         masks = rest[R + R * S:]
-        E = engine()
         need = ctx.needs_input_grad
-        if R * S <= MAX_JOBS and all(mk is None or mk.shape[1] == R for mk in masks):
-            return _photo_flow_jobs(ctx, cfg, tgt_img, refs, flows, masks, need, rest)
+        B = tgt_img.shape[0]
         want_grad = any(need)
+        _check_mask_channels(masks, R)
         loss_acc, nan_flag = _zeros1(tgt_img), _zeros1(tgt_img)
         arena = _GradArena(list(rest), [False] * R + list(need[2 + R:]))      # refs (no gradient), flows, masks
+        fl = [[_f32c(flows[i][s].detach()) for s in range(S)] for i in range(R)]
+        hw = [(fl[0][s].shape[2], fl[0][s].shape[3]) for s in range(S)]
+        px = [h * w for h, w in hw]
         for s in range(S):
-            fl = [_f32c(flows[i][s].detach()) for i in range(R)]
-            B, _, h, w = fl[0].shape
-            HW = h * w
-            assert masks[s] is None or fl[0].size()[2:] == masks[s].size()[2:]
-            tgt_s = pyramid_cache.get(tgt_img, h, w)
-            no = torch.empty(B, 1, h, w, device=tgt_img.device, dtype=torch.float32)
-            E.call("cc_flow_noocc", fl[0], fl[1], no, B, h, w, STREAM)        # occlusion_masks(flow[0], flow[1]), :70
-            m = None if masks[s] is None else _f32c(masks[s].detach())
-            MC = 0 if m is None else m.shape[1]
-            gm = arena.view(R + R * S + s) if (m is not None and want_grad) else None
-            if gm is None and m is not None and want_grad:
-                gm = torch.empty_like(m)                      # the mask itself needs no gradient: scratch for the kernel
-            scales = torch.ones(max(MC, R), device=tgt_s.device, dtype=torch.float32) if MC > R else _empty(R, tgt_s)
+            assert masks[s] is None or fl[0][s].size()[2:] == masks[s].size()[2:]
+        m = [None if masks[s] is None else _f32c(masks[s].detach()) for s in range(S)]
+        tgt_l = [pyramid_cache.get(tgt_img, h, w) for h, w in hw]
+        ref_l = [[pyramid_cache.get(refs[i], h, w) for h, w in hw] for i in range(R)]
+        no = _carve([B * n for n in px], tgt_img)
+        jb = _Jobs()
+        for s in range(S):
+            jb.add([fl[0][s], fl[1][s], no[s]], *hw[s])                        # occlusion_masks(flow[0], flow[1]), :70
+        _launch_jobs("cc_flow_noocc_jobs", jb, (B, STREAM))
+        warped = _carve([B * 3 * px[s] for s in range(S) for _ in range(R)], tgt_img)
+        jb = _Jobs()
+        for s in range(S):
             for i in range(R):
-                ref_s = pyramid_cache.get(refs[i], h, w)
-                warped = torch.empty_like(ref_s)
-                E.call("cc_flow_warp_fwd", ref_s, fl[i], warped, B, 3, h, w, 0, cfg.ac, STREAM)
-                adj, scale = _photo_term(
-                    E, tgt_s, warped, no, HW,
-                    None if m is None else m.view(-1)[i * HW:], MC * HW,
-                    None if gm is None else gm.view(-1)[i * HW:], MC * HW, want_grad, cfg, loss_acc, nan_flag,
-                    scale=scales[i:i + 1])
-                if want_grad:
-                    gw = torch.empty_like(warped)
-                    E.call("cc_ssim_photo_bwd", adj[0], adj[1], adj[2], adj[3], tgt_s, warped, scale, gw, 0, gauss13_ptr(),
-                           B, h, w, STREAM)
+                jb.add([ref_l[i][s], fl[i][s], warped[s * R + i]], *hw[s])
+        _launch_jobs("cc_flow_warp_fwd_jobs", jb, (B, 3, 0, cfg.ac, STREAM), R)
+        gm = []
+        for s in range(S):
+            g = arena.view(R + R * S + s) if (m[s] is not None and want_grad) else None
+            if g is None and m[s] is not None and want_grad:
+                g = torch.empty_like(m[s])                 # the mask itself needs no gradient: scratch for the kernel
+            gm.append(g)
+        scales, gw = _photo_terms_jobs(cfg, B, R, hw, tgt_l, warped, lambda s, i: no[s], 1, m, gm, want_grad, loss_acc, nan_flag)
+        if want_grad:
+            jb = _Jobs()
+            for s in range(S):
+                for i in range(R):
                     gf = arena.view(R + i * S + s)
-                    if gf is None:
-                        gf = torch.empty_like(fl[i])
-                    E.call("cc_flow_warp_bwd", gw, ref_s, fl[i], gf, None, B, 3, h, w, 0, cfg.ac, STREAM)
-            if gm is not None:
-                if MC > R:
-                    gm[:, R:] = 0
-                gm *= scales[:MC].view(1, MC, 1, 1)           # per-reference normalisers, one launch
+                    if gf is not None:
+                        jb.add([gw[s * R + i], ref_l[i][s], fl[i][s], gf], *hw[s])
+            if len(jb):
+                _launch_jobs("cc_flow_warp_bwd_jobs", jb, (B, 3, 0, cfg.ac, STREAM))
+            jb = _mask_grad_rows(_Jobs(), [None] * S, [None] * S, gm, scales, R, hw)      # per-reference normalisers
+            if len(jb):
+                _launch_jobs("cc_sum_refs_scale_jobs", jb, lambda j0, j1: (B, R, jb.rows[j0][3], STREAM))
         _register_nan_flag(nan_flag)
         ctx.arena = arena
         ctx.need = need
@@ -959,28 +866,9 @@ def gaussian_explainability_loss(mask):
     return loss
 
 
-class _PerScaleFn(torch.autograd.Function):
-    """Shared driver: sum over scales of a fused value+gradient kernel on one prediction list."""
-
-    @staticmethod
-    @_on_forward_stream
-    def forward(ctx, launch, *preds):
-        need = ctx.needs_input_grad
-        loss_acc = _zeros1(preds[0])
-        arena = _GradArena(list(preds), list(need[1:]))
-        for s, p in enumerate(preds):
-            launch(s, _f32c(p.detach()), arena.view(s), loss_acc)
-        ctx.arena = arena
-        return loss_acc.reshape(())
-
-    @staticmethod
-    def backward(ctx, gout):
-        return (None,) + tuple(ctx.arena.scaled(gout))
-
-
 class _ScaleJobsFn(torch.autograd.Function):
-    """Sum over scales of a fused value+gradient kernel, ALL scales in one launch + one finalize (job tables).
-    build(preds_detached, grad_views, partial_offsets_fn) -> issues the call; see the users below."""
+    """Shared driver: sum over scales of a fused value+gradient kernel on one prediction list, ALL scales in one launch + one
+    finalize (job tables).  issue(preds_detached, grad_views, loss_acc) issues the call(s); see the users below."""
 
     @staticmethod
     @_on_forward_stream
@@ -1025,7 +913,7 @@ def weighted_total(weights, terms):
 
 
 def _partials_for(shapes, planes_of):
-    """Per-job partial-sum areas laid out back to back: -> (flat buffer allocator, [float offsets])."""
+    """Per-job partial-sum areas laid out back to back: -> ([float offsets], total)."""
     offs, tot = [], 0
     for shp in shapes:
         offs.append(tot)
@@ -1037,44 +925,29 @@ def explainability_loss(mask):
     """loss_functions.py:148-155: sum over scales of BCE(mask, ones)."""
     if type(mask) not in [tuple, list]:
         mask = [mask]
-    E = engine()
-    if len(mask) <= MAX_JOBS and len({(mk.shape[0], mk.shape[1]) for mk in mask}) == 1:
-        def issue(ps, gs, acc):
-            planes = ps[0].shape[0] * ps[0].shape[1]
-            offs, tot = _partials_for([p.shape for p in ps], lambda shp: planes)
-            part = _empty(tot, ps[0])
-            jb = _Jobs()
-            for p, g, o in zip(ps, gs, offs):
-                jb.add([p, g, _off(part, o)], p.shape[2], p.shape[3])
-            E.call("cc_bce_ones_fwd_bwd_jobs", jb.pack(), len(jb), planes, part, acc, 1.0, STREAM)
-        return _ScaleJobsFn.apply(issue, *mask)
 
-    def launch(s, p, g, acc):
-        n = p.numel()
-        E.call("cc_bce_ones_fwd_bwd", p, g, _empty(E.call("cc_elem_num_blocks", n), p), acc, 1.0, n, STREAM)
-    return _PerScaleFn.apply(launch, *mask)
+    def issue(ps, gs, acc):
+        offs, tot = _partials_for([p.shape for p in ps], lambda shp: shp[0] * shp[1])
+        part = _empty(tot, ps[0])
+        jb = _Jobs()
+        for p, g, o in zip(ps, gs, offs):
+            jb.add([p, g, _off(part, o)], p.shape[2], p.shape[3], key=p.shape[0] * p.shape[1])      # planes
+        _launch_jobs("cc_bce_ones_fwd_bwd_jobs", jb, lambda j0, j1: (jb.rows[j0][3], _off(part, offs[j0]), acc, 1.0, STREAM))
+    return _ScaleJobsFn.apply(issue, *mask)
 
 
 def edge_aware_smoothness_loss(img, pred_disp):
     """loss_functions.py:287-319."""
-    E = engine()
-    if len(pred_disp) <= MAX_JOBS and len({(p.shape[0], p.shape[1]) for p in pred_disp}) == 1:
-        def issue(ps, gs, acc):
-            B, C = ps[0].shape[0], ps[0].shape[1]
-            offs, tot = _partials_for([p.shape for p in ps], lambda shp: B * C)
-            part = _empty(tot, ps[0])
-            jb = _Jobs()
-            for p, g, o in zip(ps, gs, offs):
-                jb.add([pyramid_cache.get(img, p.shape[2], p.shape[3]), p, g, _off(part, o)], p.shape[2], p.shape[3])
-            E.call("cc_edge_smooth_fwd_bwd_jobs", jb.pack(), len(jb), B, C, part, acc, 1.0, STREAM)
-        return _ScaleJobsFn.apply(issue, *pred_disp)
-
-    def launch(s, p, g, acc):
-        B, C, h, w = p.shape
-        im = pyramid_cache.get(img, h, w)
-        nb = E.call("cc_elem_num_blocks", h * w) * B * C
-        E.call("cc_edge_smooth_fwd_bwd", im, p, g, _empty(nb, p), acc, 1.0, B, C, h, w, STREAM)
-    return _PerScaleFn.apply(launch, *pred_disp)
+    def issue(ps, gs, acc):
+        offs, tot = _partials_for([p.shape for p in ps], lambda shp: shp[0] * shp[1])
+        part = _empty(tot, ps[0])
+        jb = _Jobs()
+        for p, g, o in zip(ps, gs, offs):
+            jb.add([pyramid_cache.get(img, p.shape[2], p.shape[3]), p, g, _off(part, o)], p.shape[2], p.shape[3],
+                   key=(p.shape[0], p.shape[1]))
+        _launch_jobs("cc_edge_smooth_fwd_bwd_jobs", jb,
+                     lambda j0, j1: jb.rows[j0][3] + (_off(part, offs[j0]), acc, 1.0, STREAM))
+    return _ScaleJobsFn.apply(issue, *pred_disp)
 
 
 def edge_aware_smoothness_sum(img, pred_lists):
@@ -1082,95 +955,65 @@ def edge_aware_smoothness_sum(img, pred_lists):
     flow_bwd, exp_mask) as ONE job table: one launch + one reduction instead of four of each, one gradient-scaling launch in the
     backward pass.  Engine extension (cc_amd.trainer.cc_forward); same per-term arithmetic, the partial sums of all terms are added
     in one fixed order."""
-    flat = [p for preds in pred_lists for p in preds]
-    if len(flat) > MAX_JOBS or len({p.shape[0] for p in flat}) != 1:
-        t = None
-        for preds in pred_lists:
-            v = edge_aware_smoothness_loss(img, preds)
-            t = v if t is None else t + v
-        return t
-    E = engine()
-
     def issue(ps, gs, acc):
-        B = ps[0].shape[0]
         offs, tot = _partials_for([p.shape for p in ps], lambda shp: shp[0] * shp[1])
         part = _empty(tot, ps[0])
         jb = _Jobs()
         ew = pyramid_cache.edge_weights(img, [(p.shape[2], p.shape[3]) for p in ps]) if img.shape[1] == 3 else {}
         for p, g, o in zip(ps, gs, offs):
             hw = (p.shape[2], p.shape[3])
-            jb.add([pyramid_cache.get(img, hw[0], hw[1]), p, g, _off(part, o), p.shape[1], ew.get(hw)], hw[0], hw[1])
-        E.call("cc_edge_smooth_fwd_bwd_jobs", jb.pack(), len(jb), B, 0, part, acc, 1.0, STREAM)
-    return _ScaleJobsFn.apply(issue, *flat)
+            jb.add([pyramid_cache.get(img, hw[0], hw[1]), p, g, _off(part, o), p.shape[1], ew.get(hw)], hw[0], hw[1],
+                   key=p.shape[0])
+        _launch_jobs("cc_edge_smooth_fwd_bwd_jobs", jb,
+                     lambda j0, j1: (jb.rows[j0][3], 0, _off(part, offs[j0]), acc, 1.0, STREAM))
+    return _ScaleJobsFn.apply(issue, *[p for preds in pred_lists for p in preds])
 
 
 def smooth_loss(pred_disp):
-    """loss_functions.py:323-341."""
+    """loss_functions.py:323-341 (one launch per scale: the kernel has no job-table form)."""
     if type(pred_disp) not in [tuple, list]:
         pred_disp = [pred_disp]
     E = engine()
 
-    def launch(s, p, g, acc):
-        B, C, h, w = p.shape
-        nb = E.call("cc_elem_num_blocks", h * w) * B * C
-        E.call("cc_smooth2_fwd_bwd", p, g, _empty(nb, p), acc, 1.0 / (2.3 ** s), 1.0, B * C, h, w, STREAM)
-    return _PerScaleFn.apply(launch, *pred_disp)
+    def issue(ps, gs, acc):
+        for s, (p, g) in enumerate(zip(ps, gs)):
+            B, C, h, w = p.shape
+            nb = E.call("cc_elem_num_blocks", h * w) * B * C
+            E.call("cc_smooth2_fwd_bwd", p, g, _empty(nb, p), acc, 1.0 / (2.3 ** s), 1.0, B * C, h, w, STREAM)
+    return _ScaleJobsFn.apply(issue, *pred_disp)
 
 
 # ----------------------------------------------------------------------------- consensus
 def consensus_exp_masks(cam_flows_fwd, cam_flows_bwd, flows_fwd, flows_bwd, tgt_img, ref_img_fwd, ref_img_bwd, wssim,
                         wrig, ws=0.1, align_corners=None):
     """loss_functions.py:160-202: per-pixel {0,1} consensus target (non-differentiable; `ws` is unused there too)."""
-    E = engine()
     ac = _ac(align_corners)
     out = []
     S = len(cam_flows_fwd)
-    if 3 * S <= MAX_JOBS:
-        # the 3 warps + 3 error maps of every scale (18 of each per step) as one launch each, then all targets in one launch
-        with torch.no_grad():
-            B = tgt_img.shape[0]
-            cf = [_f32c(t) for t in cam_flows_fwd]
-            cb = [_f32c(t) for t in cam_flows_bwd]
-            ff = [_f32c(t) for t in flows_fwd]
-            hw = [(t.shape[2], t.shape[3]) for t in cf]
-            px = [h * w for h, w in hw]
-            tgt_l = [pyramid_cache.get(tgt_img, h, w) for h, w in hw]
-            rf = [pyramid_cache.get(ref_img_fwd, h, w) for h, w in hw]
-            rb = [pyramid_cache.get(ref_img_bwd, h, w) for h, w in hw]
-            warped = _carve([B * 3 * px[s] for s in range(S) for _ in range(3)], tgt_img)
-            ev = _carve([B * px[s] for s in range(S) for _ in range(6)], tgt_img)       # err x3, valid x3 per scale
-            jw, je, jc = _Jobs(), _Jobs(), _Jobs()
-            for s in range(S):
-                for k, (src, flow) in enumerate(((rf[s], cf[s]), (rb[s], cb[s]), (rf[s], ff[s]))):
-                    jw.add([src, flow, warped[3 * s + k]], *hw[s])
-                    je.add([tgt_l[s], warped[3 * s + k], ev[6 * s + k], ev[6 * s + 3 + k]], *hw[s])
-                target = torch.empty(B, 1, hw[s][0], hw[s][1], device=tgt_img.device, dtype=torch.float32)
-                jc.add([ev[6 * s], ev[6 * s + 1], ev[6 * s + 2], ev[6 * s + 3], ev[6 * s + 4], target], *hw[s])
-                out.append(target)
-            E.call("cc_flow_warp_fwd_jobs", jw.pack(), len(jw), B, 3, 0, ac, STREAM)
-            E.call("cc_ssim_err_fwd_jobs", je.pack(), len(je), B, float(wssim), gauss13_ptr(), STREAM)
-            E.call("cc_consensus_target_jobs", jc.pack(), len(jc), B, float(wrig), STREAM)
-        return out
+    # the 3 warps + 3 error maps of every scale (18 of each per step) as one launch each, then all targets in one launch
     with torch.no_grad():
-        for i in range(len(cam_flows_fwd)):
-            cf, cb, ff = _f32c(cam_flows_fwd[i]), _f32c(cam_flows_bwd[i]), _f32c(flows_fwd[i])
-            B, _, h, w = cf.shape
-            tgt_s = pyramid_cache.get(tgt_img, h, w)
-            rf = pyramid_cache.get(ref_img_fwd, h, w)
-            rb = pyramid_cache.get(ref_img_bwd, h, w)
-            errs, valids = [], []
-            for src, flow in ((rf, cf), (rb, cb), (rf, ff)):
-                warped = torch.empty_like(src)
-                E.call("cc_flow_warp_fwd", src, flow, warped, B, 3, h, w, 0, ac, STREAM)
-                err = torch.empty(B, 1, h, w, device=src.device, dtype=torch.float32)
-                valid = torch.empty_like(err)
-                E.call("cc_ssim_err_fwd", tgt_s, warped, err, valid, float(wssim), gauss13_ptr(), B, h, w, STREAM)
-                errs.append(err)
-                valids.append(valid)
-            target = torch.empty_like(errs[0])
-            E.call("cc_consensus_target", errs[0], errs[1], errs[2], valids[0], valids[1], target, float(wrig),
-                   target.numel(), STREAM)
+        B = tgt_img.shape[0]
+        cf = [_f32c(t) for t in cam_flows_fwd]
+        cb = [_f32c(t) for t in cam_flows_bwd]
+        ff = [_f32c(t) for t in flows_fwd]
+        hw = [(t.shape[2], t.shape[3]) for t in cf]
+        px = [h * w for h, w in hw]
+        tgt_l = [pyramid_cache.get(tgt_img, h, w) for h, w in hw]
+        rf = [pyramid_cache.get(ref_img_fwd, h, w) for h, w in hw]
+        rb = [pyramid_cache.get(ref_img_bwd, h, w) for h, w in hw]
+        warped = _carve([B * 3 * px[s] for s in range(S) for _ in range(3)], tgt_img)
+        ev = _carve([B * px[s] for s in range(S) for _ in range(6)], tgt_img)       # err x3, valid x3 per scale
+        jw, je, jc = _Jobs(), _Jobs(), _Jobs()
+        for s in range(S):
+            for k, (src, flow) in enumerate(((rf[s], cf[s]), (rb[s], cb[s]), (rf[s], ff[s]))):
+                jw.add([src, flow, warped[3 * s + k]], *hw[s])
+                je.add([tgt_l[s], warped[3 * s + k], ev[6 * s + k], ev[6 * s + 3 + k]], *hw[s])
+            target = torch.empty(B, 1, hw[s][0], hw[s][1], device=tgt_img.device, dtype=torch.float32)
+            jc.add([ev[6 * s], ev[6 * s + 1], ev[6 * s + 2], ev[6 * s + 3], ev[6 * s + 4], target], *hw[s])
             out.append(target)
+        _launch_jobs("cc_flow_warp_fwd_jobs", jw, (B, 3, 0, ac, STREAM))
+        _launch_jobs("cc_ssim_err_fwd_jobs", je, (B, float(wssim), gauss13_ptr(), STREAM))
+        _launch_jobs("cc_consensus_target_jobs", jc, (B, float(wrig), STREAM))
     return out
 
 
@@ -1194,34 +1037,19 @@ class _ConsensusBCEFn(torch.autograd.Function):
         S = cfg.n_scales
         masks = rest[:S]
         cb, cf, tb, tf = (rest[S * (k + 1):S * (k + 2)] for k in range(4))
-        E = engine()
         need = ctx.needs_input_grad
         loss_acc = _zeros1(masks[0])
         arena = _GradArena(list(masks), list(need[1:1 + S]))
-        if S <= MAX_JOBS:
-            B = masks[0].shape[0]
-            offs, tot = _partials_for([mk.shape for mk in masks], lambda shp: B)
-            part = _empty(tot, masks[0])
-            jb = _Jobs()
-            for s in range(S):
-                e = _f32c(masks[s].detach())
-                assert e.shape[1] == 4
-                jb.add([e, _f32c(cb[s].detach()), _f32c(cf[s].detach()), _f32c(tb[s].detach()), _f32c(tf[s].detach()),
-                        arena.view(s), _off(part, offs[s])], e.shape[2], e.shape[3])
-            E.call("cc_consensus_bce_fwd_bwd_jobs", jb.pack(), len(jb), B, part, loss_acc, float(cfg.THRESH), float(cfg.wbce), 1.0,
-                   STREAM)
-            ctx.arena = arena
-            ctx.n_rest = len(rest)
-            return loss_acc.reshape(())
+        offs, tot = _partials_for([mk.shape for mk in masks], lambda shp: shp[0])
+        part = _empty(tot, masks[0])
+        jb = _Jobs()
         for s in range(S):
             e = _f32c(masks[s].detach())
-            B, C, h, w = e.shape
-            assert C == 4
-            g = arena.view(s)
-            nb = E.call("cc_elem_num_blocks", h * w) * B
-            E.call("cc_consensus_bce_fwd_bwd", e, _f32c(cb[s].detach()), _f32c(cf[s].detach()), _f32c(tb[s].detach()),
-                   _f32c(tf[s].detach()), g, _empty(nb, e), loss_acc, float(cfg.THRESH), float(cfg.wbce), 1.0, B, h, w,
-                   STREAM)
+            assert e.shape[1] == 4
+            jb.add([e, _f32c(cb[s].detach()), _f32c(cf[s].detach()), _f32c(tb[s].detach()), _f32c(tf[s].detach()),
+                    arena.view(s), _off(part, offs[s])], e.shape[2], e.shape[3], key=e.shape[0])
+        _launch_jobs("cc_consensus_bce_fwd_bwd_jobs", jb,
+                     lambda j0, j1: (jb.rows[j0][3], _off(part, offs[j0]), loss_acc, float(cfg.THRESH), float(cfg.wbce), 1.0, STREAM))
         ctx.arena = arena
         ctx.n_rest = len(rest)
         return loss_acc.reshape(())

@@ -130,6 +130,53 @@ def function_level(ac, smooth=0):
     return g
 
 
+def rare_inputs(B=FB, H=FH, W=FW):
+    """Inputs of the loss calls that no training configuration makes (rare_level): the function-level case on low-pass frames; its
+    pose as it is for rotation_mode='quat' (pose[:, 3:] = the last three quaternion coefficients, inverse_warp.py:122-143; the
+    reference asserts 6 columns, inverse_warp.py:265) and a mask list whose entries alternate between 4 and 2 channels."""
+    tgt, refs, K, Kinv = syn.sample(B, H, W, seed=1, smooth=3)
+    pyr = pyramid_inputs(B, H, W)
+    pose = syn.kernel_inputs(B, 8, 8, seed=2)["pose"] * 3.0
+    mixed = [p["mask"] if i % 2 == 0 else p["mask"][:, :2].contiguous() for i, p in enumerate(pyr)]
+    return dict(tgt=tgt, refs=refs, K=K, Kinv=Kinv, pyr=pyr, pose=pose, mixed=mixed)
+
+
+def rare_calls(lf, x, leaf):
+    """(name, loss, {key: differentiable input}) of the three calls, on module `lf` (the reference's loss_functions or its
+    drop-in) with leaf(t) making the differentiable inputs."""
+    depth, mask = [leaf(p["depth"]) for p in x["pyr"]], [leaf(p["mask"]) for p in x["pyr"]]
+    pose = leaf(x["pose"])
+    wrt = {("depth%d" % i): d for i, d in enumerate(depth)}
+    wrt.update({("mask%d" % i): m for i, m in enumerate(mask)})
+    wrt["pose"] = pose
+    yield ("photometric_reconstruction_loss_quat",
+           lf.photometric_reconstruction_loss(x["tgt"], x["refs"], x["K"], x["Kinv"], depth, mask, pose, rotation_mode="quat",
+                                              wssim=0.997, qch=0.5), wrt)
+    ffw, fbw = [leaf(p["flow_fwd"]) for p in x["pyr"]], [leaf(p["flow_bwd"]) for p in x["pyr"]]
+    mask = [leaf(p["mask"]) for p in x["pyr"]]
+    wrt = {("flow_fwd%d" % i): f for i, f in enumerate(ffw)}
+    wrt.update({("flow_bwd%d" % i): f for i, f in enumerate(fbw)})
+    wrt.update({("mask%d" % i): m for i, m in enumerate(mask)})
+    yield ("photometric_flow_loss_wide_masks",
+           lf.photometric_flow_loss(x["tgt"], x["refs"][1:3], [fbw, ffw], mask, wssim=0.997, qch=0.5), wrt)
+    mixed = [leaf(m) for m in x["mixed"]]
+    yield ("explainability_loss_mixed", lf.explainability_loss(mixed), {("mask%d" % i): m for i, m in enumerate(mixed)})
+
+
+def rare_level():
+    """tests/golden/loss_rare.npz: value and gradients of rare_calls from the unmodified reference, as it executes under this torch
+    (align_corners=False)."""
+    ref = ref_import.load(None)
+    g = {}
+    for name, loss, wrt in rare_calls(ref.loss_functions, rare_inputs(), lambda t: t.clone().requires_grad_(True)):
+        g[name] = npy(loss)
+        grads = torch.autograd.grad(loss, list(wrt.values()), allow_unused=True)
+        for k, gr in zip(wrt, grads):
+            if gr is not None:
+                g[name + ".grad." + k] = npy(gr)
+    return g
+
+
 def _coarse(name, tensors, g, limit=4096):
     """store small tensors fully, large ones as (sum, abs-sum, strided sample)."""
     for i, t in enumerate(tensors):
@@ -521,6 +568,10 @@ def main():
         print("wrote headline")
         return
     torch.set_num_threads(1)   # run-to-run bit reproducibility of the fixtures
+    if len(sys.argv) > 1 and sys.argv[1] == "rare":
+        np.savez_compressed(os.path.join(OUT, "loss_rare.npz"), **rare_level())
+        print("wrote loss_rare")
+        return
     if len(sys.argv) > 1 and sys.argv[1] == "validate":
         np.savez_compressed(os.path.join(OUT, "validate.npz"), **validate_level())
         print("wrote validate")

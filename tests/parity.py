@@ -361,13 +361,15 @@ def _flip_pinned(name, a, wrt_keys, grads, g, ac):
     return nflip
 
 
-def check_losses_vs_golden(dev, golden_dir):
+def check_losses_vs_golden(dev, golden_dir, values=None):
     """a12-a17 (+ gradients) against the fixtures the UNMODIFIED reference wrote (oracle/make_golden.py): the
     host-CPU-independent parity gate.  Losses within 1e-4 rel (north star) on white-noise AND low-pass frames;
-    gradients: tight on the low-pass frames, flip-tolerant on white noise (see _grad_ok)."""
+    gradients: tight on the low-pass frames, flip-tolerant on white noise (see _grad_ok).
+    values: a dict that receives {case: (loss, {input: gradient})} of every checked call."""
     import os
     from oracle.make_golden import FB, FH, FW
     res = {}
+    values = {} if values is None else values
     for tag, ac in (("acF", False), ("acT", True)):
         for smooth, suffix in ((0, ""), (3, "_smooth")):
             g = dict(np.load(os.path.join(golden_dir, "functions_%s%s.npz" % (tag, suffix))))
@@ -377,6 +379,7 @@ def check_losses_vs_golden(dev, golden_dir):
                     return
                 assert abs(float(loss) - float(g[name])) <= 1e-4 * abs(float(g[name])), (tag, suffix, name, float(loss), float(g[name]))
                 grads = torch.autograd.grad(loss, list(wrt.values()), allow_unused=True)
+                values[tag + suffix + ":" + name] = (loss.detach().cpu(), {k: gr.detach().cpu() for k, gr in zip(wrt, grads) if gr is not None})
                 worst = 0.0
                 for (k, _), gr in zip(wrt.items(), grads):
                     key = name + ".grad." + k
@@ -436,7 +439,68 @@ def check_losses_vs_golden(dev, golden_dir):
             # THRESH-ed census masks are discontinuous in the rigid flow: compare the loss only loosely on this term's
             # inputs that came through this device's P (rb); exact reference values are used for rf
             l5 = LF.consensus_depth_flow_mask(a["mask"], rb, rf, tgt_ref, tgt_ref, THRESH=0.5, wbce=0.5)
+            values[tag + suffix + ":consensus_depth_flow_mask"] = (l5.detach().cpu(), {})
             assert abs(float(l5) - float(g["consensus_depth_flow_mask"])) <= 1e-3 * abs(float(g["consensus_depth_flow_mask"]))
+    return res
+
+
+def check_losses_chunked(dev, golden_dir):
+    """Job tables longer than a launch holds: check_losses_vs_golden again with loss_functions.MAX_JOBS = 5 -- 5 divides none of
+    the 24, 18 and 12 rows of the step's tables, and the rigid loss runs one level per chunk -- under the same bars against the
+    reference's fixtures.  The photometric losses add their terms one by one in job order (k_photo_finalize_jobs), so they equal
+    their unchunked values bit for bit; the terms summed by k_reduce_add (one reduction per chunk instead of one over all rows)
+    and the pose gradient (one partial gradient per chunk, added in chunk order) are printed against the unchunked values."""
+    full, cut = {}, {}
+    assert LF.MAX_JOBS == 24
+    check_losses_vs_golden(dev, golden_dir, values=full)
+    LF.MAX_JOBS = 5
+    try:
+        res = check_losses_vs_golden(dev, golden_dir, values=cut)
+    finally:
+        LF.MAX_JOBS = 24
+    assert sorted(full) == sorted(cut) and len(full) >= 20
+    for case in sorted(full):
+        (l0, g0), (l1, g1) = full[case], cut[case]
+        if "photometric" in case:
+            assert torch.equal(l0, l1), (case, float(l0), float(l1))
+        else:
+            print("%-50s loss %.9g, chunked %.9g (diff %.2e)" % (case, float(l0), float(l1), abs(float(l0) - float(l1))))
+        for k in g0:
+            if k == "pose":
+                print("%-50s pose gradient: chunked vs whole, rel %.2e" % (case, rel(g1[k], g0[k])))
+    return res
+
+
+def check_losses_rare(dev, golden_dir):
+    """Loss calls no training configuration makes, against tests/golden/loss_rare.npz (the unmodified reference, low-pass frames,
+    align_corners=False; oracle/make_golden.py rare_level): rotation_mode='quat', masks with more channels than reference frames,
+    a mask list of mixed channel counts.  Bars of check_losses_vs_golden: 1e-4 rel on the loss, the tight gradient bar."""
+    import os
+    from oracle.make_golden import rare_calls, rare_inputs
+    g = dict(np.load(os.path.join(golden_dir, "loss_rare.npz")))
+    x = rare_inputs()
+    x = {k: (to(dev, v) if k not in ("pyr", "pose") else v) for k, v in x.items()}
+    res, seen = {}, 0
+    for name, loss, wrt in rare_calls(LF, x, lambda t: leaf(t, dev)):
+        assert abs(float(loss) - float(g[name])) <= 1e-4 * abs(float(g[name])), (name, float(loss), float(g[name]))
+        grads = torch.autograd.grad(loss, list(wrt.values()), allow_unused=True)
+        worst = 0.0
+        for k, gr in zip(wrt, grads):
+            key = name + ".grad." + k
+            if gr is None:
+                assert key not in g, key
+                continue
+            ref = torch.from_numpy(g[key])
+            assert gr.shape == ref.shape, (key, gr.shape, ref.shape)
+            worst = max(worst, rel(gr, ref))
+            assert _grad_ok(gr, ref, True), (name, k, rel(gr, ref))
+            if name == "photometric_flow_loss_wide_masks" and k.startswith("mask"):
+                assert gr.shape[1] == 4 and not bool(gr[:, 2:].ne(0).any()), (name, k)      # channels no term reads: exactly zero
+                assert bool(gr[:, :2].ne(0).any()), (name, k)
+            seen += 1
+        res[name] = (float(loss), worst)
+        print("%-40s loss %.8g (reference %.8g), worst gradient rel %.2e" % (name, float(loss), float(g[name]), worst))
+    assert len(res) == 3 and seen == sum(1 for k in g if ".grad." in k)
     return res
 
 

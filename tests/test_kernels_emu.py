@@ -47,6 +47,14 @@ def test_losses_vs_reference_golden(golden_dir):
     print("measured against the bars:", parity.MEASURED)
 
 
+def test_losses_chunked_job_tables(golden_dir):
+    print(parity.check_losses_chunked("cpu", golden_dir))
+
+
+def test_losses_rare_inputs_vs_reference_golden(golden_dir):
+    parity.check_losses_rare("cpu", golden_dir)
+
+
 def test_convs():
     parity.check_convs("cpu")
 

@@ -56,6 +56,23 @@ def test_full_cc_step_matches_oracle():
         assert abs(float(got2["loss"])) < 1e3
 
 
+def test_loss_phase_engine_calls_match_fixture():
+    """The loss phase of the 2 x 64 x 128 step makes the engine calls recorded in tests/golden/loss_calls.json: same entry points
+    in the same order, same scalar arguments, same job tables (tests/loss_calls.py; the fixture was recorded before the per-term
+    forms of cc_amd/loss_functions.py were removed)."""
+    import json
+    import loss_calls as LC
+    with emulated_engine():
+        losses, grads, calls = LC.loss_phase("cpu")
+    with open(LC.FIXTURE) as f:
+        want = json.load(f)
+    got = json.loads(json.dumps(calls))
+    assert [c[0] for c in got] == [c[0] for c in want]
+    for k, (a, b) in enumerate(zip(got, want)):
+        assert a == b, (k, a, b)
+    assert all(bool(torch.isfinite(v).all()) for v in losses.values()) and sum(g is not None for g in grads) == 25
+
+
 def test_flat_adam_matches_torch_adam():
     torch.manual_seed(0)
     with emulated_engine():
