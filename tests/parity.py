@@ -1340,3 +1340,447 @@ def check_kernel_names(dev, cases):
         out.append((case, answer, recorded))
     ops.packs.reset()
     return out
+
+
+# ------------------------------------------------------------------ rigid geometry against float64, away from the identity pose
+# Every term is computed three times: by the device, by the oracle in fp32 on the host and by the oracle in float64.
+#   e_dev = max|dev - f64| / max|f64|,   e_32 = the same for the fp32 oracle,   bar: e_dev <= 4 * e_32 + 2^-23
+# Both fp32 sides evaluate the same formulas and differ in summation order, fma contraction and sinf / cosf only: hence the
+# margin of 4; 2^-23 is one rounding of the largest element, for the terms where the host's fp32 result happens to be exact.
+# Where sampling DECISIONS enter (the 'zeros' rewrite at |xn| = 1, the border clip, the bilinear tap boundaries) the pixels
+# within RIGID_DELTA px of one in float64 are left out on all sides (their upstream gradient is zero), at most 2 % of a map.
+RIGID_MARGIN = 4.0
+RIGID_FLOOR = 2.0 ** -23
+RIGID_DELTA = 1e-3
+RIGID_MAX_EXCLUDED = 0.02
+
+
+def _e64(x, ref, keep=None):
+    x, ref = x.detach().cpu().double(), ref.detach().cpu().double()
+    assert x.shape == ref.shape, (x.shape, ref.shape)
+    if keep is not None:
+        x, ref = x[keep], ref[keep]
+    return float((x - ref).abs().max() / ref.abs().max())
+
+
+def _leaf_as(t, dt, d="cpu"):
+    """a fresh leaf of t's values in dtype dt on device d (never t itself: .to() of the same dtype returns its argument)"""
+    return t.detach().to(dt).to(d).clone().requires_grad_(True)
+
+
+class _RigidTerms:
+    """The comparisons of one check: every figure is printed and noted first, the bars are asserted together at the end."""
+
+    def __init__(self, check):
+        self.check, self.bad = check, []
+
+    def term(self, name, v_dev, v_32, v_64, keep=None):
+        z = v_64.detach() if keep is None else v_64.detach()[keep]
+        if float(z.abs().max()) == 0:
+            # nothing reaches this term (every coordinate rewritten or clipped): exactly zero on every side, no ratio to take
+            for v in (v_dev, v_32):
+                v = v.detach().cpu()
+                assert float((v if keep is None else v[keep]).abs().max()) == 0, (self.check, name, "not exactly zero")
+            print("%-64s exactly zero on all sides" % (self.check + ":" + name))
+            return
+        e_dev, e_32 = _e64(v_dev, v_64, keep), _e64(v_32, v_64, keep)
+        ratio = e_dev / e_32 if e_32 > 0 else float("inf") if e_dev > 0 else 0.0
+        key = "rigid:%s:%s" % (self.check, name.split(" ")[0])
+        _note(key + ":e_dev", e_dev)
+        _note(key + ":e_32", e_32)
+        ok = e_dev <= RIGID_MARGIN * e_32 + RIGID_FLOOR
+        print("%-64s e_dev %.3e  e_32 %.3e  ratio %6.2f  %s" % (self.check + ":" + name, e_dev, e_32, ratio, "ok" if ok else "OVER THE BAR"))
+        if not ok:
+            self.bad.append((name, e_dev, e_32))
+
+    def done(self):
+        assert not self.bad, (self.check, "e_dev > 4 * e_32 + 2^-23", self.bad)
+
+
+def _rigid_poses(B, R, seed):
+    """[B,R,6] (tx,ty,tz,rx,ry,rz): angles U(-pi, pi) per axis, translations N(0, 1); the first rows are the zero pose and the
+    angle triples (pi/2,0,0), (0,pi/2,0) (cos(ry) ~ 0), (0,0,pi), (-3,1.5,2.5)."""
+    g = torch.Generator().manual_seed(seed)
+    n = B * R
+    pose = torch.cat((torch.randn(n, 3, generator=g), (torch.rand(n, 3, generator=g) * 2 - 1) * np.pi), 1)
+    fixed = torch.tensor([[0, 0, 0], [np.pi / 2, 0, 0], [0, np.pi / 2, 0], [0, 0, np.pi], [-3, 1.5, 2.5]], dtype=torch.float32)
+    pose[:5, 3:] = fixed
+    pose[0, :3] = 0
+    return pose.float().view(B, R, 6).contiguous()
+
+
+def _rigid_K(B, H=24, W=40):
+    """syn.sample's intrinsics, focal lengths and principal point scaled per batch item so that a kernel that reads the K of
+    another batch item shows."""
+    K = syn.sample(B, H, W, seed=1)[2].clone()
+    for b in range(B):
+        K[b, :2] *= 1.0 + 0.125 * b
+    return K.contiguous()
+
+
+def _proj(pose, K, kdiv, dt):
+    """oracle: pose [N,6], K [N,3,3] -> P [N,12] with rows 0, 1 of K divided by kdiv (loss_functions.py:91), in dtype dt"""
+    K = K.to(dt)
+    return G.projection(pose.to(dt), torch.cat((K[:, 0:2] / kdiv, K[:, 2:]), dim=1)).reshape(-1, 12)
+
+
+def _proj_grad(pose, K, kdiv, gP, dt):
+    p = pose.detach().to(dt).requires_grad_(True)
+    return torch.autograd.grad((_proj(p, K, kdiv, dt) * gP.to(dt)).sum(), p)[0]
+
+
+def check_rigid_pose_proj(dev):
+    """cc_pose_proj_fwd, cc_pose_proj_levels and cc_pose_proj_bwd through the C ABI at arbitrary rotations against float64
+    (smooth functions of the pose: nothing is left out)."""
+    import ctypes
+    from cc_amd._lib import engine, STREAM
+    E = engine()
+    T = _RigidTerms("proj")
+    B, R, L = 3, 4, 3
+    N = B * R
+    pose, K = _rigid_poses(B, R, seed=11), _rigid_K(B)
+    pose_d, K_d = pose.to(dev), K.reshape(B, 9).to(dev)
+    pose_flat, K_flat = pose.view(N, 6), K.repeat_interleave(R, 0)                      # sample n = b * R + r
+    K_flat_d = K_flat.reshape(N, 9).contiguous().to(dev)
+    fwd = {}
+    for kdiv in (1.0, 4.0, 32.0):
+        P = torch.full((N, 12), float("nan"), device=dev)
+        E.call("cc_pose_proj_fwd", pose_d.view(N, 6), 6, K_flat_d, P, N, kdiv, STREAM)
+        T.term("fwd kdiv=%g stride=6" % kdiv, P, _proj(pose_flat, K_flat, kdiv, torch.float32), _proj(pose_flat, K_flat, kdiv, torch.float64))
+        fwd[kdiv] = P.cpu()
+        # a pose[:, r] slice read in place: rows 6R floats apart
+        Ps = torch.full((B, R, 12), float("nan"), device=dev)
+        for r in range(R):
+            Pr = torch.empty(B, 12, device=dev)
+            E.call("cc_pose_proj_fwd", pose_d.data_ptr() + 4 * 6 * r, 6 * R, K_d, Pr, B, kdiv, STREAM)
+            Ps[:, r] = Pr
+        T.term("fwd kdiv=%g stride=6R" % kdiv, Ps.view(N, 12), _proj(pose_flat, K_flat, kdiv, torch.float32),
+               _proj(pose_flat, K_flat, kdiv, torch.float64))
+        assert torch.equal(Ps.view(N, 12).cpu(), fwd[kdiv]), "the strided read computes something else than the dense one"
+    # ---- all levels in one launch: [L][R][B][12], three distinct extents, a kdiv per level
+    kd = [4.0, 1.0, float(np.float32(19.2))]
+    kdv = (ctypes.c_float * L)(*kd)
+    P_all = torch.full((L, R, B, 12), float("nan"), device=dev)
+    E.call("cc_pose_proj_levels", pose_d, K_d, P_all, L, R, B, ctypes.addressof(kdv), STREAM)
+    for l in range(L):
+        lrb = lambda dt: _proj(pose_flat, K_flat, kd[l], dt).reshape(B, R, 12).transpose(0, 1)
+        T.term("levels l=%d kdiv=%g" % (l, kd[l]), P_all[l], lrb(torch.float32), lrb(torch.float64))
+    assert torch.equal(P_all[0].cpu(), fwd[4.0].view(B, R, 12).transpose(0, 1)), "cc_pose_proj_levels != cc_pose_proj_fwd at the same kdiv"
+    # ---- the adjoint: accumulate flag, both strides
+    g = torch.Generator().manual_seed(12)
+    gP, pre = torch.randn(N, 12, generator=g), torch.randn(N, 6, generator=g)
+    gP_d = gP.to(dev)
+    for kdiv in (1.0, 4.0, 32.0):
+        g32, g64 = _proj_grad(pose_flat, K_flat, kdiv, gP, torch.float32), _proj_grad(pose_flat, K_flat, kdiv, gP, torch.float64)
+        for width in (6, 8):
+            for acc in (0, 1):
+                buf = torch.full((N, width), -77.0)
+                if acc:
+                    buf[:, :6] = pre
+                buf = buf.to(dev)
+                E.call("cc_pose_proj_bwd", gP_d, pose_d.view(N, 6), 6, K_flat_d, buf, width, N, kdiv, acc, STREAM)
+                T.term("bwd kdiv=%g gpose_stride=%d accumulate=%d" % (kdiv, width, acc), buf[:, :6],
+                       pre + g32 if acc else g32, pre.double() + g64 if acc else g64)
+                assert bool((buf[:, 6:] == -77.0).all()), "cc_pose_proj_bwd wrote into the padding of its gradient rows"
+        # one reference frame of [B,R,6]: pose rows AND gradient rows 6R floats apart, the other frames' rows stay
+        buf = torch.full((B, R, 6), -77.0, device=dev)
+        r = 2
+        E.call("cc_pose_proj_bwd", gP_d.view(B, R, 12)[:, r].contiguous(), pose_d.data_ptr() + 4 * 6 * r, 6 * R, K_d,
+               buf.data_ptr() + 4 * 6 * r, 6 * R, B, kdiv, 0, STREAM)
+        T.term("bwd kdiv=%g strides=6R" % kdiv, buf[:, r], g32.reshape(B, R, 6)[:, r], g64.reshape(B, R, 6)[:, r])
+        rest = [q for q in range(R) if q != r]
+        assert bool((buf[:, rest] == -77.0).all())
+    T.done()
+
+
+def check_rigid_pose_grad_jobs(dev):
+    """cc_pose_grad_jobs on synthetic dL/dP partials [B][nb][12], the table built as _PhotoRigidFn builds it: nb = 72 (the lane loop
+    wraps, and not a whole number of times), 18 and 1; reference: the float64 sum of the partials per (level, r, b) through the
+    float64 adjoint of the projection at that level's kdiv, summed over the levels."""
+    import ctypes
+    from cc_amd._lib import STREAM
+    T = _RigidTerms("grad_jobs")
+    L, R, B = 3, 4, 2
+    hw = [(96, 192), (48, 96), (5, 7)]
+    kd = [1.0, 2.0, float(np.float32(19.2))]
+    nb = [(h * w + 255) // 256 for h, w in hw]
+    assert nb == [72, 18, 1]
+    pose, K = _rigid_poses(B, R, seed=13), _rigid_K(B)
+    g = torch.Generator().manual_seed(14)
+    # (levels scaled so that each one carries a comparable share of the rotation gradient: K rows 0, 1 are divided by kdiv)
+    parts = [torch.randn(B, nb[l], 12, generator=g) * kd[l] for l in range(L) for _ in range(R)]
+    parts_d = [p.to(dev) for p in parts]
+    pose_d, K_d = pose.to(dev), K.reshape(B, 9).to(dev)
+    gpose = torch.full((B, R, 6), float("nan"), device=dev)
+    kdv = (ctypes.c_float * L)(*kd)
+    jp = LF._Jobs()
+    for l in range(L):
+        for r in range(R):
+            jp.add([parts_d[l * R + r]], *hw[l])
+    LF._launch_jobs("cc_pose_grad_jobs", jp, (L, R, B, pose_d, K_d, gpose, ctypes.addressof(kdv), STREAM), R)
+
+    def ref(dt):
+        p = _leaf_as(pose, dt)
+        tot = 0
+        for l in range(L):
+            for r in range(R):
+                tot = tot + (_proj(p[:, r], K, kd[l], dt) * parts[l * R + r].to(dt).sum(1)).sum()
+        return torch.autograd.grad(tot, p)[0]
+    T.term("gpose", gpose, ref(torch.float32), ref(torch.float64))
+    T.done()
+
+
+def _rigid_recipe(name, B, R, H, W, seed):
+    """-> pose [B,R,6], depth [B,H,W].  'moderate': angles U(-0.4, 0.4), translation N(0, 0.3^2), depth U(0.5, 5.5);
+    'behind': angles U(-0.1, 0.1), tz = -2.2 (tx, ty N(0, 0.3^2)), depth in the two bands [0.5, 1.5] and [3.2, 5.2]: about half
+    of the pixels end up behind the camera, none close to the Z clamp."""
+    g = torch.Generator().manual_seed(seed)
+    u = lambda *s: torch.rand(*s, generator=g)
+    tr = torch.randn(B, R, 3, generator=g) * 0.3
+    if name == "moderate":
+        ang = (u(B, R, 3) * 2 - 1) * 0.4
+        depth = u(B, H, W) * 5 + 0.5
+    else:
+        ang = (u(B, R, 3) * 2 - 1) * 0.1
+        tr[:, :, 2] = -2.2
+        depth = torch.where(u(B, H, W) < 0.5, 0.5 + u(B, H, W), 3.2 + 2 * u(B, H, W))
+    return torch.cat((tr, ang), 2).float().contiguous(), depth.float().contiguous()
+
+
+def _rigid_probe(depth, rot, tr, Kinv):
+    """float64: the unclamped Z and the normalised coordinates before any rewrite, [B,H,W] each"""
+    b, h, w = depth.shape
+    cam = G.pixel2cam(depth, Kinv)
+    p = cam.view(b, 3, -1)
+    if rot is not None:
+        p = rot.bmm(p)
+    if tr is not None:
+        p = p + tr
+    grid = G.cam2pixel(cam, rot, tr, None)
+    return p[:, 2].view(b, h, w), grid[..., 0], grid[..., 1]
+
+
+def _rigid_conditions(recipe, Z, xn, yn, full=True):
+    """What the recipes promise, asserted on the float64 reference alone.  full: the recipe's own projection (rotation and
+    translation); the switched-off variants only have to stay clear of the Z clamp."""
+    if recipe == "moderate":
+        assert float((Z - 1e-3).abs().min()) >= 0.1, float((Z - 1e-3).abs().min())
+        if full:
+            inside = float(((xn.abs() <= 1) & (yn.abs() <= 1)).double().mean())
+            assert inside >= 0.20, inside
+    else:
+        assert float(Z.abs().min()) >= 0.2, float(Z.abs().min())
+        if full:
+            behind = float((Z < 1e-3).double().mean())
+            assert 0.30 <= behind <= 0.70, behind
+
+
+def _excluded_share(tag, excl):
+    share = float(excl.double().mean())
+    _note("rigid:excluded_share", share)
+    print("%-64s excluded %.4f" % (tag, share))
+    assert share <= RIGID_MAX_EXCLUDED, (tag, share)
+    return share
+
+
+# seeds at which the recipes meet their conditions (asserted by _rigid_conditions on the float64 reference)
+RIGID_SEEDS = {("coords", "moderate"): 2, ("coords", "behind"): 1, ("chain", "moderate"): 4, ("chain", "behind"): 2}
+
+
+def check_rigid_coords(dev, B=2, H=24, W=40):
+    """IW.pixel2cam / IW.cam2pixel (grid and all gradients) and IW.pose2flow (flow, d/d depth, d/dP) at real rotations and with
+    points behind the camera, P taken from cc_pose_proj_fwd on the device and handed to all three sides."""
+    from cc_amd._lib import engine, STREAM
+    T = _RigidTerms("coords")
+    _, _, K, Kinv = syn.sample(B, H, W, seed=1)
+    for recipe in ("moderate", "behind"):
+        pose, depth = _rigid_recipe(recipe, B, 1, H, W, RIGID_SEEDS["coords", recipe])
+        P_d = torch.empty(B, 12, device=dev)
+        engine().call("cc_pose_proj_fwd", pose[:, 0].contiguous().to(dev), 6, K.reshape(B, 9).to(dev), P_d, B, 1.0, STREAM)
+        P = P_d.cpu().view(B, 3, 4)
+        for mode, use_rot, use_tr in (("zeros", True, True), ("border", True, True), ("zeros", False, True), ("zeros", True, False)):
+            tag = "%s %s%s%s" % (recipe, mode, "" if use_rot else " no-rot", "" if use_tr else " no-tr")
+            Z, xn, yn = _rigid_probe(depth.double(), P[:, :, :3].double() if use_rot else None, P[:, :, 3:].double() if use_tr else None,
+                                     Kinv.double())
+            _rigid_conditions(recipe, Z, xn, yn, full=use_rot and use_tr)
+            excl = torch.zeros_like(Z, dtype=torch.bool)
+            if mode == "zeros":             # the rewrite decision |xn| = 1, |yn| = 1, measured in pixels
+                excl = ((xn.abs() - 1).abs() * (W - 1) / 2 < RIGID_DELTA) | ((yn.abs() - 1).abs() * (H - 1) / 2 < RIGID_DELTA)
+            _excluded_share(tag, excl)
+            keep = ~excl
+            clamped = Z < 1e-3
+            wgt = torch.randn(B, H, W, 2, generator=torch.Generator().manual_seed(9))
+            wgt[excl] = 0
+            sides = {}
+            for side, dt in (("dev", torch.float32), ("o32", torch.float32), ("o64", torch.float64)):
+                d = dev if side == "dev" else "cpu"
+                d_, ki = _leaf_as(depth, dt, d), _leaf_as(Kinv, dt, d)
+                rot = _leaf_as(P[:, :, :3].contiguous(), dt, d) if use_rot else None
+                tr = _leaf_as(P[:, :, 3:].contiguous(), dt, d) if use_tr else None
+                mod = IW if side == "dev" else G
+                cam = mod.pixel2cam(d_, ki)
+                grid = mod.cam2pixel(cam, rot, tr, mode)
+                wrt = {k: t for k, t in (("depth", d_), ("Kinv", ki), ("cam", cam), ("rot", rot), ("tr", tr)) if t is not None}
+                gs = torch.autograd.grad((grid * wgt.to(dt).to(d)).sum() + (cam * cam).sum() * 1e-3, list(wrt.values()))
+                sides[side] = dict(cam=cam.detach(), grid=grid.detach(), **{"g_" + k: v for k, v in zip(wrt, gs)})
+            a, b, c = sides["dev"], sides["o32"], sides["o64"]
+            T.term("cam %s" % tag, a["cam"], b["cam"], c["cam"])
+            for nm, sel in (("front", keep & ~clamped), ("clamped", keep & clamped)):
+                if bool(sel.any()):
+                    T.term("grid[%s] %s" % (nm, tag), a["grid"], b["grid"], c["grid"], keep=sel)
+            for k in a:
+                if k.startswith("g_"):
+                    T.term("%s %s" % (k, tag), a[k], b[k], c[k])
+        # ---- pose2flow: no rewrite, no clip: nothing to leave out; the Z clamp is taken (recipe 'behind') and stays clear of its edge
+        Z, xn, yn = _rigid_probe(depth.double(), P[:, :, :3].double(), P[:, :, 3:].double(), Kinv.double())
+        clamped = Z < 1e-3
+        gf = torch.randn(B, 2, H, W, generator=torch.Generator().manual_seed(6))
+        sides = {}
+        for side, dt in (("dev", torch.float32), ("o32", torch.float32), ("o64", torch.float64)):
+            d = dev if side == "dev" else "cpu"
+            d_ = _leaf_as(depth, dt, d)
+            if side == "dev":
+                P_ = _leaf_as(P.reshape(B, 12), dt, d)
+                f = IW._Pose2FlowFn.apply(d_, P_, Kinv.to(d), 0)
+            else:
+                P_ = _leaf_as(P, dt)
+                f = G.flow_from_projection(d_, P_, Kinv.to(dt))
+            gd, gP = torch.autograd.grad(f, [d_, P_], gf.to(dt).to(d))
+            sides[side] = dict(flow=f.detach(), g_depth=gd, g_P=gP.reshape(B, 12))
+        a, b, c = sides["dev"], sides["o32"], sides["o64"]
+        for nm, sel in (("front", ~clamped), ("clamped", clamped)):
+            if bool(sel.any()):
+                sel2 = sel.unsqueeze(1).expand(B, 2, H, W)
+                T.term("flow[%s] %s" % (nm, recipe), a["flow"], b["flow"], c["flow"], keep=sel2)
+                T.term("flow g_depth[%s] %s" % (nm, recipe), a["g_depth"], b["g_depth"], c["g_depth"], keep=sel)
+        T.term("flow g_P %s" % recipe, a["g_P"], b["g_P"], c["g_P"])
+    T.done()
+
+
+def _pinned_out(Z, xn, yn, H, W, border, ac):
+    """float64 unclamped Z and normalised coordinates [B,H,W] -> the pixels within RIGID_DELTA px of a sampling decision: the 'zeros' rewrite
+    (|xn| = 1) or the border clip (ix = 0, W - 1), and -- for a coordinate that is neither rewritten nor clipped -- a bilinear tap
+    boundary (an integer ix).  ATen's unnormalisation: ix = (xn + 1) / 2 * (W - 1) with align_corners, ((xn + 1) * W - 1) / 2 without."""
+    excl = torch.zeros_like(xn, dtype=torch.bool)
+    alive = torch.zeros_like(excl)
+    for cn, n in ((xn, W), (yn, H)):
+        unnorm = (lambda v: (v + 1) / 2 * (n - 1)) if ac else (lambda v: ((v + 1) * n - 1) / 2)
+        pix = unnorm(cn)
+        if border:
+            lo, hi = 0.0, float(n - 1)
+            live = (pix > lo) & (pix < hi)
+        else:
+            lo, hi = float(unnorm(-1.0)), float(unnorm(1.0))
+            live = cn.abs() <= 1
+        excl |= ((pix - lo).abs() < RIGID_DELTA) | ((pix - hi).abs() < RIGID_DELTA)
+        excl |= live & ((pix - pix.round()).abs() < RIGID_DELTA)
+        alive |= live
+    # a point behind the camera (Z clamped to 1e-3) whose coordinate nevertheless stays inside the image: X / 1e-3 carries the
+    # rounding of X (~1e-6) as ~1e-3 px, the size of RIGID_DELTA itself, so its taps cannot be pinned at that distance.  A handful
+    # of pixels per map (they count towards the 2 % cap); the clamp itself is held by check_rigid_coords on every such pixel.
+    # Consequence: the pinned chain never takes the clamp branch of rigid_backward on a live tap; the warp backward's clamp is covered
+    # only through pose2flow (check_rigid_coords: flow g_depth[clamped], flow g_P), which shares rigid_backward with the warps.
+    return excl | ((Z < 1e-3) & alive)
+
+
+def check_rigid_chain(dev, B=2, R=2, C=3):
+    """The product's pose-gradient chain cc_pose_proj_levels -> cc_inverse_warp_fwd_jobs -> cc_inverse_warp_bwd_jobs ->
+    cc_pose_grad_jobs, called as _PhotoRigidFn calls them (two levels, kdiv 1 and 2), and the single-problem IW.inverse_warp,
+    against float64 projection -> pixel2cam -> cam2pixel -> grid_sample under autograd, the sampling decisions pinned."""
+    import ctypes
+    from cc_amd._lib import engine, STREAM
+    E = engine()
+    T = _RigidTerms("chain")
+    hw, kd = [(24, 40), (12, 20)], [1.0, 2.0]
+    S = len(hw)
+    px = [h * w for h, w in hw]
+    nb = [(n + 255) // 256 for n in px]
+    _, refs, K, Kinv = syn.sample(B, *hw[0], seed=1, smooth=3)
+    img = [[refs[r], torch.nn.functional.avg_pool2d(refs[r], 2).contiguous()] for r in range(R)]       # [r][s]
+    K_s = lambda s, dt: torch.cat((K.to(dt)[:, 0:2] / kd[s], K.to(dt)[:, 2:]), dim=1)
+    Kinv_s = lambda s, dt: torch.cat((Kinv.to(dt)[:, :, 0:2] * kd[s], Kinv.to(dt)[:, :, 2:]), dim=2)
+    K_d, Kinv_d = K.reshape(B, 9).to(dev), Kinv.to(dev).contiguous()
+    Kinv_all = LF._kinv_levels(Kinv_d, kd)
+    img_d = [[im.to(dev) for im in per_r] for per_r in img]
+    kdv = (ctypes.c_float * S)(*kd)
+    for recipe in ("moderate", "behind"):
+        pose, d0 = _rigid_recipe(recipe, B, R, *hw[0], RIGID_SEEDS["chain", recipe])
+        depth = [d0, d0[:, ::2, ::2].contiguous()]
+        pose_d, depth_d = pose.to(dev), [d.to(dev) for d in depth]
+        P_all = torch.empty(S, R, B, 12, device=dev)
+        E.call("cc_pose_proj_levels", pose_d, K_d, P_all, S, R, B, ctypes.addressof(kdv), STREAM)
+        probe = {}
+        for s in range(S):
+            for r in range(R):
+                P64 = G.projection(pose[:, r].double(), K_s(s, torch.float64))
+                probe[s, r] = _rigid_probe(depth[s].double(), P64[:, :, :3], P64[:, :, 3:], Kinv_s(s, torch.float64))
+                _rigid_conditions(recipe, *probe[s, r])
+        for ac in (False, True):
+            for pad in ("zeros", "border"):
+                border = 1 if pad == "border" else 0
+                tag = "%s %s ac=%d" % (recipe, pad, ac)
+                go, keep = [], []
+                g = torch.Generator().manual_seed(5)
+                for s in range(S):
+                    for r in range(R):
+                        excl = _pinned_out(*probe[s, r], *hw[s], border, ac)
+                        _excluded_share("%s level %d ref %d" % (tag, s, r), excl)
+                        k3 = (~excl).unsqueeze(1).expand(B, C, *hw[s])
+                        keep.append(k3)
+                        go.append(torch.randn(B, C, *hw[s], generator=g) * k3)
+                go_d = [x.to(dev) for x in go]
+                # ---- the device: the four launches of _PhotoRigidFn
+                warped = [torch.full((B, C) + hw[s], float("nan"), device=dev) for s in range(S) for _ in range(R)]
+                jb = LF._Jobs()
+                for s in range(S):
+                    for r in range(R):
+                        jb.add([img_d[r][s], depth_d[s], P_all[s][r], Kinv_all[s], warped[s * R + r]], *hw[s])
+                LF._launch_jobs("cc_inverse_warp_fwd_jobs", jb, (B, C, border, int(ac), STREAM), R)
+                gd_all = [torch.full((R, B) + hw[s], float("nan"), device=dev) for s in range(S)]
+                gpp = [torch.full((B, nb[s], 12), float("nan"), device=dev) for s in range(S) for _ in range(R)]
+                jb, jp = LF._Jobs(), LF._Jobs()
+                for s in range(S):
+                    for r in range(R):
+                        j = s * R + r
+                        jb.add([go_d[j], img_d[r][s], depth_d[s], P_all[s][r], Kinv_all[s], LF._off(gd_all[s], r * B * px[s]), gpp[j]],
+                               *hw[s])
+                        jp.add([gpp[j]], *hw[s])
+                LF._launch_jobs("cc_inverse_warp_bwd_jobs", jb, (B, C, border, int(ac), STREAM), R)
+                gpose = torch.full((B, R, 6), float("nan"), device=dev)
+                LF._launch_jobs("cc_pose_grad_jobs", jp, (S, R, B, pose_d, K_d, gpose, ctypes.addressof(kdv), STREAM), R)
+                # ---- the single-problem entry on (level 0, reference frame 0): also the image gradient
+                im1, d1, p1 = leaf(img[0][0], dev), leaf(depth[0], dev), leaf(pose[:, 0], dev)
+                o1 = IW.inverse_warp(im1, d1, p1, K.to(dev), Kinv_d, padding_mode=pad, align_corners=ac)
+                g1 = torch.autograd.grad(o1, [im1, d1, p1], go_d[0])
+
+                # ---- the oracle, fp32 and float64
+                def oracle(dt):
+                    p, im0 = _leaf_as(pose, dt), _leaf_as(img[0][0], dt)
+                    outs, dl, tot = [], [], 0
+                    for s in range(S):
+                        for r in range(R):
+                            dl.append(_leaf_as(depth[s], dt))
+                            im = im0 if (s, r) == (0, 0) else img[r][s].to(dt)
+                            o = G.inverse_warp(im, dl[-1], p[:, r], K_s(s, dt), Kinv_s(s, dt), padding_mode=pad, align_corners=ac)
+                            outs.append(o.detach())
+                            tot = tot + (o * go[s * R + r].to(dt)).sum()
+                    gr = torch.autograd.grad(tot, [p, im0] + dl)
+                    return outs, gr[0], gr[1], gr[2:]
+                (w32, gp32, gi32, gd32), (w64, gp64, gi64, gd64) = oracle(torch.float32), oracle(torch.float64)
+                for s in range(S):
+                    for r in range(R):
+                        j = s * R + r
+                        T.term("warped %s level %d ref %d" % (tag, s, r), warped[j], w32[j], w64[j], keep=keep[j])
+                        T.term("gdepth %s level %d ref %d" % (tag, s, r), gd_all[s][r], gd32[j], gd64[j])
+                T.term("gpose %s" % tag, gpose, gp32, gp64)
+                # the single problem differentiates level 0, frame 0 alone: its own oracle gradients
+                T.term("single:warped %s" % tag, o1, w32[0], w64[0], keep=keep[0])
+                T.term("single:gdepth %s" % tag, g1[1], gd32[0], gd64[0])
+                T.term("single:gimg %s" % tag, g1[0], gi32, gi64)
+                sp = []
+                for dt in (torch.float32, torch.float64):
+                    p = _leaf_as(pose[:, 0], dt)
+                    o = G.inverse_warp(img[0][0].to(dt), depth[0].to(dt), p, K.to(dt), Kinv.to(dt), padding_mode=pad, align_corners=ac)
+                    sp.append(torch.autograd.grad((o * go[0].to(dt)).sum(), p)[0])
+                T.term("single:gpose %s" % tag, g1[2], sp[0], sp[1])
+    T.done()

@@ -240,6 +240,23 @@ def test_pixel2cam_cam2pixel_gradients():
     parity.check_pixel2cam_cam2pixel_grads("cpu")
 
 
+# the rigid-geometry kernels against the oracle in float64, away from the identity pose (bars: parity.RIGID_*)
+def test_rigid_pose_projection_float64():
+    parity.check_rigid_pose_proj("cpu")
+
+
+def test_rigid_pose_grad_jobs_float64():
+    parity.check_rigid_pose_grad_jobs("cpu")
+
+
+def test_rigid_coordinates_float64():
+    parity.check_rigid_coords("cpu")
+
+
+def test_rigid_chain_float64_pinned():
+    parity.check_rigid_chain("cpu")
+
+
 def test_bias_gradient_table():
     parity.check_bias_grad_table("cpu")
 

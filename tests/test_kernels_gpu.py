@@ -239,6 +239,23 @@ def test_pixel2cam_cam2pixel_gradients():
     parity.check_pixel2cam_cam2pixel_grads("cuda", B=2, H=128, W=416)
 
 
+# the rigid-geometry kernels against the oracle in float64, away from the identity pose (bars: parity.RIGID_*)
+def test_rigid_pose_projection_float64():
+    parity.check_rigid_pose_proj("cuda")
+
+
+def test_rigid_pose_grad_jobs_float64():
+    parity.check_rigid_pose_grad_jobs("cuda")
+
+
+def test_rigid_coordinates_float64():
+    parity.check_rigid_coords("cuda")
+
+
+def test_rigid_chain_float64_pinned():
+    parity.check_rigid_chain("cuda")
+
+
 def test_bias_gradient_table():
     parity.check_bias_grad_table("cuda")
     parity.check_bias_grad_table("cuda", cases=((4, 64, 64, 208, 0), (4, 16, 256, 832, 1), (4, 512, 2, 7, 0), (4, 32, 128, 416, 33)) * 9)
