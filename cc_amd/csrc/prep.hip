@@ -3,15 +3,21 @@
 // datasets/sequence_folders.py:27-28 produces) -> normalised fp32 NCHW in ONE pass over the batch:
 //     dst[n, c, y, x] = ((float)src[n, y + oy_n, xs, c] / 255 - mean_c) / std_c,   xs = flip_n ? W - 1 - (x + ox_n) : x + ox_n
 // (the reference's arithmetic order: `.float() / 255`, then `t.sub_(m).div_(s)`; custom_transforms.py:21-30,47-57).
+//
+// Where the frames come from: every frame kernel takes an index table -- frame n of the launch is frame `idx[n]` of `src`
+// (idx == nullptr: frame n, the dense batches of the cc_frames_* entries; a table: the resident uint8 frame store of
+// cc_amd/datasets, cc_store_*) -- and the resampling kernels a source mode STRETCH: the taps go through `bytescale` with the
+// frame's (min, max) row of `minmax` (float32 frames, and stored uint8 frames that stand for the float32 arrays the reference's
+// loader decodes) or are taken as they are (uint8 frames).  Frame offsets are 64-bit: a store holds more than 4 GiB.
 #include "cc_common.h"
 #include "../../include/ccengine.h"
 
 namespace {
 
 template <typename T>
-__global__ __launch_bounds__(256) void k_frames_to_tensor(const T* __restrict__ src, float* __restrict__ dst,
-                                                          const int* __restrict__ geo, int H, int W, int h, int w, float m0,
-                                                          float m1, float m2, float s0, float s1, float s2) {
+__global__ __launch_bounds__(256) void k_frames_to_tensor(const T* __restrict__ src, const int* __restrict__ idx,
+                                                          float* __restrict__ dst, const int* __restrict__ geo, int H, int W, int h,
+                                                          int w, float m0, float m1, float m2, float s0, float s1, float s2) {
     const int n = blockIdx.y;
     const int p = blockIdx.x * 256 + threadIdx.x;
     if (p >= h * w) return;
@@ -19,7 +25,8 @@ __global__ __launch_bounds__(256) void k_frames_to_tensor(const T* __restrict__ 
     const int flip = geo[3 * n], oy = geo[3 * n + 1], ox = geo[3 * n + 2];
     const int ys = y + oy, xc = x + ox;
     const int xs = flip ? (W - 1 - xc) : xc;
-    const T* s = src + (((size_t)n * H + ys) * W + xs) * 3;
+    const int f = idx ? idx[n] : n;
+    const T* s = src + (((size_t)f * H + ys) * W + xs) * 3;
     float* d = dst + (size_t)n * 3 * h * w + p;
     const float mean[3] = {m0, m1, m2}, stdv[3] = {s0, s1, s2};
 #pragma unroll
@@ -88,10 +95,11 @@ __device__ __forceinline__ int bytescale(float v, float cmin, float scale) {
     return (int)b;
 }
 
-template <typename T>
-__global__ __launch_bounds__(256) void k_frames_resize_h(const T* __restrict__ src, const float* __restrict__ minmax,
-                                                         unsigned char* __restrict__ tmp, const int* __restrict__ geo,
-                                                         const int* __restrict__ tab, int H, int W, int tmp_w, int KT) {
+template <typename T, bool STRETCH>
+__global__ __launch_bounds__(256) void k_frames_resize_h(const T* __restrict__ src, const int* __restrict__ idx,
+                                                         const float* __restrict__ minmax, unsigned char* __restrict__ tmp,
+                                                         const int* __restrict__ geo, const int* __restrict__ tab, int H, int W,
+                                                         int tmp_w, int KT) {
     const int n = blockIdx.z, y = blockIdx.y;
     const int xo = blockIdx.x * 256 + threadIdx.x;
     const int* g = geo + GEO * n;
@@ -100,14 +108,15 @@ __global__ __launch_bounds__(256) void k_frames_resize_h(const T* __restrict__ s
     const int* xmin = tab + g[5];
     const int* kk = xmin + sw + (size_t)xo * KT;
     const int x0 = xmin[xo];
+    const int f = idx ? idx[n] : n;
     float cmin = 0.f, scale = 1.f;
-    if constexpr (sizeof(T) == 4) {
-        cmin = minmax[2 * n];
-        float cs = minmax[2 * n + 1] - cmin;
+    if constexpr (STRETCH) {
+        cmin = minmax[2 * (size_t)f];
+        float cs = minmax[2 * (size_t)f + 1] - cmin;
         if (cs == 0.f) cs = 1.f;
         scale = 255.0f / cs;
     }
-    const T* row = src + ((size_t)n * H + y) * W * 3;
+    const T* row = src + ((size_t)f * H + y) * W * 3;
     int acc[3] = {1 << (PREC - 1), 1 << (PREC - 1), 1 << (PREC - 1)};
     for (int i = 0; i < KT; i++) {
         const int k = kk[i];
@@ -118,7 +127,7 @@ __global__ __launch_bounds__(256) void k_frames_resize_h(const T* __restrict__ s
 #pragma unroll
         for (int c = 0; c < 3; c++) {
             int v;
-            if constexpr (sizeof(T) == 4) v = bytescale((float)px[c], cmin, scale);
+            if constexpr (STRETCH) v = bytescale((float)px[c], cmin, scale);
             else v = (int)px[c];
             acc[c] += k * v;
         }
@@ -163,25 +172,27 @@ __global__ __launch_bounds__(256) void k_frames_resize_v(const unsigned char* __
 // [0, W) x [0, H) -> 0; else shift by -0.5, floor, blend the clamped 2x2 neighbourhood as a + (b - a) * d (the lower row
 // replaced by the upper one beyond the last row), truncate to uint8.  rot per frame: (apply, a0 .. a5, -) doubles; apply == 0:
 // the frame is only byte-scaled (what the resize that follows would do first).  Output: uint8 [N,H,W,3].
-template <typename T>
-__global__ __launch_bounds__(256) void k_frames_rotate(const T* __restrict__ src, const float* __restrict__ minmax,
-                                                       unsigned char* __restrict__ dst, const double* __restrict__ rot, int H, int W) {
+template <typename T, bool STRETCH>
+__global__ __launch_bounds__(256) void k_frames_rotate(const T* __restrict__ src, const int* __restrict__ idx,
+                                                       const float* __restrict__ minmax, unsigned char* __restrict__ dst,
+                                                       const double* __restrict__ rot, int H, int W) {
     const int n = blockIdx.y;
     const int p = blockIdx.x * 256 + threadIdx.x;
     if (p >= H * W) return;
     const int y = p / W, x = p - y * W;
+    const int f = idx ? idx[n] : n;
     float cmin = 0.f, scale = 1.f;
-    if constexpr (sizeof(T) == 4) {
-        cmin = minmax[2 * n];
-        float cs = minmax[2 * n + 1] - cmin;
+    if constexpr (STRETCH) {
+        cmin = minmax[2 * (size_t)f];
+        float cs = minmax[2 * (size_t)f + 1] - cmin;
         if (cs == 0.f) cs = 1.f;
         scale = 255.0f / cs;
     }
-    const T* img = src + (size_t)n * H * W * 3;
+    const T* img = src + (size_t)f * H * W * 3;
     unsigned char* d = dst + ((size_t)n * H * W + p) * 3;
     auto tap = [&](int yy, int xx, int c) -> double {
         const T v = img[((size_t)yy * W + xx) * 3 + c];
-        if constexpr (sizeof(T) == 4) return (double)bytescale((float)v, cmin, scale);
+        if constexpr (STRETCH) return (double)bytescale((float)v, cmin, scale);
         else return (double)v;
     };
     const double* r = rot + 8 * n;
@@ -218,6 +229,135 @@ __global__ __launch_bounds__(256) void k_frames_rotate(const T* __restrict__ src
     }
 }
 
+// ---- the resident frame store (cc_amd/datasets FrameStore): the (min, max) row of every stored uint8 frame, computed once when the
+// store is built -- a stored frame never changes, so the per-step reduction of the float32 path has nothing left to do.  One
+// workgroup per frame; 16 bytes per lane and load where the frames are 16-byte aligned.  Exact: uint8 -> float32.
+__global__ __launch_bounds__(256) void k_store_minmax(const unsigned char* __restrict__ frames, float* __restrict__ minmax,
+                                                      long per_frame, int vec16) {
+    const size_t f = blockIdx.x;
+    const unsigned char* s = frames + f * (size_t)per_frame;
+    unsigned lo = 255u, hi = 0u;
+    long done = 0;
+    if (vec16) {
+        typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+        const long nv = per_frame / 16;
+        const u32x4* v = (const u32x4*)s;
+        for (long i = threadIdx.x; i < nv; i += 256) {
+            const u32x4 q = v[i];
+            const unsigned wds[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+#pragma unroll
+                for (int b = 0; b < 32; b += 8) {
+                    const unsigned e = (wds[k] >> b) & 255u;
+                    lo = e < lo ? e : lo;
+                    hi = e > hi ? e : hi;
+                }
+            }
+        }
+        done = nv * 16;
+    }
+    for (long i = done + threadIdx.x; i < per_frame; i += 256) {
+        const unsigned e = s[i];
+        lo = e < lo ? e : lo;
+        hi = e > hi ? e : hi;
+    }
+    __shared__ unsigned slo[256], shi[256];
+    slo[threadIdx.x] = lo;
+    shi[threadIdx.x] = hi;
+    __syncthreads();
+    for (int st = 128; st > 0; st >>= 1) {
+        if ((int)threadIdx.x < st) {
+            const unsigned a = slo[threadIdx.x + st], b = shi[threadIdx.x + st];
+            if (a < slo[threadIdx.x]) slo[threadIdx.x] = a;
+            if (b > shi[threadIdx.x]) shi[threadIdx.x] = b;
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        minmax[2 * f] = (float)slo[0];
+        minmax[2 * f + 1] = (float)shi[0];
+    }
+}
+
+// ---- NormalizeLocally (custom_transforms.py:33-44; train.py:168-169 --data-normalization local): per sample and channel the mean and the
+// unbiased standard deviation over the sample's nf frames (already / 255), then (x - m) / s in place.  Sums in fp64 in two launches
+// like k_frames_minmax_*: LNB partial (sum, sum of squares) pairs per (sample, channel), then one workgroup per pair folds them and
+// leaves (m, 1 / s); the apply pass rounds once, from double.  Element (b, i, c, p) of x lies at b * sstride + i * fstride + c * hw + p.
+constexpr int LNB = 64;
+
+__global__ __launch_bounds__(256) void k_local_norm_partial(const float* __restrict__ x, double* __restrict__ ws, int nf, long hw,
+                                                            long sstride, long fstride) {
+    const int bc = blockIdx.y, b = bc / 3, c = bc - 3 * b;
+    const float* base = x + (size_t)b * sstride + (size_t)c * hw;
+    const long total = (long)nf * hw;
+    double s1 = 0.0, s2 = 0.0;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)LNB * 256) {
+        const long fr = i / hw, p = i - fr * hw;
+        const double v = (double)base[(size_t)fr * fstride + p];
+        s1 += v;
+        s2 += v * v;
+    }
+    __shared__ double a1[256], a2[256];
+    a1[threadIdx.x] = s1;
+    a2[threadIdx.x] = s2;
+    __syncthreads();
+    for (int st = 128; st > 0; st >>= 1) {
+        if ((int)threadIdx.x < st) {
+            a1[threadIdx.x] += a1[threadIdx.x + st];
+            a2[threadIdx.x] += a2[threadIdx.x + st];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        ws[((size_t)bc * LNB + blockIdx.x) * 2] = a1[0];
+        ws[((size_t)bc * LNB + blockIdx.x) * 2 + 1] = a2[0];
+    }
+}
+
+__global__ __launch_bounds__(LNB) void k_local_norm_final(const double* __restrict__ ws, double* __restrict__ stat, double count) {
+    const int bc = blockIdx.x;
+    __shared__ double a1[LNB], a2[LNB];
+    a1[threadIdx.x] = ws[((size_t)bc * LNB + threadIdx.x) * 2];
+    a2[threadIdx.x] = ws[((size_t)bc * LNB + threadIdx.x) * 2 + 1];
+    __syncthreads();
+    for (int st = LNB / 2; st > 0; st >>= 1) {
+        if ((int)threadIdx.x < st) {
+            a1[threadIdx.x] += a1[threadIdx.x + st];
+            a2[threadIdx.x] += a2[threadIdx.x + st];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        const double m = a1[0] / count;
+        double var = (a2[0] - a1[0] * m) / (count - 1.0);          // unbiased (torch.std's default), as the reference takes it
+        if (var < 0.0) var = 0.0;
+        stat[2 * bc] = m;
+        stat[2 * bc + 1] = 1.0 / sqrt(var);                         // a constant sample: inf, and (x - m) * inf = NaN like the reference's 0 / 0
+    }
+}
+
+__global__ __launch_bounds__(256) void k_local_norm_apply(float* __restrict__ x, const double* __restrict__ stat, int nf, long hw,
+                                                          long sstride, long fstride) {
+    const int bc = blockIdx.y, b = bc / 3, c = bc - 3 * b;
+    float* base = x + (size_t)b * sstride + (size_t)c * hw;
+    const long total = (long)nf * hw;
+    const double m = stat[2 * bc], rs = stat[2 * bc + 1];
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+        const long fr = i / hw, p = i - fr * hw;
+        float* e = base + (size_t)fr * fstride + p;
+        *e = (float)(((double)*e - m) * rs);
+    }
+}
+
+// every id of a launch's index table lies inside the store (checked on the host copy of the table: a bad id would read outside it)
+bool ids_in_range(const int* idx_host, int N, int F) {
+    if (!idx_host || F <= 0) return false;
+    for (int n = 0; n < N; n++)
+        if (idx_host[n] < 0 || idx_host[n] >= F) return false;
+    return true;
+}
+
 }  // namespace
 
 extern "C" {
@@ -230,10 +370,10 @@ int cc_frames_to_tensor(const void* src, int src_is_u8, float* dst, const int* g
     dim3 g((unsigned)((h * w + 255) / 256), (unsigned)N);
     if (src_is_u8)
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_frames_to_tensor<unsigned char>), g, dim3(256), 0, (hipStream_t)stream,
-                           (const unsigned char*)src, dst, geo, H, W, h, w, mean0, mean1, mean2, std0, std1, std2);
+                           (const unsigned char*)src, (const int*)nullptr, dst, geo, H, W, h, w, mean0, mean1, mean2, std0, std1, std2);
     else
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_frames_to_tensor<float>), g, dim3(256), 0, (hipStream_t)stream, (const float*)src, dst,
-                           geo, H, W, h, w, mean0, mean1, mean2, std0, std1, std2);
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_frames_to_tensor<float>), g, dim3(256), 0, (hipStream_t)stream, (const float*)src,
+                           (const int*)nullptr, dst, geo, H, W, h, w, mean0, mean1, mean2, std0, std1, std2);
     CC_CHECK_LAUNCH();
     return CC_OK;
 }
@@ -258,11 +398,11 @@ int cc_frames_resize_to_tensor(const void* src, int src_is_u8, float* dst, const
     if (!src_is_u8) {
         hipLaunchKernelGGL(k_frames_minmax_partial, dim3(MMB, (unsigned)N), dim3(256), 0, s, (const float*)src, mmws, (long)H * W * 3);
         hipLaunchKernelGGL(k_frames_minmax_final, dim3((unsigned)N), dim3(MMB), 0, s, (const float*)mmws, minmax);
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_frames_resize_h<float>), gh, dim3(256), 0, s, (const float*)src, (const float*)minmax, tmp,
-                           geo, tab, H, W, tmp_w, KT);
-    } else {
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_frames_resize_h<unsigned char>), gh, dim3(256), 0, s, (const unsigned char*)src,
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_frames_resize_h<float, true>), gh, dim3(256), 0, s, (const float*)src, (const int*)nullptr,
                            (const float*)minmax, tmp, geo, tab, H, W, tmp_w, KT);
+    } else {
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_frames_resize_h<unsigned char, false>), gh, dim3(256), 0, s, (const unsigned char*)src,
+                           (const int*)nullptr, (const float*)minmax, tmp, geo, tab, H, W, tmp_w, KT);
     }
     hipLaunchKernelGGL(k_frames_resize_v, dim3((unsigned)((h * w + 255) / 256), (unsigned)N), dim3(256), 0, s,
                        (const unsigned char*)tmp, dst, geo, tab, H, tmp_w, KT, h, w, mean0, mean1, mean2, std0, std1, std2);
@@ -284,12 +424,93 @@ int cc_frames_rotate(const void* src, int src_is_u8, void* dst_u8, const double*
     if (!src_is_u8) {
         hipLaunchKernelGGL(k_frames_minmax_partial, dim3(MMB, (unsigned)N), dim3(256), 0, s, (const float*)src, mmws, (long)H * W * 3);
         hipLaunchKernelGGL(k_frames_minmax_final, dim3((unsigned)N), dim3(MMB), 0, s, (const float*)mmws, minmax);
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_frames_rotate<float>), g, dim3(256), 0, s, (const float*)src, (const float*)minmax,
-                           (unsigned char*)dst_u8, rot, H, W);
-    } else {
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_frames_rotate<unsigned char>), g, dim3(256), 0, s, (const unsigned char*)src,
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_frames_rotate<float, true>), g, dim3(256), 0, s, (const float*)src, (const int*)nullptr,
                            (const float*)minmax, (unsigned char*)dst_u8, rot, H, W);
+    } else {
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_frames_rotate<unsigned char, false>), g, dim3(256), 0, s, (const unsigned char*)src,
+                           (const int*)nullptr, (const float*)minmax, (unsigned char*)dst_u8, rot, H, W);
     }
+    CC_CHECK_LAUNCH();
+    return CC_OK;
+}
+
+/* ---- the resident frame store.  frames: uint8 [F,H,W,3] on the device; minmax: fp32 [F,2]. */
+int cc_store_minmax(const void* frames, float* minmax, int F, long per_frame, void* stream) {
+    if (!frames || !minmax || F <= 0 || per_frame <= 0) return CC_ERR_ARG;
+    const int vec16 = (per_frame % 16 == 0) && ((uintptr_t)frames % 16 == 0);
+    hipLaunchKernelGGL(k_store_minmax, dim3((unsigned)F), dim3(256), 0, (hipStream_t)stream, (const unsigned char*)frames, minmax,
+                       per_frame, vec16);
+    CC_CHECK_LAUNCH();
+    return CC_OK;
+}
+
+/* The store-indexed forms of the three entries above: frame n of the launch is frame idx[n] of the store.  idx_host / idx_dev: the
+ * same int32 [N] table in host and in device memory -- the host copy is range-checked here, the kernels read the device copy. */
+int cc_store_to_tensor(const void* frames, int F, const int* idx_host, const int* idx_dev, float* dst, const int* geo, int N, int H,
+                       int W, int h, int w, float mean0, float mean1, float mean2, float std0, float std1, float std2, void* stream) {
+    if (!frames || !idx_dev || !dst || !geo || N <= 0 || h <= 0 || w <= 0 || h > H || w > W || !ids_in_range(idx_host, N, F)) return CC_ERR_ARG;
+    dim3 g((unsigned)((h * w + 255) / 256), (unsigned)N);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_frames_to_tensor<unsigned char>), g, dim3(256), 0, (hipStream_t)stream,
+                       (const unsigned char*)frames, idx_dev, dst, geo, H, W, h, w, mean0, mean1, mean2, std0, std1, std2);
+    CC_CHECK_LAUNCH();
+    return CC_OK;
+}
+
+size_t cc_store_resize_ws_bytes(int N, int H, int tmp_w) { return (size_t)N * H * tmp_w * 3; }
+
+int cc_store_resize_to_tensor(const void* frames, const float* minmax_or_null, int F, const int* idx_host, const int* idx_dev,
+                              float* dst, const int* geo, const int* tab, int KT, void* ws, int N, int H, int W, int tmp_w, int max_sw,
+                              int h, int w, float mean0, float mean1, float mean2, float std0, float std1, float std2, void* stream) {
+    if (!frames || !idx_dev || !dst || !geo || !tab || !ws || N <= 0 || KT <= 0 || h <= 0 || w <= 0 || max_sw <= 0 || max_sw > tmp_w ||
+        !ids_in_range(idx_host, N, F))
+        return CC_ERR_ARG;
+    hipStream_t s = (hipStream_t)stream;
+    unsigned char* tmp = (unsigned char*)ws;
+    dim3 gh((unsigned)((max_sw + 255) / 256), (unsigned)H, (unsigned)N);
+    if (minmax_or_null)
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_frames_resize_h<unsigned char, true>), gh, dim3(256), 0, s, (const unsigned char*)frames,
+                           idx_dev, minmax_or_null, tmp, geo, tab, H, W, tmp_w, KT);
+    else
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_frames_resize_h<unsigned char, false>), gh, dim3(256), 0, s, (const unsigned char*)frames,
+                           idx_dev, minmax_or_null, tmp, geo, tab, H, W, tmp_w, KT);
+    hipLaunchKernelGGL(k_frames_resize_v, dim3((unsigned)((h * w + 255) / 256), (unsigned)N), dim3(256), 0, s,
+                       (const unsigned char*)tmp, dst, geo, tab, H, tmp_w, KT, h, w, mean0, mean1, mean2, std0, std1, std2);
+    CC_CHECK_LAUNCH();
+    return CC_OK;
+}
+
+int cc_store_rotate(const void* frames, const float* minmax_or_null, int F, const int* idx_host, const int* idx_dev, void* dst_u8,
+                    const double* rot, int N, int H, int W, void* stream) {
+    if (!frames || !idx_dev || !dst_u8 || !rot || N <= 0 || H <= 0 || W <= 0 || !ids_in_range(idx_host, N, F)) return CC_ERR_ARG;
+    hipStream_t s = (hipStream_t)stream;
+    dim3 g((unsigned)((H * W + 255) / 256), (unsigned)N);
+    if (minmax_or_null)
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_frames_rotate<unsigned char, true>), g, dim3(256), 0, s, (const unsigned char*)frames, idx_dev,
+                           minmax_or_null, (unsigned char*)dst_u8, rot, H, W);
+    else
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_frames_rotate<unsigned char, false>), g, dim3(256), 0, s, (const unsigned char*)frames, idx_dev,
+                           minmax_or_null, (unsigned char*)dst_u8, rot, H, W);
+    CC_CHECK_LAUNCH();
+    return CC_OK;
+}
+
+size_t cc_sample_local_norm_ws_bytes(int B) { return (size_t)B * 3 * (LNB * 2 + 2) * sizeof(double); }
+
+/* NormalizeLocally for B samples of nf frames [3,h,w] each, in place; sample_stride / frame_stride in floats ([B,nf,3,h,w]:
+ * nf * 3 * h * w and 3 * h * w; frame-major [nf,B,3,h,w]: 3 * h * w and B * 3 * h * w).  ws: cc_sample_local_norm_ws_bytes(B). */
+int cc_sample_local_norm(float* x, void* ws, int B, int nf, int h, int w, long sample_stride, long frame_stride, void* stream) {
+    if (!x || !ws || B <= 0 || nf <= 0 || h <= 0 || w <= 0 || (long)nf * h * w < 2 || sample_stride <= 0 || frame_stride <= 0) return CC_ERR_ARG;
+    hipStream_t s = (hipStream_t)stream;
+    double* part = (double*)ws;
+    double* stat = part + (size_t)B * 3 * LNB * 2;
+    const long hw = (long)h * w, total = (long)nf * hw;
+    hipLaunchKernelGGL(k_local_norm_partial, dim3(LNB, (unsigned)(B * 3)), dim3(256), 0, s, (const float*)x, part, nf, hw, sample_stride,
+                       frame_stride);
+    hipLaunchKernelGGL(k_local_norm_final, dim3((unsigned)(B * 3)), dim3(LNB), 0, s, (const double*)part, stat, (double)total);
+    long blocks = (total + 4 * 256 - 1) / (4 * 256);
+    if (blocks > 1024) blocks = 1024;
+    hipLaunchKernelGGL(k_local_norm_apply, dim3((unsigned)blocks, (unsigned)(B * 3)), dim3(256), 0, s, x, (const double*)stat, nf, hw,
+                       sample_stride, frame_stride);
     CC_CHECK_LAUNCH();
     return CC_OK;
 }

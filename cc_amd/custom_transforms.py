@@ -11,7 +11,9 @@ train.py:171-176 (--fix-flownet) leaves it out.
 
 Device side: ``DeviceFrames`` fuses ArrayToTensor + Normalize (+ the mirror of RandomHorizontalFlip and the crop of
 RandomScaleCrop) for a whole batch of frames into one HIP launch (``cc_frames_to_tensor``) -- HWC uint8 / float32 frames go
-to HBM as they are (4x less PCIe traffic for uint8) and come out as the normalised fp32 NCHW tensors the nets consume."""
+to HBM as they are (4x less PCIe traffic for uint8) and come out as the normalised fp32 NCHW tensors the nets consume.
+``DeviceTrainTransform.from_store`` runs the same pipeline on frames that never leave HBM: the uint8 ``FrameStore`` of
+cc_amd/datasets, read through an index table (``cc_store_*``)."""
 import random
 
 import numpy as np
@@ -227,18 +229,24 @@ class DeviceFrames(object):
         return dst
 
     # ---- RandomRotate on the device
+    @staticmethod
+    def _rot_table(angles, H, W):
+        """double [N,8] = (apply, a0..a5, 0) per frame: what cc_frames_rotate / cc_store_rotate take"""
+        rot = np.zeros((len(angles), 8), dtype=np.float64)
+        for n, a in enumerate(angles):
+            if a is not None and (a % 360.0) != 0:
+                assert (a % 360.0) not in (90.0, 180.0, 270.0), "quarter turns: Pillow transposes instead of resampling"
+                rot[n, 0] = 1.0
+                rot[n, 1:7] = rotate_matrix(W, H, a)
+        return rot
+
     def rotate(self, frames, angles):
         """scipy.misc.imrotate of every frame (angles[n] in degrees, None = not rotated: byte-scaled only, which is what the
         resize that follows does first) -> uint8 [N,H,W,3] on the device, bit-exact with the host classes."""
         src = self._to_device(frames)
         N, H, W, _ = src.shape
         assert len(angles) == N
-        rot = np.zeros((N, 8), dtype=np.float64)
-        for n, a in enumerate(angles):
-            if a is not None and (a % 360.0) != 0:
-                assert (a % 360.0) not in (90.0, 180.0, 270.0), "quarter turns: Pillow transposes instead of resampling"
-                rot[n, 0] = 1.0
-                rot[n, 1:7] = rotate_matrix(W, H, a)
+        rot = self._rot_table(angles, H, W)
         E = engine()
         ws = torch.empty(int(E.call("cc_frames_rotate_ws_bytes", N)), dtype=torch.uint8, device=self.device)
         dst = torch.empty(N, H, W, 3, dtype=torch.uint8, device=self.device)
@@ -246,12 +254,9 @@ class DeviceFrames(object):
         return dst
 
     # ---- RandomScaleCrop's resize on the device
-    def resize_crop(self, frames, scaled_hw, out_hw, flips=None, offsets=None):
-        """RandomHorizontalFlip -> imresize to scaled_hw -> crop out_hw at offsets -> ArrayToTensor -> Normalize, all on the
-        device and bit-exact with the host classes.  scaled_hw: (sh, sw) or one pair per frame (the frames of one sample share
-        a draw, the samples of a batch do not).  -> fp32 [N,3,h,w]."""
-        src = self._to_device(frames)
-        N, H, W, _ = src.shape
+    @staticmethod
+    def _resize_tables(N, H, W, scaled_hw, out_hw, flips, offsets):
+        """the host tables of the resize entries -> (geo int32 [N,8], tab int32, KT, max_sw, tmp_w)"""
         h, w = out_hw
         sizes = [tuple(scaled_hw)] * N if isinstance(scaled_hw[0], (int, np.integer)) else [tuple(s) for s in scaled_hw]
         assert len(sizes) == N
@@ -276,14 +281,94 @@ class DeviceFrames(object):
             geo[n, 3:7] = (sh, sw, offs[(W, sw)], offs[(H, sh)])
             assert 0 <= geo[n, 1] and geo[n, 1] + h <= sh and 0 <= geo[n, 2] and geo[n, 2] + w <= sw, "crop window outside the scaled frame"
         max_sw = max(sw for _, sw in sizes)
-        tmp_w = (max_sw + 3) // 4 * 4
+        return geo, np.concatenate(chunks), KT, max_sw, (max_sw + 3) // 4 * 4
+
+    def resize_crop(self, frames, scaled_hw, out_hw, flips=None, offsets=None):
+        """RandomHorizontalFlip -> imresize to scaled_hw -> crop out_hw at offsets -> ArrayToTensor -> Normalize, all on the
+        device and bit-exact with the host classes.  scaled_hw: (sh, sw) or one pair per frame (the frames of one sample share
+        a draw, the samples of a batch do not).  -> fp32 [N,3,h,w]."""
+        src = self._to_device(frames)
+        N, H, W, _ = src.shape
+        h, w = out_hw
+        geo, tab, KT, max_sw, tmp_w = self._resize_tables(N, H, W, scaled_hw, out_hw, flips, offsets)
         E = engine()
         ws = torch.empty(int(E.call("cc_frames_resize_ws_bytes", N, H, tmp_w)), dtype=torch.uint8, device=self.device)
         geo_d = torch.from_numpy(geo).to(self.device)
-        tab_d = torch.from_numpy(np.concatenate(chunks)).to(self.device)
+        tab_d = torch.from_numpy(tab).to(self.device)
         dst = torch.empty(N, 3, h, w, device=self.device, dtype=torch.float32)
         E.call("cc_frames_resize_to_tensor", src, int(src.dtype == torch.uint8), dst, geo_d, tab_d, KT, ws, N, H, W, tmp_w, max_sw, h, w,
                self.mean[0], self.mean[1], self.mean[2], self.std[0], self.std[1], self.std[2], STREAM)
+        return dst
+
+    # ---- the same three steps on the frames of a resident FrameStore (cc_amd/datasets), read in place through an index table
+    def _upload(self, *arrays):
+        """Small host tables -> device copies (in the order given) through ONE pinned block and one asynchronous copy: no
+        synchronisation with the device (the caching host allocator keeps the block until that copy has completed), plus the
+        pinned block itself (the host copies the entry points range-check).  arrays: int32 / float32 / float64 numpy arrays."""
+        arrays = [np.ascontiguousarray(a) for a in arrays]
+        offs, pos = [], 0
+        for a in arrays:
+            pos = (pos + 7) // 8 * 8
+            offs.append(pos)
+            pos += a.nbytes
+        host = torch.empty(pos, dtype=torch.uint8, pin_memory=self.device.type == "cuda")
+        hv = host.numpy()
+        for a, o in zip(arrays, offs):
+            hv[o:o + a.nbytes] = a.reshape(-1).view(np.uint8)
+        dev = host.to(self.device, non_blocking=True)
+        views = [dev[o:o + a.nbytes].view(torch.from_numpy(a).dtype).view(a.shape) for a, o in zip(arrays, offs)]
+        return views, host, offs
+
+    @staticmethod
+    def _check_ids(store, idx):
+        idx = np.ascontiguousarray(idx, dtype=np.int32).reshape(-1)
+        F = int(store.frames.shape[0])
+        if idx.size == 0 or int(idx.min()) < 0 or int(idx.max()) >= F:
+            raise ValueError("frame ids outside the store's [0, %d)" % F)
+        return idx, F
+
+    def store_to_tensor(self, store, idx, out_hw=None, flips=None, offsets=None):
+        """`__call__` on frames idx[n] of the store (the validation / plain path: no resampling) -> fp32 [N,3,h,w]."""
+        idx, F = self._check_ids(store, idx)
+        _, H, W, _ = store.frames.shape
+        N = idx.size
+        h, w = out_hw if out_hw is not None else (H, W)
+        geo = np.zeros((N, 3), dtype=np.int32)
+        if flips is not None:
+            geo[:, 0] = np.asarray(flips, dtype=np.int32)
+        if offsets is not None:
+            geo[:, 1:] = np.asarray(offsets, dtype=np.int32)
+        assert (geo[:, 1] >= 0).all() and (geo[:, 2] >= 0).all() and (geo[:, 1] + h <= H).all() and (geo[:, 2] + w <= W).all()
+        (idx_d, geo_d), host, offs = self._upload(idx, geo)
+        dst = torch.empty(N, 3, h, w, device=self.device, dtype=torch.float32)
+        engine().call("cc_store_to_tensor", store.frames, F, host.data_ptr() + offs[0], idx_d, dst, geo_d, N, H, W, h, w, self.mean[0],
+                      self.mean[1], self.mean[2], self.std[0], self.std[1], self.std[2], STREAM)
+        return dst
+
+    def store_resize_crop(self, store, idx, scaled_hw, out_hw, flips=None, offsets=None, angles=None, stretch=True):
+        """`rotate` (angles given) and `resize_crop` on frames idx[n] of the store.  stretch=True: the stored uint8 frames stand for
+        the float32 arrays the reference's loader decodes (byte-scaled to their own min..max, store.minmax); False: plain uint8
+        frames.  Bit-exact with the host classes either way.  -> fp32 [N,3,h,w]."""
+        idx, F = self._check_ids(store, idx)
+        _, H, W, _ = store.frames.shape
+        N = idx.size
+        h, w = out_hw
+        geo, tab, KT, max_sw, tmp_w = self._resize_tables(N, H, W, scaled_hw, out_hw, flips, offsets)
+        E = engine()
+        mm = store.minmax if stretch else None
+        dst = torch.empty(N, 3, h, w, device=self.device, dtype=torch.float32)
+        norm = (self.mean[0], self.mean[1], self.mean[2], self.std[0], self.std[1], self.std[2])
+        if angles is None:
+            (idx_d, geo_d, tab_d), host, offs = self._upload(idx, geo, tab)
+            ws = torch.empty(int(E.call("cc_store_resize_ws_bytes", N, H, tmp_w)), dtype=torch.uint8, device=self.device)
+            E.call("cc_store_resize_to_tensor", store.frames, mm, F, host.data_ptr() + offs[0], idx_d, dst, geo_d, tab_d, KT, ws, N, H, W,
+                   tmp_w, max_sw, h, w, *norm, STREAM)
+            return dst
+        (idx_d, geo_d, tab_d, rot_d), host, offs = self._upload(idx, geo, tab, self._rot_table(angles, H, W))
+        rotated = torch.empty(N, H, W, 3, dtype=torch.uint8, device=self.device)
+        E.call("cc_store_rotate", store.frames, mm, F, host.data_ptr() + offs[0], idx_d, rotated, rot_d, N, H, W, STREAM)
+        ws = torch.empty(int(E.call("cc_frames_resize_ws_bytes", N, H, tmp_w)), dtype=torch.uint8, device=self.device)
+        E.call("cc_frames_resize_to_tensor", rotated, 1, dst, geo_d, tab_d, KT, ws, N, H, W, tmp_w, max_sw, h, w, *norm, STREAM)
         return dst
 
 
@@ -319,21 +404,27 @@ class DeviceTrainTransform(object):
     `random` for the flip, then `np.random` uniform(1, 1.1, 2) and the two randint of RandomScaleCrop -- the same seeds give
     the same augmentations), the pixels never leave the device (`DeviceFrames.resize_crop`).
     samples: list of (frames, intrinsics) with frames = list of [H,W,3] arrays, all samples of one size.
-    -> (fp32 [B, n_frames, 3, h, w] on the device, list of updated intrinsics)."""
+    -> (fp32 [B, n_frames, 3, h, w] on the device, list of updated intrinsics).
+    normalize='local': train.py:168-169's NormalizeLocally in place of Normalize(mean, std) -- the frames leave the resize as
+    x / 255 (mean 0, std 1) and `cc_sample_local_norm` normalises every sample by its own per-channel statistics.
+    `from_store` is `__call__` on samples of a resident FrameStore (cc_amd/datasets)."""
 
-    def __init__(self, mean=(0.5, 0.5, 0.5), std=(0.5, 0.5, 0.5), device="cuda", h=0, w=0, rotate=False):
-        self.frames = DeviceFrames(mean, std, device)
+    def __init__(self, mean=(0.5, 0.5, 0.5), std=(0.5, 0.5, 0.5), device="cuda", h=0, w=0, rotate=False, normalize="global"):
+        if normalize not in ("global", "local"):
+            raise ValueError("normalize: 'global' or 'local', got %r" % (normalize,))
+        self.local = normalize == "local"
+        self.frames = DeviceFrames((0.0, 0.0, 0.0), (1.0, 1.0, 1.0), device) if self.local else DeviceFrames(mean, std, device)
         self.crop = RandomScaleCrop(h, w)
         self.rotate = rotate          # True: train.py:178-184 (RandomRotate first: the pipeline when the flow network is trained)
 
-    def __call__(self, samples):
-        flat, flips, offsets, sizes, Ks, angles = [], [], [], [], [], []
+    def _draw(self, shapes):
+        """The random decisions and the intrinsics arithmetic of one batch, sample by sample in the reference's order.
+        shapes: per sample (in_h, in_w, n_frames, K) -> per-frame angles, flips, offsets, scaled sizes; Ks; (oh, ow)."""
+        flips, offsets, sizes, Ks, angles = [], [], [], [], []
         out_hw = None
-        for frames, K in samples:
-            in_h, in_w, _ = frames[0].shape
+        for in_h, in_w, nf, K in shapes:
             K = np.copy(K)
             rot = RandomRotate.draw() if self.rotate else None                        # RandomRotate, :78-82 (intrinsics unchanged)
-            angles += [rot] * len(frames)
             flip = random.random() < 0.5                                              # RandomHorizontalFlip, :62
             if flip:
                 K[0, 2] = in_w - K[0, 2]
@@ -344,14 +435,55 @@ class DeviceTrainTransform(object):
             K[1, 2] -= oy
             assert out_hw in (None, (oh, ow)), "DeviceTrainTransform: samples of one batch must share the output size"
             out_hw = (oh, ow)
-            for f in frames:
-                flat.append(f)
-                flips.append(int(flip))
-                offsets.append((oy, ox))
-                sizes.append((sh, sw))
+            angles += [rot] * nf
+            flips += [int(flip)] * nf
+            offsets += [(oy, ox)] * nf
+            sizes += [(sh, sw)] * nf
             Ks.append(K)
+        return angles, flips, offsets, sizes, Ks, out_hw
+
+    def _local_norm(self, x, B, nf, sample_stride, frame_stride):
+        h, w = x.shape[-2:]
+        E = engine()
+        ws = torch.empty(int(E.call("cc_sample_local_norm_ws_bytes", B)), dtype=torch.uint8, device=x.device)
+        E.call("cc_sample_local_norm", x, ws, B, nf, h, w, sample_stride, frame_stride, STREAM)
+
+    def __call__(self, samples):
+        flat = [f for frames, _ in samples for f in frames]
+        nf = len(samples[0][0])
+        angles, flips, offsets, sizes, Ks, out_hw = self._draw([frames[0].shape[:2] + (len(frames), K) for frames, K in samples])
         if self.rotate:
             flat = self.frames.rotate(flat, angles)           # uint8 frames on the device; flip / resize / crop follow there
         out = self.frames.resize_crop(flat, sizes, out_hw, flips, offsets)
-        nf = len(samples[0][0])
-        return out.view(len(samples), nf, 3, out_hw[0], out_hw[1]), Ks
+        out = out.view(len(samples), nf, 3, out_hw[0], out_hw[1])
+        if self.local:
+            self._local_norm(out, len(samples), nf, nf * 3 * out_hw[0] * out_hw[1], 3 * out_hw[0] * out_hw[1])
+        return out, Ks
+
+    def from_store(self, store, sample_ids, frame_major=False, stretch=True):
+        """`__call__` on samples `sample_ids` of a FrameStore: the same draws in the same order, so the same seeds give the same
+        batch as `__call__` on the decoded float32 frames of those samples -- bit for bit, the stored uint8 frames being
+        byte-scaled with their stored (min, max).  The host draws and uploads small tables; no frame is copied and nothing waits
+        for the device.  -> (fp32 [B,nf,3,h,w], Ks); frame_major=True: [nf,B,3,h,w], whose slices are the contiguous
+        [B,3,h,w] batches of the target and of each reference frame.  stretch=False: the stored frames are taken as plain uint8
+        frames (what `__call__` computes for uint8 arrays)."""
+        ids = np.asarray(sample_ids, dtype=np.int64).reshape(-1)
+        S, nf = store.samples.shape
+        if ids.size == 0 or int(ids.min()) < 0 or int(ids.max()) >= S:
+            raise ValueError("sample ids outside the store's [0, %d)" % S)
+        B = ids.size
+        _, H, W, _ = store.frames.shape
+        Kall = store.intrinsics_np[store.sample_scene_np[ids]]
+        angles, flips, offsets, sizes, Ks, (oh, ow) = self._draw([(H, W, nf, K) for K in Kall])
+        idx = store.samples_np[ids]                                        # [B,nf] frame ids, the target first
+        if frame_major:                                                    # launch frame i * B + b <- frame i of sample b
+            order = np.arange(B * nf).reshape(B, nf).T.reshape(-1)
+            idx = idx.reshape(-1)[order]
+            angles, flips, offsets, sizes = ([v[j] for j in order] for v in (angles, flips, offsets, sizes))
+        out = self.frames.store_resize_crop(store, idx, sizes, (oh, ow), flips, offsets, angles if self.rotate else None,
+                                            stretch)
+        out = out.view((nf, B, 3, oh, ow) if frame_major else (B, nf, 3, oh, ow))
+        if self.local:
+            one = 3 * oh * ow
+            self._local_norm(out, B, nf, *((one, B * one) if frame_major else (nf * one, one)))
+        return out, Ks

@@ -370,6 +370,32 @@ int cc_frames_resize_to_tensor(const void* src, int src_is_u8, float* dst, const
 size_t cc_frames_rotate_ws_bytes(int N);
 int cc_frames_rotate(const void* src, int src_is_u8, void* dst_u8, const double* rot, void* ws, int N, int H, int W, void* stream);
 
+/* ---- the resident frame store (cc_amd/datasets: FrameStore, DeviceSequenceLoader).  Every distinct training frame is decoded once
+ * on the host and kept in device memory as uint8 -- frames: [F,H,W,3], more than 4 GiB in real use (all frame offsets are 64-bit);
+ * minmax: fp32 [F,2], each frame's own (min, max), filled once by cc_store_minmax (exact).  The reference's loader hands FLOAT32
+ * frames to imresize / imrotate, which byte-scale every frame to its own min..max first (datasets/sequence_folders.py:26-27,
+ * custom_transforms.py:75-121): the store-indexed forms below read frame idx[n] of the store in place of frame n of a batch and,
+ * given `minmax`, push every uint8 tap through that float arithmetic (cmax == cmin: scale 1), bit for bit what the float32 path
+ * of the cc_frames_* entries computes for the same pixels; minmax == NULL: plain uint8 frames.
+ * idx_host / idx_dev: the same int32 [N] table in host and in device memory; an id outside [0, F) in the host copy -> CC_ERR_ARG
+ * before anything is launched (the kernels read the device copy).  geo / tab / rot / dst / the constants: as in the cc_frames_* entries;
+ * cc_store_rotate's dense uint8 output goes on through cc_frames_resize_to_tensor(src_is_u8 = 1). */
+int cc_store_minmax(const void* frames, float* minmax, int F, long per_frame, void* stream);
+int cc_store_to_tensor(const void* frames, int F, const int* idx_host, const int* idx_dev, float* dst, const int* geo, int N, int H,
+                       int W, int h, int w, float mean0, float mean1, float mean2, float std0, float std1, float std2, void* stream);
+size_t cc_store_resize_ws_bytes(int N, int H, int tmp_w);
+int cc_store_resize_to_tensor(const void* frames, const float* minmax_or_null, int F, const int* idx_host, const int* idx_dev,
+                              float* dst, const int* geo, const int* tab, int KT, void* ws, int N, int H, int W, int tmp_w, int max_sw,
+                              int h, int w, float mean0, float mean1, float mean2, float std0, float std1, float std2, void* stream);
+int cc_store_rotate(const void* frames, const float* minmax_or_null, int F, const int* idx_host, const int* idx_dev, void* dst_u8,
+                    const double* rot, int N, int H, int W, void* stream);
+/* NormalizeLocally (custom_transforms.py:33-44, train.py:168-169 `--data-normalization local`) in place on B samples of nf frames
+ * [3,h,w] that are already / 255: per sample and channel the mean and the UNBIASED standard deviation over the sample's nf frames
+ * (fp64 sums, two launches), then (x - m) / s.  Element (b, i, c, y, x) lies at b * sample_stride + i * frame_stride + (c * h + y) * w + x
+ * floats.  ws: cc_sample_local_norm_ws_bytes(B) bytes. */
+size_t cc_sample_local_norm_ws_bytes(int B);
+int cc_sample_local_norm(float* x, void* ws, int B, int nf, int h, int w, long sample_stride, long frame_stride, void* stream);
+
 /* ---------------------------------------------------------------- BatchNorm2d, training mode
  * (models/DispResNet6.py:53-56: the Conv1x1 + BatchNorm2d shortcut of every ResNet stage; 13 per forward)
  * y = (x - mean_c) / sqrt(var_c + eps) * w_c + b_c with batch statistics over (B,H,W); running stats updated with
