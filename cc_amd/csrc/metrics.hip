@@ -89,18 +89,73 @@ __device__ __forceinline__ double block_sum(double v, double* red) {
     return r;
 }
 
+__host__ __device__ inline int flow_blocks(int B, int Hg, int Wg) {
+    const long n = (long)B * Hg * Wg;
+    const long nb = (n + kThreads - 1) / kThreads;
+    return (int)(nb < kMaxFlowBlocks ? nb : kMaxFlowBlocks);
+}
+
+// cc_flow_metrics_samples: the ground truth of sample s of the launch is row idx[s] of a device table, so one launch shape serves
+// batches whose ground truths differ in size
+struct FlowTable {
+    const float* flow_pool;     // (u, v, valid) planes, [3,Hg,Wg] per sample at its flow offset
+    const float* obj_pool;      // object maps, [Hg,Wg] per sample at its obj-map offset
+    const long* table;          // [N,4] {flow offset, obj-map offset, Hg, Wg}, offsets in floats
+    const int* idx;             // [B] table rows of this batch
+    long flow_floats, obj_floats, max_px;
+    int N, slab;                // slab: the workgroups (partial slots) a sample owns = flow_blocks(1, max_px)
+};
+
+// row idx[s] of the table; false for a row that is outside the table, larger than max_px or reaches outside a pool
+__device__ __forceinline__ bool table_row(const FlowTable& t, int s, long& fo, long& oo, int& Hg, int& Wg) {
+    const int r = t.idx[s];
+    if (r < 0 || r >= t.N) return false;
+    const long* row = t.table + 4 * (long)r;
+    fo = row[0];
+    oo = row[1];
+    const long h = row[2], w = row[3];
+    if (h <= 0 || w <= 0 || h > t.max_px || w > t.max_px || h * w > t.max_px) return false;     // max_px < 2^31: no overflow
+    if (fo < 0 || oo < 0 || fo > t.flow_floats - 3 * h * w || oo > t.obj_floats - h * w) return false;
+    Hg = (int)h;
+    Wg = (int)w;
+    return true;
+}
+
 // one pass over the ground-truth pixels; per mask k the seven sums of compute_all_epes (loss_functions.py:411-429), or with no
 // mask the epe / valid / outlier sums of compute_epe and outlier_err (:368-409) in the same slots
 // NV = max(nmasks, 1), a template argument so that the accumulators stay in registers
-template <int NV>
-__global__ __launch_bounds__(kThreads) void k_flow_metrics(FlowArgs a, double* partial) {
+// TABLE: workgroup (x, s) of a kMaxFlowBlocks-wide grid works on sample s alone, as workgroup x of the flow_blocks(1, Hg, Wg) that
+// cc_flow_metrics launches for that sample at B = 1 -- the same stride, accumulators and tree, hence the same sums; the surplus
+// workgroups return at once
+template <int NV, bool TABLE>
+__global__ __launch_bounds__(kThreads) void k_flow_metrics(FlowArgs a, FlowTable t, double* partial) {
     __shared__ double red[kThreads];
+    int nblk = gridDim.x;
+    if (TABLE) {
+        const int s = blockIdx.y;
+        long fo, oo;
+        int Hg, Wg;
+        if (!table_row(t, s, fo, oo, Hg, Wg)) return;
+        nblk = flow_blocks(1, Hg, Wg);
+        if ((int)blockIdx.x >= nblk) return;
+        const long HWp = (long)a.Hp * a.Wp;
+        a.gt = t.flow_pool + fo;
+        a.rigid += (long)s * 2 * HWp;
+        a.non_rigid += (long)s * 2 * HWp;
+        a.mask[0].m += (long)s * a.mask[0].H * a.mask[0].W;
+        a.mask[1] = MaskIn{t.obj_pool + oo, Hg, Wg, 1};
+        a.B = 1;
+        a.Cg = 3;
+        a.Hg = Hg;
+        a.Wg = Wg;
+        partial += (long)s * t.slab * NV * kFlowSums;
+    }
     double acc[NV * kFlowSums];
 #pragma unroll
     for (int i = 0; i < NV * kFlowSums; i++) acc[i] = 0.0;
     const long HWg = (long)a.Hg * a.Wg, HWp = (long)a.Hp * a.Wp, n = (long)a.B * HWg;
     const float su = (float)((double)a.Wg / (double)a.Wp), sv = (float)((double)a.Hg / (double)a.Hp);
-    for (long i = (long)blockIdx.x * kThreads + threadIdx.x; i < n; i += (long)gridDim.x * kThreads) {
+    for (long i = (long)blockIdx.x * kThreads + threadIdx.x; i < n; i += (long)nblk * kThreads) {
         const int b = (int)(i / HWg);
         const long p = i - (long)b * HWg;
         const int y = (int)(p / a.Wg), x = (int)(p - (long)y * a.Wg);
@@ -172,8 +227,8 @@ __global__ __launch_bounds__(kThreads) void k_flow_metrics(FlowArgs a, double* p
     }
 }
 
-__global__ __launch_bounds__(64) void k_flow_finish(const double* partial, int nblocks, int nmasks, int Cg, long npix, float* out) {
-    __shared__ double tot[kMaxMasks * kFlowSums];
+// the workgroups' partials summed in workgroup order -> the metrics of one cc_flow_metrics call (one workgroup of 64 threads)
+__device__ __forceinline__ void flow_finish(const double* partial, int nblocks, int nmasks, int Cg, long npix, float* out, double* tot) {
     const int nv = nmasks > 0 ? nmasks : 1, ns = nv * kFlowSums;
     const int t = threadIdx.x;
     if (t < ns) {
@@ -201,10 +256,33 @@ __global__ __launch_bounds__(64) void k_flow_finish(const double* partial, int n
     }
 }
 
-int flow_blocks(int B, int Hg, int Wg) {
-    const long n = (long)B * Hg * Wg;
-    const long nb = (n + kThreads - 1) / kThreads;
-    return (int)(nb < kMaxFlowBlocks ? nb : kMaxFlowBlocks);
+__global__ __launch_bounds__(64) void k_flow_finish(const double* partial, int nblocks, int nmasks, int Cg, long npix, float* out) {
+    __shared__ double tot[kMaxMasks * kFlowSums];
+    flow_finish(partial, nblocks, nmasks, Cg, npix, out, tot);
+}
+
+// workgroup s: row s of out [B,8] from the sample's own partials; NaN for a row that table_row refuses
+__global__ __launch_bounds__(64) void k_flow_finish_samples(const double* partial, FlowTable t, float* out) {
+    __shared__ double tot[kMaxMasks * kFlowSums];
+    const int s = blockIdx.x;
+    long fo, oo;
+    int Hg, Wg;
+    if (!table_row(t, s, fo, oo, Hg, Wg)) {
+        if (threadIdx.x < 2 * 4) out[(long)s * 8 + threadIdx.x] = __int_as_float(0x7fc00000);
+        return;
+    }
+    flow_finish(partial + (long)s * t.slab * 2 * kFlowSums, flow_blocks(1, Hg, Wg), 2, 3, (long)Hg * Wg, out + (long)s * 8, tot);
+}
+
+// the meter: one workgroup adds the B rows to the running fp64 sums in sample order, and B to the count
+__global__ __launch_bounds__(64) void k_flow_accumulate(const float* out, int B, double* sums, long* count) {
+    const int t = threadIdx.x;
+    if (t < 8) {
+        double s = sums[t];
+        for (int b = 0; b < B; b++) s += (double)out[(long)b * 8 + t];
+        sums[t] = s;
+    }
+    if (t == 0) count[0] += (long)B;
 }
 
 // ------------------------------------------------------------------------------------------------------------- depth errors
@@ -378,13 +456,65 @@ int cc_flow_metrics(const float* gt, int Cg, int Hg, int Wg, const float* rigid_
     const int nblk = flow_blocks(B, Hg, Wg);
     double* partial = (double*)ws;
     if (nmasks == 2)
-        hipLaunchKernelGGL(k_flow_metrics<2>, dim3(nblk), dim3(kThreads), 0, (hipStream_t)stream, a, partial);
+        hipLaunchKernelGGL((k_flow_metrics<2, false>), dim3(nblk), dim3(kThreads), 0, (hipStream_t)stream, a, FlowTable{}, partial);
     else
-        hipLaunchKernelGGL(k_flow_metrics<1>, dim3(nblk), dim3(kThreads), 0, (hipStream_t)stream, a, partial);
+        hipLaunchKernelGGL((k_flow_metrics<1, false>), dim3(nblk), dim3(kThreads), 0, (hipStream_t)stream, a, FlowTable{}, partial);
     CC_CHECK_LAUNCH();
     hipLaunchKernelGGL(k_flow_finish, dim3(1), dim3(64), 0, (hipStream_t)stream, (const double*)partial, nblk, nmasks, Cg,
                        (long)B * Hg * Wg, out);
     CC_CHECK_LAUNCH();
+    return CC_OK;
+}
+
+size_t cc_flow_metrics_samples_ws(int B, long max_px) {
+    if (B <= 0 || max_px < 1 || max_px > 0x7fffffffL) return 0;
+    return (size_t)B * flow_blocks(1, 1, (int)max_px) * 2 * kFlowSums * sizeof(double);
+}
+
+int cc_flow_metrics_samples(const float* flow_pool, long flow_floats, const float* obj_pool, long obj_floats, const long* table, int N,
+                            const int* idx, int B, long max_px, const float* rigid_pred, const float* non_rigid_pred, int Hp, int Wp,
+                            const float* mask0, int Hm0, int Wm0, float thresh, float tau_px, float tau_rel, float* out,
+                            double* acc_sums, long* acc_count, void* ws, void* stream) {
+    if (!flow_pool || !obj_pool || !table || !idx || !rigid_pred || !non_rigid_pred || !mask0 || !out || !ws) return CC_ERR_ARG;
+    if ((acc_sums != nullptr) != (acc_count != nullptr)) return CC_ERR_ARG;
+    if (B <= 0 || B > 65535 || N <= 0 || max_px < 1 || max_px > 0x7fffffffL || flow_floats < 3 || obj_floats < 1) return CC_ERR_ARG;
+    if (Hp <= 0 || Wp <= 0 || Hm0 <= 0 || Wm0 <= 0) return CC_ERR_ARG;
+    FlowArgs a;
+    a.gt = nullptr;
+    a.rigid = rigid_pred;
+    a.non_rigid = non_rigid_pred;
+    a.mask[0] = MaskIn{mask0, Hm0, Wm0, 0};
+    a.mask[1] = MaskIn{nullptr, 0, 0, 1};
+    a.nmasks = 2;
+    a.B = 1;
+    a.Cg = 3;
+    a.Hg = a.Wg = 0;
+    a.Hp = Hp;
+    a.Wp = Wp;
+    a.thresh = thresh;
+    a.tau_px = tau_px;
+    a.tau_rel = tau_rel;
+    a.epe_map = nullptr;
+    FlowTable t;
+    t.flow_pool = flow_pool;
+    t.obj_pool = obj_pool;
+    t.table = table;
+    t.idx = idx;
+    t.flow_floats = flow_floats;
+    t.obj_floats = obj_floats;
+    t.max_px = max_px;
+    t.N = N;
+    t.slab = flow_blocks(1, 1, (int)max_px);
+    double* partial = (double*)ws;
+    const hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL((k_flow_metrics<2, true>), dim3(t.slab, B), dim3(kThreads), 0, s, a, t, partial);
+    CC_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_flow_finish_samples, dim3(B), dim3(64), 0, s, (const double*)partial, t, out);
+    CC_CHECK_LAUNCH();
+    if (acc_sums) {
+        hipLaunchKernelGGL(k_flow_accumulate, dim3(1), dim3(64), 0, s, (const float*)out, B, acc_sums, acc_count);
+        CC_CHECK_LAUNCH();
+    }
     return CC_OK;
 }
 

@@ -567,21 +567,31 @@ def pose_statistics(errors, n_rows=None):
     return {'mean': E.mean(0), 'std': E.std(0)}
 
 
-def evaluate_flow(disp_net, pose_net, mask_net, flow_net, framework, THRESH=0.01, flownet='Back2Future', img_hw=(256, 832)):
+def evaluate_flow(disp_net, pose_net, mask_net, flow_net, framework, THRESH=0.01, flownet='Back2Future', img_hw=(256, 832), store=None,
+                  batch_size=1):
     """test_flow.py:main without argparse over a Kitti2015Flow framework -> (errors [8] fp64 numpy, FLOW_ERROR_NAMES): EPE of
     the composed flow over all / static / moving pixels and Fl, with the predicted rigidity mask and with the ground-truth object
     map.  test_flow.py:108-146 is the loop of train.py:650-748 statement for statement (and has no spatial_normalize), so the
     items go through validate.validate_flow_with_gt unchanged: one launch for the composition, one for the eight errors, one
-    host read-back after the loop.  The ground-truth PNG is inflated on the host and unfiltered on the device."""
+    host read-back after the loop.  The ground-truth PNG is inflated on the host and unfiltered on the device.
+
+    store: a `datasets.FlowValStore` of the framework (`FlowValStore.build(framework, img_hw, device)`, or loaded from its cache):
+    the pass then reads no file -- `framework` may be None -- and goes through validate.validate_flow_from_store, batch_size
+    samples per forward pass.  Without a store, batch_size must be 1 (the ground truths differ in size)."""
     from . import validate as V
     from .custom_transforms import DeviceFrames
+    args = types.SimpleNamespace(THRESH=THRESH, flownet=flownet, spatial_normalize=False)
+    if store is not None:
+        errors, _ = V.validate_flow_from_store(store, disp_net, pose_net, mask_net, flow_net, batch_size=batch_size, args=args)
+        return np.asarray(errors, dtype=np.float64), list(FLOW_ERROR_NAMES)
+    if batch_size != 1:
+        raise ValueError("evaluate_flow: batch_size %d needs a FlowValStore (store=)" % batch_size)
     frames_dev = DeviceFrames(device=_device_of(disp_net))
 
     def items():
         for i in range(len(framework)):
             yield kitti2015_item(framework[i], img_hw, frames_dev)[:6]
 
-    args = types.SimpleNamespace(THRESH=THRESH, flownet=flownet, spatial_normalize=False)
     errors, _ = V.validate_flow_with_gt(items(), disp_net, pose_net, mask_net, flow_net, args=args)
     return np.asarray(errors, dtype=np.float64), list(FLOW_ERROR_NAMES)
 
@@ -696,10 +706,29 @@ def _four_nets(args, dev):
     return disp_net, pose_net, mask_net, flow_net
 
 
+def _flow_store(args, framework, dev):
+    """the resident store of --batch-size / --cache: loaded from the cache directory when it holds one, else built (and saved)"""
+    import os
+    from .datasets import FlowValStore
+    if args.cache is not None and os.path.isfile(os.path.join(args.cache, "store.json")):
+        store = FlowValStore.load(args.cache, device=dev)
+        if len(store) != len(framework) or tuple(store.inputs.shape[3:]) != (args.img_height, args.img_width):
+            raise ValueError("%s holds %d samples at %d x %d, not the %d at %d x %d asked for"
+                             % (args.cache, len(store), store.inputs.shape[3], store.inputs.shape[4], len(framework), args.img_height,
+                                args.img_width))
+        return store
+    store = FlowValStore.build(framework, (args.img_height, args.img_width), device=dev)
+    if args.cache is not None:
+        store.save(args.cache)
+    return store
+
+
 def _flow_main(args):
     dev = torch.device('cuda')
     framework = Kitti2015Flow(args.kitti_dir, sequence_length=5, N=args.N)
-    errors, names = evaluate_flow(*_four_nets(args, dev), framework, args.THRESH, args.flownet, (args.img_height, args.img_width))
+    store = _flow_store(args, framework, dev) if (args.cache is not None or args.batch_size != 1) else None
+    errors, names = evaluate_flow(*_four_nets(args, dev), framework, args.THRESH, args.flownet, (args.img_height, args.img_width),
+                                  store=store, batch_size=args.batch_size)
     print("Results")
     print("\t {:>10}, {:>10}, {:>10}, {:>6}, {:>10}, {:>10}, {:>10}, {:>10} ".format(*names))
     print("Errors \t {:10.4f}, {:10.4f}, {:10.4f}, {:10.4f}, {:10.4f}, {:10.4f}, {:10.4f}, {:10.4f}".format(*errors))
@@ -759,7 +788,12 @@ def parser():
     q.add_argument("--dataset-dir", default='.', type=str, help="KITTI odometry directory")
     q.add_argument("--sequences", default=['09'], type=str, nargs='*', help="sequences to test")
     q.add_argument("--rotation-mode", default='euler', choices=['euler', 'quat'], type=str)
-    _kitti2015_arguments(sub.add_parser('flow', help='test_flow.py: KITTI 2015 EPE all / static / moving and Fl'), 0.01)
+    f = sub.add_parser('flow', help='test_flow.py: KITTI 2015 EPE all / static / moving and Fl')
+    _kitti2015_arguments(f, 0.01)
+    f.add_argument('--batch-size', dest='batch_size', type=int, default=1,
+                   help='samples per forward pass; above 1 the samples are kept on the device (datasets.FlowValStore)')
+    f.add_argument('--cache', dest='cache', type=str, default=None, metavar='DIR',
+                   help='keep the samples on the device and cache the decoded store in DIR (loaded from there when present)')
     _kitti2015_arguments(sub.add_parser('mask', help='test_mask.py: motion-segmentation IoU (full, census only, bare)'), 0.94)
     return p
 

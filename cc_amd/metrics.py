@@ -61,6 +61,51 @@ def flow_metrics(gt, rigid_pred, non_rigid_pred=None, masks=(), THRESH=0.5, epe_
     return (out, emap) if epe_map else out
 
 
+class ErrorSums(object):
+    """The running meter of `flow_metrics_samples`: fp64 sums [8] and an int64 count [1] in one 72-byte device buffer, which the
+    kernel adds to.  `read()` is the one host read-back -> (sums / count as a list of 8 floats, count)."""
+
+    def __init__(self, device):
+        self.buf = torch.zeros(72, dtype=torch.uint8, device=device)
+        self.sums, self.count = self.buf[:64].view(torch.float64), self.buf[64:].view(torch.int64)
+
+    def read(self, extra=None):
+        """extra: an optional device flag (0-dim bool) that travels with the same copy -> (..., bool(extra))"""
+        buf = self.buf if extra is None else torch.cat([self.buf, extra.reshape(1).to(torch.uint8)])
+        host = buf.cpu()
+        sums, n = host[:64].view(torch.float64), int(host[64:72].view(torch.int64)[0])
+        means = [float(v) / n if n else float("nan") for v in sums]
+        return (means, n) if extra is None else (means, n, bool(host[72]))
+
+
+def flow_metrics_samples(flow_pool, obj_pool, table, idx, rigid_pred, non_rigid_pred, mask, max_px, THRESH=0.5, tau=TAU, acc=None):
+    """The eight flow errors of validate_flow_with_gt (train.py:748: compute_all_epes with the predicted mask, then with
+    1 - obj_map_gt) for B samples whose ground truths differ in size, in one call -> fp32 [B,8] on the device, one row per sample.
+    flow_pool / obj_pool: 1-D fp32 device pools; table: device int64 [N,4] rows {flow offset, obj-map offset, Hg, Wg} (offsets in
+    floats: the sample's [3,Hg,Wg] (u, v, valid) planes and its [Hg,Wg] object map); idx: device int32 [B], the table rows of
+    this batch; rigid_pred / non_rigid_pred [B,2,Hp,Wp]; mask [B,1,Hm,Wm] the predicted rigidity mask; max_px: the largest
+    Hg * Wg among the table's rows (the only geometry the host passes).  acc: an `ErrorSums` the rows are added to, in order.
+    Row b equals `flow_metrics(gt_b, rigid_pred[b:b+1], non_rigid_pred[b:b+1], masks=(mask[b:b+1], ("1-", obj_b)))` bit for bit."""
+    assert flow_pool.dim() == 1 and obj_pool.dim() == 1 and flow_pool.dtype == torch.float32 and obj_pool.dtype == torch.float32, \
+        "flow_metrics_samples: the pools are 1-D fp32 tensors"
+    assert table.dim() == 2 and table.shape[1] == 4 and table.dtype == torch.int64, "flow_metrics_samples: table must be int64 [N,4]"
+    assert idx.dim() == 1 and idx.dtype == torch.int32, "flow_metrics_samples: idx must be int32 [B]"
+    B = idx.shape[0]
+    assert rigid_pred.dim() == 4 and rigid_pred.shape[:2] == (B, 2) and non_rigid_pred.shape == rigid_pred.shape, \
+        "flow_metrics_samples: predictions must be [B,2,H,W] of one shape, B = len(idx)"
+    Hp, Wp = rigid_pred.shape[2:]
+    m, Hm, Wm, inv = _mask(mask, B)
+    assert not inv, "flow_metrics_samples: the predicted mask is not inverted"
+    dev = rigid_pred.device
+    out = torch.empty((B, 8), dtype=torch.float32, device=dev)
+    e = engine()
+    ws = torch.empty(e.call("cc_flow_metrics_samples_ws", B, int(max_px)), dtype=torch.uint8, device=dev)
+    e.call("cc_flow_metrics_samples", flow_pool, flow_pool.numel(), obj_pool, obj_pool.numel(), table.contiguous(), table.shape[0],
+           idx.contiguous(), B, int(max_px), _f32(rigid_pred), _f32(non_rigid_pred), Hp, Wp, m, Hm, Wm, float(THRESH), float(tau[0]),
+           float(tau[1]), out, None if acc is None else acc.sums, None if acc is None else acc.count, ws, STREAM)
+    return out
+
+
 def crop_box(H, W, crop=True):
     """Garg / Eigen crop of compute_errors (loss_functions.py:441-444) as rows [y1,y2) x cols [x1,x2); the whole image without."""
     if not crop:

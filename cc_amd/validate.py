@@ -134,3 +134,68 @@ def validate_flow_with_gt(val_loader, disp_net, pose_net, mask_net, flow_net, ep
     if nan_seen is not None and bool(nan_seen):
         print('NaN encountered')                                               # :747
     return _finish(errors), error_names
+
+
+# ------------------------------------------------------------------------------------- the same two passes over resident stores
+def validate_flow_from_store(store, disp_net, pose_net, mask_net, flow_net, batch_size=1, args=None, on_batch=None):
+    """validate_flow_with_gt over a `datasets.FlowValStore`, batch_size samples at a time -> (errors, error_names).  Per batch: the
+    four forward passes, pose2flow, the per-sample composition and ONE `metrics.flow_metrics_samples` call, which scores every
+    sample against its own ground truth (read where it lies, through the store's table) and adds the rows to a device meter in
+    sample order.  The NaN flag of train.py:746 stays on the device; the meter and the flag are read back once, after the loop;
+    errors = sums / count in fp64 (the sums are fp64 where AverageMeter's are fp32).  At batch_size=1 every row is what
+    validate_flow_with_gt computes for that sample; larger batches change only what the networks' own kernels make of a batch.
+    on_batch(k, dict): the hook of a caller's own logging, called per batch with idx, the rows [b,8] and the tensors they were
+    computed from (flow_cam, flow_fwd, rigidity_mask_combined, total_flow)."""
+    from .datasets import DeviceFlowValLoader
+    assert args is not None, "validate_flow_from_store: pass the training arguments namespace as args= (THRESH, flownet, spatial_normalize)"
+    for net in (disp_net, pose_net, mask_net, flow_net):
+        net.eval()
+    acc = metrics.ErrorSums(store.device)
+    nan_seen = store.gt_nan()
+    with torch.no_grad():
+        for k, (tgt_img, ref_imgs, intrinsics, intrinsics_inv, idx) in enumerate(DeviceFlowValLoader(store, batch_size).batches()):
+            flow_cam, flow_fwd, r = _flow_batch(tgt_img, ref_imgs, intrinsics, intrinsics_inv, disp_net, pose_net, mask_net, flow_net, args)
+            nan_seen = nan_seen | torch.isnan(r.total_flow.sum())
+            rows = metrics.flow_metrics_samples(store.flow_pool, store.obj_pool, store.table, idx, flow_cam, flow_fwd,
+                                                r.rigidity_mask_combined, store.max_px, THRESH=0.5, acc=acc)
+            if on_batch is not None:
+                on_batch(k, dict(idx=idx, rows=rows, flow_cam=flow_cam, flow_fwd=flow_fwd, rigidity_mask_combined=r.rigidity_mask_combined,
+                                 total_flow=r.total_flow))
+    errors, _, nan = acc.read(extra=nan_seen)                                  # the loop's only host read-back
+    if nan:
+        print('NaN encountered')
+    return errors, list(FLOW_ERROR_NAMES)
+
+
+def _flow_batch(tgt_img, ref_imgs, intrinsics, intrinsics_inv, disp_net, pose_net, mask_net, flow_net, args):
+    """train.py:659-687 for one batch -> (flow_cam, flow_fwd, composition)"""
+    disp = disp_net(tgt_img)
+    if getattr(args, "spatial_normalize", False):
+        disp = LF.spatial_normalize(disp)
+    depth = 1 / disp
+    pose = pose_net(tgt_img, ref_imgs)
+    explainability_mask = mask_net(tgt_img, ref_imgs)
+    if getattr(args, "flownet", "Back2Future") == 'Back2Future':
+        flow_fwd, _, _ = flow_net(tgt_img, ref_imgs[1:3])
+    else:
+        flow_fwd = flow_net(tgt_img, ref_imgs[2])
+    flow_cam = pose2flow(depth.squeeze(1), pose[:, 2], intrinsics, intrinsics_inv)
+    r = rigidity_composition(explainability_mask, flow_cam, flow_fwd, args.THRESH, want=("rigidity_mask_combined", "total_flow"))
+    return flow_cam, flow_fwd, r
+
+
+def validate_depth_from_store(store, disp_net, batch_size, args=None):
+    """validate_depth_with_gt over a `datasets.DepthValStore` -> (errors, error_names).  As there, every batch's mean counts once
+    (AverageMeter.update(n=1), so a short last batch weighs as much as a full one); the six errors are summed in fp64 on the
+    device and read back once."""
+    from .datasets import DeviceDepthValLoader
+    disp_net.eval()
+    total, n = torch.zeros(len(DEPTH_ERROR_NAMES), dtype=torch.float64, device=store.device), 0
+    with torch.no_grad():
+        for tgt_img, depth in DeviceDepthValLoader(store, batch_size):
+            output_disp = disp_net(tgt_img)
+            if args is not None and getattr(args, "spatial_normalize", False):
+                output_disp = LF.spatial_normalize(output_disp)
+            total += metrics.depth_errors(depth, (1 / output_disp).squeeze(1)).double()
+            n += 1
+    return (total / n).tolist(), list(DEPTH_ERROR_NAMES)

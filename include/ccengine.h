@@ -512,6 +512,23 @@ size_t cc_flow_metrics_ws(int B, int Hg, int Wg, int nmasks);
 int cc_flow_metrics(const float* gt, int Cg, int Hg, int Wg, const float* rigid_pred, const float* non_rigid_pred, int Hp, int Wp,
                     const float* mask0, int Hm0, int Wm0, int inv0, const float* mask1, int Hm1, int Wm1, int inv1, float thresh,
                     float tau_px, float tau_rel, int B, float* epe_map, float* out, void* ws, void* stream);
+/* cc_flow_metrics_samples: the two compute_all_epes calls of train.py:748 for B samples whose ground truths differ in size, one
+ * row of out [B,8] per sample = [all, rigid, non-rigid EPE, outliers] with mask0, then the same with the inverted object map.
+ * flow_pool / obj_pool: fp32 device pools of flow_floats / obj_floats floats; sample r holds its (u, v, valid) planes [3,Hg,Wg]
+ * and its object map [Hg,Wg] at the offsets of row r of table (device int64 [N,4] = {flow offset, obj-map offset, Hg, Wg}, offsets
+ * in floats).  idx: device int32 [B], the table rows of this batch (any order, repeats allowed).  The geometry is read on the
+ * device; the host passes max_px, the largest Hg * Wg it may meet (1 .. 2^31 - 1), which sizes the grid and the workspace.
+ * rigid_pred, non_rigid_pred [B,2,Hp,Wp]; mask0 [B,1,Hm0,Wm0] (not inverted).
+ * Row b is bit for bit what cc_flow_metrics writes at B = 1 for gt = that sample's planes, the b-th slices of the predictions
+ * and of mask0, and mask1 = its object map with inv1 = 1.  A row whose table entry is outside the table or the pools, or larger
+ * than max_px, is NaN and nothing of it is read.
+ * acc_sums (device double [8]) / acc_count (device int64 [1]): both NULL, or a running meter: one workgroup adds the B rows to
+ * acc_sums in sample order (in fp64) and B to acc_count.  ws: cc_flow_metrics_samples_ws(B, max_px) bytes. */
+size_t cc_flow_metrics_samples_ws(int B, long max_px);
+int cc_flow_metrics_samples(const float* flow_pool, long flow_floats, const float* obj_pool, long obj_floats, const long* table, int N,
+                            const int* idx, int B, long max_px, const float* rigid_pred, const float* non_rigid_pred, int Hp, int Wp,
+                            const float* mask0, int Hm0, int Wm0, float thresh, float tau_px, float tau_rel, float* out,
+                            double* acc_sums, long* acc_count, void* ws, void* stream);
 /* cc_depth_errors: compute_errors (:432-467) of gt / pred [B,H,W] inside the crop box rows [y1,y2) x cols [x1,x2) (the whole image
  * for crop=False) -> out6 = [abs_diff, abs_rel, sq_rel, a1, a2, a3]: per sample valid = 0 < gt < 80, p = clamp(pred, 1e-3, 80)
  * scaled by median(gt) / median(p) (exact lower medians by radix select), six means; summed over samples in order, / B.
