@@ -4,6 +4,8 @@
 Everything heavy is a HIP kernel.  What is still stock ATen (tiny tensors, listed in DESIGN.md as "torch
 plumbing"): nearest upsampling + channel softmax of the (unused-by-training) occlusion head, torch.cat.
 """
+import ctypes
+
 import torch
 import torch.nn.functional as F
 
@@ -29,6 +31,122 @@ def _slice_or_c(t):
 
 def _ws(nbytes, ref):
     return torch.empty(max(int(nbytes) // 4, 4), device=ref.device, dtype=torch.float32)
+
+
+def _parr(ts):
+    """HOST array of device addresses (0 = null) for the *_group entry points; keep the returned object alive over the call."""
+    return (ctypes.c_long * len(ts))(*[(t.data_ptr() if t is not None else 0) for t in ts])
+
+
+def _addr(arr):
+    return ctypes.addressof(arr) if arr is not None else 0
+
+
+# ----------------------------------------------------------------------------- launchers
+# One function per entry-point family: the only place in cc_amd/ where the entry's name and argument list are written down.  A
+# launcher takes the tensors (lists for the group spellings; None = operand absent), reads the geometry off their shapes and the
+# batch strides off t.stride(0), asks for the workspace, fetches the weight images and calls the engine.  WHAT to launch (grouping,
+# uniform strides, epilogue form, targets, accumulate) is the caller's decision.
+def _conv_fwd(xs, ws, bs, rs, ys, stride, pad, act, act_a, act_b, single=False):
+    """y_k = act(conv2d(x_k, w_k) + b_k + r_k) for len(xs) same-shaped problems (bs holds None without biases, rs = None without
+    residuals) in one cc_conv2d_fwd_group call; single: the one-problem spelling cc_conv2d_fwd."""
+    E = engine()
+    B, Cin, IH, IW = xs[0].shape
+    Cout, _, R, S = ws[0].shape
+    OH, OW = ys[0].shape[2:]
+    geom = (B, Cin, IH, IW, Cout, R, S, stride, pad, OH, OW)
+    tail = (B, Cin, IH, IW, xs[0].stride(0), Cout, R, S, stride, pad, OH, OW, ys[0].stride(0), rs[0].stride(0) if rs else 0,
+            act, float(act_a), float(act_b), STREAM)
+    if single:
+        wsb = _ws(E.call("cc_conv2d_fwd_ws_bytes", *geom), xs[0])
+        E.call("cc_conv2d_fwd", xs[0], ws[0], bs[0], rs[0] if rs else None, ys[0], wsb, packs.get("fwd", ws[0], geom), *tail)
+        return
+    wsb = _ws(E.call("cc_conv2d_fwd_group_ws_bytes", len(xs), *geom), xs[0])
+    ax, aw, ab, ar, ay = _parr(xs), _parr(ws), _parr(bs), (_parr(rs) if rs else None), _parr(ys)
+    ap = _parr([packs.get("fwd", w, geom) for w in ws])
+    E.call("cc_conv2d_fwd_group", len(xs), _addr(ax), _addr(aw), _addr(ab), _addr(ar), _addr(ay), wsb, _addr(ap), *tail)
+
+
+def _conv_dgrad(gys, ws, bs, gxs, muls, adds, stride, pad, act, act_a, act_b, spelling="group"):
+    """The transposed-convolution arithmetic sum_k = conv_transpose2d(gy_k, w_k) -- the data gradient of conv2d, the forward of
+    ConvTranspose2d -- for len(gys) same-shaped problems, with the epilogue of the spelling:
+      "single" (cc_conv2d_dgrad)           gx = act(sum + b);
+      "group"  (cc_conv2d_dgrad_group)     gx_k = act(sum_k + b_k), or sum_k * act'(mul_k) with muls;
+      "add"    (cc_conv2d_dgrad_group_add) gx_k = (sum_k + add_k) * act'(mul_k), act(sum_k + add_k) without muls.
+    bs / muls / adds: None = operand absent."""
+    E = engine()
+    G = len(gys)
+    B, K, OH, OW = gys[0].shape
+    C, IH, IW = gxs[0].shape[1:]
+    R, S = ws[0].shape[2:]
+    geom = (B, K, OH, OW, C, R, S, stride, pad, IH, IW)
+    w_k_stride, w_c_stride = C * R * S, R * S
+    head = (B, K, OH, OW, gys[0].stride(0), C, R, S, stride, pad, IH, IW, gxs[0].stride(0))
+    tail = (w_k_stride, w_c_stride, act, float(act_a), float(act_b), STREAM)
+    if spelling == "single":
+        wsb = _ws(E.call("cc_conv2d_dgrad_ws_bytes", *geom), gys[0])
+        pk = packs.get("dgrad", ws[0], geom + (w_k_stride, w_c_stride))
+        E.call("cc_conv2d_dgrad", gys[0], ws[0], bs[0] if bs else None, gxs[0], wsb, pk, *head, *tail)
+        return
+    wsb = _ws(E.call("cc_conv2d_dgrad_group_ws_bytes", G, *geom), gys[0])
+    pks = [packs.get("dgrad", w, geom + (w_k_stride, w_c_stride)) for w in ws]
+    agy, aw, ab, agx, am, aa, ap = [(_parr(ts) if ts else None) for ts in (gys, ws, bs, gxs, muls, adds, pks)]
+    mul_bs = muls[0].stride(0) if muls else 0
+    if spelling == "add":
+        E.call("cc_conv2d_dgrad_group_add", G, _addr(agy), _addr(aw), _addr(agx), _addr(am), _addr(aa), wsb, _addr(ap), *head, mul_bs,
+               adds[0].stride(0) if adds else 0, *tail)
+    else:
+        E.call("cc_conv2d_dgrad_group", G, _addr(agy), _addr(aw), _addr(ab), _addr(agx), _addr(am), wsb, _addr(ap), *head, mul_bs, *tail)
+
+
+def _bn_train_fwd(x, weight, bias, running_mean, running_var, momentum, eps):
+    """-> (y, batch mean, batch 1/std) of training-mode BatchNorm2d; the running statistics are updated in place"""
+    E = engine()
+    B, C, H, W = x.shape
+    y = torch.empty_like(x)
+    mean = torch.empty(C, device=x.device, dtype=torch.float32)
+    invstd = torch.empty_like(mean)
+    E.call("cc_bn_train_fwd", x, weight, bias, running_mean, running_var, y, mean, invstd, _ws(E.call("cc_bn_ws_bytes", C), x),
+           B, C, H, W, float(momentum), float(eps), STREAM)
+    return y, mean, invstd
+
+
+def _bn_train_bwd(gy, x, weight, mean, invstd, gx, gw, gb, accumulate):
+    """gx; gw (+)= sum gy * xhat, gb (+)= sum gy (either may be None; accumulate: add into them)"""
+    E = engine()
+    B, C, H, W = x.shape
+    E.call("cc_bn_train_bwd", gy, x, weight, mean, invstd, gx, gw, gb, _ws(E.call("cc_bn_ws_bytes", C), x), B, C, H, W,
+           int(accumulate), STREAM)
+
+
+def _bn_eval_fwd(x, weight, bias, running_mean, running_var, y, eps, grad_only=0):
+    """y = eval-mode BatchNorm2d of x; grad_only: the input gradient of that map (x is the output gradient, bias None)"""
+    B, C, H, W = x.shape
+    engine().call("cc_bn_eval_fwd", x, weight, bias, running_mean, running_var, y, _ws(8 * C, x), B, C, H, W, float(eps), grad_only,
+                  STREAM)
+
+
+def _up2x_fwd(x, y, scale):
+    B, C, H, W = x.shape
+    engine().call("cc_upsample2x_fwd", x, y, B, C, H, W, x.stride(0), y.stride(0), float(scale), STREAM)
+
+
+def _up2x_bwd(gy, gx, scale, accumulate=0):
+    B, C, H, W = gx.shape
+    engine().call("cc_upsample2x_bwd", gy, gx, B, C, H, W, gy.stride(0), gx.stride(0), float(scale), int(accumulate), STREAM)
+
+
+def _corr9x9_fwd(a, b, out, inv, offset=0):
+    """the 81 channels of correlate(a, b) (permuted by inv) at channel `offset` of out, which may be a channel slice of a wider
+    buffer: the kernels address out[n, offset + ch] through the buffer's channel count"""
+    B, C, H, W = a.shape
+    engine().call("cc_corr9x9_fwd", a, b, out, inv, B, C, H, W, out.stride(0) // (H * W), offset, STREAM)
+
+
+def _corr9x9_bwd(g, a, b, ga, gb, inv, offset=0, accumulate=0):
+    """ga (+)=, gb = the gradients of _corr9x9_fwd (gb may be None); accumulate: add into ga"""
+    B, C, H, W = a.shape
+    engine().call("cc_corr9x9_bwd", g, a, b, ga, gb, inv, B, C, H, W, g.stride(0) // (H * W), offset, accumulate, STREAM)
 
 
 # ----------------------------------------------------------------------------- per-step weight prepack
@@ -63,7 +181,6 @@ class PackRegistry:
         return ent["buf"]
 
     def _register(self, key, kind, w, geom):
-        import ctypes
         E = engine()
         fn = "cc_conv2d_fwd_pack" if kind == "fwd" else "cc_conv2d_dgrad_pack"
         n = E.call(fn + "_floats", *geom)
@@ -245,7 +362,6 @@ class _WgradReduces:
         self.bias_jobs = []      # parked pure bias-gradient sums (cc_bias_grad_defer): one cc_bias_grad_table launch per 32
 
     def flush(self):
-        import ctypes
         if self.bias_jobs:
             arr = (ctypes.c_long * len(self.bias_jobs))(*self.bias_jobs)
             engine().call("cc_bias_grad_table", ctypes.addressof(arr), len(self.bias_jobs) // 12, STREAM)
@@ -264,7 +380,6 @@ class _WgradReduces:
 
     def park_bias(self, gy, gbias, B, C, H, W, gy_bs):
         """gbias += sum over (n, h, w) of gy, at the end of the stage (gy is kept alive until then)"""
-        import ctypes
         if gbias.data_ptr() in self.targets:
             self.flush()
         self.targets.add(gbias.data_ptr())
@@ -346,28 +461,29 @@ wgrad_queue = _PerStream(_WgradQueue)
 wgrad_reduces = _PerStream(_WgradReduces)
 
 
-def _act_bwd_bias(gys, ys, geffs, gbs, ref, B, C, H, W, gy_bs, act, act_a, act_b, accumulate):
-    """cc_act_bwd_bias_group for G = len(gys) <= 4 same-shaped problems (lists may hold None uniformly).  Inside a trainer stage
-    the second stage of bias gradients that accumulate into the optimizer's bucket is parked with the weight-gradient
-    reductions (one table launch per stage instead of one k_bias_reduce per call)."""
-    import ctypes
+def _act_bwd_bias(gys, ys, geffs, gbs, act, act_a, act_b, accumulate):
+    """geff_k = gy_k * act'(y_k), gb_k (+)= sum over (n, h, w) of geff_k: cc_act_bwd_bias_group for G = len(gys) <= 4 same-shaped
+    problems (ys / geffs / gbs may hold None uniformly; gys and ys are read through their batch strides).  Inside a trainer stage
+    the second stage of bias gradients that accumulate into the optimizer's bucket is parked with the weight-gradient reductions
+    (one table launch per stage instead of one k_bias_reduce per call); gys and gbs stay referenced until then."""
     E = engine()
     G = len(gys)
-    a1, a2, a3, a4 = _parr(gys), _parr(ys), _parr(geffs), _parr(gbs)
+    B, C, H, W = gys[0].shape
     has_y, has_ge, has_gb = ys[0] is not None, geffs[0] is not None, gbs[0] is not None
-    ws = _ws(E.call("cc_act_bwd_ws_bytes", C) * G, ref)
-    args = (G, _addr(a1), _addr(a2) if has_y else 0, _addr(a3) if has_ge else 0, _addr(a4) if has_gb else 0, ws, B, C, H, W,
-            gy_bs, C * H * W, C * H * W, act, act_a, act_b, int(accumulate))
+    a1, a2, a3, a4 = _parr(gys), _parr(ys) if has_y else None, _parr(geffs) if has_ge else None, _parr(gbs) if has_gb else None
+    ws = _ws(E.call("cc_act_bwd_ws_bytes", C) * G, gys[0])
+    args = (G, _addr(a1), _addr(a2), _addr(a3), _addr(a4), ws, B, C, H, W, gys[0].stride(0), ys[0].stride(0) if has_y else C * H * W,
+            C * H * W, act, act_a, act_b, int(accumulate))
     if has_gb and accumulate and wgrad_queue.enabled and not _dbg.no_wgrad_defer:
         ptrs = [t.data_ptr() for t in gbs]
-        if wgrad_reduces.targets.intersection(ptrs):
+        if wgrad_reduces.targets.intersection(ptrs) or len(set(ptrs)) != len(ptrs):     # two parked `gb +=` of one bias would race
             wgrad_reduces._cur().flush()       # (this stream's table only: the proxy's flush() would launch every stream's)
         wgrad_reduces.targets.update(ptrs)
         red = (ctypes.c_long * (16 * G))()
         nred = ctypes.c_int(0)
         E.call("cc_act_bwd_bias_group_defer", *args, ctypes.addressof(red), G, ctypes.addressof(nred), STREAM)
         if nred.value:
-            wgrad_reduces.keep.append((ws, gbs))
+            wgrad_reduces.keep.append((ws, gbs, gys))
             wgrad_reduces.desc.extend(red[:16 * nred.value])
     else:
         E.call("cc_act_bwd_bias_group", *args, STREAM)
@@ -406,7 +522,6 @@ def _zeros64(ref):
 def _wgrad_group(a_list, x_list, gw_list, ref, B, M, AH, AW, a_bs, Cin, IH, IW, x_bs, R, S, si, pad, o_sm, o_sc, accumulate):
     """cc_conv2d_wgrad_group for G = len(a_list) <= 4 same-shaped problems.  Inside a trainer stage (queue enabled) and when the
     results go straight into the optimizer's gradient bucket (accumulate), the reductions are parked (see _WgradReduces)."""
-    import ctypes
     E = engine()
     G = len(a_list)
     per = _wgrad_ws_bytes(B, M, AH, AW, Cin, R, S, si)
@@ -437,7 +552,6 @@ def _wgrad_group(a_list, x_list, gw_list, ref, B, M, AH, AW, a_bs, Cin, IH, IW, 
 def _wgrad_list(items):
     """items: [(a_list, x_list, gw_list, (B, M, AH, AW, a_bs, Cin, IH, IW, x_bs, R, S, si, pad, o_sm, o_sc))], gradients accumulated into
     the optimizer's bucket, reductions parked (the queue is enabled): one cc_conv2d_wgrad_list call."""
-    import ctypes
     E = engine()
     if _dbg.no_wgrad_defer or not wgrad_queue.enabled or _dbg.no_wgrad_list:
         for a_list, x_list, gw_list, geo in items:
@@ -478,167 +592,78 @@ def _wgrad_list(items):
     run()
 
 
-# ----------------------------------------------------------------------------- convolution
-class _Conv2dFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, w, bias, res, stride, pad, act, act_a, act_b, pre_act=0, pre_b=0.0, defer=False):
-        x, w = _c(x), _c(w)
-        B, Cin, IH, IW = x.shape
-        Cout, _, R, S = w.shape
-        OH = (IH + 2 * pad - R) // stride + 1
-        OW = (IW + 2 * pad - S) // stride + 1
-        y = torch.empty(B, Cout, OH, OW, device=x.device, dtype=torch.float32)
-        bias_c = None if bias is None else _c(bias)
-        res_c = None if res is None else _c(res)
-        E = engine()
-        ws = _ws(E.call("cc_conv2d_fwd_ws_bytes", B, Cin, IH, IW, Cout, R, S, stride, pad, OH, OW), x)
-        pk = packs.get("fwd", w, (B, Cin, IH, IW, Cout, R, S, stride, pad, OH, OW))
-        E.call("cc_conv2d_fwd", x, w, bias_c, res_c, y, ws, pk, B, Cin, IH, IW, Cin * IH * IW, Cout, R, S, stride, pad,
-               OH, OW, Cout * OH * OW, Cout * OH * OW, act, act_a, act_b, STREAM)
-        # defer: the consumers of y (convolutions called with pre_act = this activation) apply act'(y) in their data-gradient
-        # epilogue, so the gradient arriving here is already w.r.t. the pre-activation (see _ConvGroupFn)
-        ctx.save_for_backward(x, w, y if (act != 0 and not defer) else None)
-        ctx.cfg = (stride, pad, act if not defer else 0, act_a, act_b, bias is not None, res is not None)
-        ctx.pre = (pre_act, pre_b)
-        ctx.bias_ptr = bias_c.data_ptr() if bias_c is not None else 0
-        return y
-
-    @staticmethod
-    def backward(ctx, gy):
-        x, w, y = ctx.saved_tensors
-        stride, pad, act, act_a, act_b, has_bias, has_res = ctx.cfg
-        pre_act, pre_b = ctx.pre
-        E = engine()
-        # a layer with an activation passes gy through cc_act_bwd_bias first: that call reads a concat-gradient slice in place
-        gy, gy_bs = _slice_or_c(gy) if act != 0 else (_c(gy), 0)
-        B, Cin, IH, IW = x.shape
-        Cout, _, R, S = w.shape
-        OH, OW = gy.shape[2], gy.shape[3]
-        need = ctx.needs_input_grad
-        gbias, bsink = None, None
-        if has_bias and need[2]:
-            bsink = grad_sinks.get(ctx.bias_ptr) if grad_sinks else None
-            gbias = bsink if bsink is not None else torch.empty(Cout, device=x.device, dtype=torch.float32)
-        if act != 0 or gbias is not None:
-            geff = torch.empty(gy.shape, device=gy.device, dtype=torch.float32) if act != 0 else None
-            _act_bwd_bias([gy], [y if act != 0 else None], [geff], [gbias], x, B, Cout, OH, OW,
-                          gy_bs if act != 0 else Cout * OH * OW, act, act_a, act_b, bsink is not None)
-            if geff is not None:
-                gy = geff
-        if bsink is not None:
-            gbias = None
-        gx = gw = None
-        if need[0]:
-            gx = torch.empty_like(x)
-            ws = _ws(E.call("cc_conv2d_dgrad_ws_bytes", B, Cout, OH, OW, Cin, R, S, stride, pad, IH, IW), x)
-            pk = packs.get("dgrad", w, (B, Cout, OH, OW, Cin, R, S, stride, pad, IH, IW, Cin * R * S, R * S))
-            if pre_act:       # gradient w.r.t. the producer's pre-activation: act'(x) multiplied in the epilogue
-                a1, a2, a3, a4, a5 = _parr([gy]), _parr([w]), _parr([gx]), _parr([x]), _parr([pk])
-                E.call("cc_conv2d_dgrad_group", 1, _addr(a1), _addr(a2), 0, _addr(a3), _addr(a4), ws, _addr(a5), B, Cout, OH, OW,
-                       Cout * OH * OW, Cin, R, S, stride, pad, IH, IW, Cin * IH * IW, Cin * IH * IW, Cin * R * S, R * S, pre_act, 1.0,
-                       pre_b, STREAM)
-            else:
-                E.call("cc_conv2d_dgrad", gy, w, None, gx, ws, pk, B, Cout, OH, OW, Cout * OH * OW, Cin, R, S, stride, pad, IH, IW,
-                       Cin * IH * IW, Cin * R * S, R * S, 0, 1.0, 0.0, STREAM)
-        if need[1]:
-            wsink = _sink(w)
-            if wsink is not None and wgrad_queue.enabled:
-                wgrad_queue.push((B, Cout, OH, OW, Cin, IH, IW, R, S, stride, pad, Cin * R * S, R * S, Cout * OH * OW, Cin * IH * IW),
-                                 gy, x, wsink)
-            else:
-                gw = wsink if wsink is not None else torch.empty_like(w)
-                _wgrad_group([gy], [x], [gw], x, B, Cout, OH, OW, Cout * OH * OW, Cin, IH, IW, Cin * IH * IW, R, S, stride, pad,
-                             Cin * R * S, R * S, int(wsink is not None))
-                if wsink is not None:
-                    gw = None
-        gres = gy if (has_res and need[3]) else None
-        return gx, gw, gbias, gres, None, None, None, None, None, None, None, None
-
-
-# ----------------------------------------------------------------------------- grouped convolution (parallel branches)
-def _parr(ts):
-    """HOST array of device addresses (0 = null) for the *_group entry points; keep the returned object alive over the call."""
-    import ctypes
-    return (ctypes.c_long * len(ts))(*[(t.data_ptr() if t is not None else 0) for t in ts])
-
-
-def _addr(arr):
-    import ctypes
-    return ctypes.addressof(arr)
-
-
+# ----------------------------------------------------------------------------- convolution (G same-shaped problems per launch)
 class _ConvGroupFn(torch.autograd.Function):
-    """G same-shaped convolutions (with their own inputs, weights, biases) as ONE launch per pass (cc_conv2d_*_group).
+    """G same-shaped convolutions (with their own inputs, weights, biases, residuals) as ONE launch per pass (cc_conv2d_*_group);
+    ops.conv2d is the case G = 1.
 
-    meta = (G, stride, pad, act, act_a, act_b, has_bias, pre_act, pre_b, defer)
+    meta = (G, stride, pad, act, act_a, act_b, has_bias, has_res, pre_act, pre_b, defer)
       defer   : this layer's outputs feed ONLY convolutions called with pre_act = this activation; those multiply act'(y)
                 into their data-gradient epilogue, so the gradient arriving here is already w.r.t. the pre-activation
                 (no separate activation-backward pass over gy and y);
       pre_act : activation (code, slope pre_b) of the deferring layer that produced xs.
-    tensors = xs + weights (+ biases)."""
+    tensors = xs + weights (+ biases) (+ residuals)."""
 
     @staticmethod
     def forward(ctx, meta, *tensors):
-        G, stride, pad, act, act_a, act_b, has_bias, pre_act, pre_b, defer = meta
+        G, stride, pad, act, act_a, act_b, has_bias, has_res, pre_act, pre_b, defer = meta
         xs = [_c(t) for t in tensors[:G]]
         ws = [_c(t) for t in tensors[G:2 * G]]
         bs = [_c(t) for t in tensors[2 * G:3 * G]] if has_bias else [None] * G
+        rs = [_c(t) for t in tensors[len(tensors) - G:]] if has_res else None
         B, Cin, IH, IW = xs[0].shape
         Cout, _, R, S = ws[0].shape
         OH = (IH + 2 * pad - R) // stride + 1
         OW = (IW + 2 * pad - S) // stride + 1
-        E = engine()
         ys = [torch.empty(B, Cout, OH, OW, device=xs[0].device, dtype=torch.float32) for _ in range(G)]
-        geom = (B, Cin, IH, IW, Cout, R, S, stride, pad, OH, OW)
-        wsb = _ws(E.call("cc_conv2d_fwd_group_ws_bytes", G, *geom), xs[0])
-        pks = [packs.get("fwd", w, geom) for w in ws]
-        ax, aw, ab, ay, ap = _parr(xs), _parr(ws), _parr(bs), _parr(ys), _parr(pks)
-        E.call("cc_conv2d_fwd_group", G, _addr(ax), _addr(aw), _addr(ab), 0, _addr(ay), wsb, _addr(ap), B, Cin, IH, IW,
-               Cin * IH * IW, Cout, R, S, stride, pad, OH, OW, Cout * OH * OW, 0, act, act_a, act_b, STREAM)
+        _conv_fwd(xs, ws, bs, rs, ys, stride, pad, act, act_a, act_b)
         ctx.set_materialize_grads(False)
-        ctx.save_for_backward(*xs, *ws, *([y for y in ys] if (act != 0 and not defer) else []))
+        ctx.save_for_backward(*xs, *ws, *(ys if (act != 0 and not defer) else []))
         ctx.meta = meta
         ctx.bias_ptrs = [b.data_ptr() if b is not None else 0 for b in bs]
         return tuple(ys)
 
     @staticmethod
     def backward(ctx, *gys):
-        G, stride, pad, act, act_a, act_b, has_bias, pre_act, pre_b, defer = ctx.meta
+        G, stride, pad, act, act_a, act_b, has_bias, has_res, pre_act, pre_b, defer = ctx.meta
         saved = ctx.saved_tensors
         xs, ws = saved[:G], saved[G:2 * G]
         ys = saved[2 * G:] if len(saved) > 2 * G else [None] * G
         need = ctx.needs_input_grad
         E = engine()
-        B, Cin, IH, IW = xs[0].shape
-        Cout, _, R, S = ws[0].shape
+        Cout = ws[0].shape[0]
         live = [k for k in range(G) if gys[k] is not None]          # branches nobody differentiates (occlusion decoders) drop out
-        gx_out, gw_out, gb_out = [None] * G, [None] * G, [None] * G
+        gx_out, gw_out, gb_out, gr_out = [None] * G, [None] * G, [None] * G, [None] * G
+
+        def result():
+            return (None,) + tuple(gx_out + gw_out + (gb_out if has_bias else []) + (gr_out if has_res else []))
         if not live:
-            return (None,) + tuple(gx_out + gw_out + (gb_out if has_bias else []))
-        gy = {k: _c(gys[k]) for k in live}
-        OH, OW = gy[live[0]].shape[2], gy[live[0]].shape[3]
-        n = len(live)
+            return result()
         dev = xs[0].device
         # ---- activation backward (unless deferred to the consumers' data-gradient epilogues) + bias gradients
         want_b = [k for k in live if has_bias and need[1 + 2 * G + k]]
         bsinks = {k: (grad_sinks.get(ctx.bias_ptrs[k]) if grad_sinks else None) for k in want_b}
         all_sink = bool(want_b) and all(v is not None for v in bsinks.values())
         do_act = act != 0 and not defer
+        # the activation pass reads a concat-gradient slice in place; every other consumer of gy wants it contiguous
+        gy = {k: (_slice_or_c(gys[k])[0] if do_act else _c(gys[k])) for k in live}
         if do_act or want_b:
             idx = live if do_act else want_b
-            geff = {k: torch.empty_like(gy[k]) for k in idx} if do_act else {}
+            geff = {k: torch.empty(gy[k].shape, device=dev, dtype=torch.float32) for k in idx} if do_act else {}
             gb = {}
             for k in idx:
                 if k in want_b:
                     gb[k] = bsinks[k] if all_sink else torch.empty(Cout, device=dev, dtype=torch.float32)
             # bias gradients are wanted for all of idx or for none of it (one network: all parameters trainable or all frozen)
             with_b = len(gb) == len(idx)
-            for c0 in range(0, len(idx), 4):
-                ch = idx[c0:c0 + 4]
+            # one launch per four members whose gradients share a batch stride, else one by one (as the tape does)
+            step = 4 if len({gy[k].stride(0) for k in idx}) == 1 else 1
+            for c0 in range(0, len(idx), step):
+                ch = idx[c0:c0 + step]
                 _act_bwd_bias([gy[k] for k in ch], [ys[k] if do_act else None for k in ch], [geff.get(k) for k in ch],
-                              [gb.get(k) if with_b else None for k in ch], xs[0], B, Cout, OH, OW, Cout * OH * OW,
-                              act if do_act else 0, act_a, act_b, all_sink)
+                              [gb.get(k) if with_b else None for k in ch], act if do_act else 0, act_a, act_b, all_sink)
             if not with_b and gb:          # mixed case: the remaining bias gradients one by one
+                B, _, OH, OW = gy[live[0]].shape
                 for k in gb:
                     E.call("cc_act_bwd_bias", geff.get(k, gy[k]), None, None, gb[k], _ws(E.call("cc_act_bwd_ws_bytes", Cout), xs[0]),
                            B, Cout, OH, OW, Cout * OH * OW, 0, 0, 0, 1.0, 0.0, int(all_sink), STREAM)
@@ -647,33 +672,40 @@ class _ConvGroupFn(torch.autograd.Function):
             if not all_sink:
                 for k in gb:
                     gb_out[k] = gb[k]
+        if has_res:                        # the residual's gradient is the gradient w.r.t. the pre-activation itself
+            for k in live:
+                if need[len(need) - G + k]:
+                    gr_out[k] = gy[k]
         # ---- data gradients
         dx = [k for k in live if need[1 + k]]
         if dx:
-            geom = (B, Cout, OH, OW, Cin, R, S, stride, pad, IH, IW)
             for k in dx:
                 gx_out[k] = torch.empty_like(xs[k])
-            wsb = _ws(E.call("cc_conv2d_dgrad_group_ws_bytes", len(dx), *geom), xs[0])
-            pks = [packs.get("dgrad", ws[k], geom + (Cin * R * S, R * S)) for k in dx]
-            a1, a2, a3 = _parr([gy[k] for k in dx]), _parr([ws[k] for k in dx]), _parr([gx_out[k] for k in dx])
-            a4, a5 = _parr([xs[k] if pre_act else None for k in dx]), _parr(pks)
-            E.call("cc_conv2d_dgrad_group", len(dx), _addr(a1), _addr(a2), 0, _addr(a3), _addr(a4) if pre_act else 0, wsb, _addr(a5),
-                   B, Cout, OH, OW, Cout * OH * OW, Cin, R, S, stride, pad, IH, IW, Cin * IH * IW, Cin * IH * IW, Cin * R * S, R * S,
-                   pre_act, 1.0, pre_b, STREAM)
+            # pre_act: gradient w.r.t. the producer's pre-activation, act'(x) multiplied in the epilogue
+            _conv_dgrad([gy[k] for k in dx], [ws[k] for k in dx], None, [gx_out[k] for k in dx], [xs[k] for k in dx] if pre_act else None,
+                        None, stride, pad, pre_act, 1.0, pre_b)
         # ---- weight gradients
         dw = [k for k in live if need[1 + G + k]]
         if dw:
+            R, S = ws[0].shape[2:]
+            B, Cin, IH, IW = xs[0].shape
+            OH, OW = gy[live[0]].shape[2:]
             wsinks = {k: _sink(ws[k]) for k in dw}
             all_wsink = all(v is not None for v in wsinks.values())
-            gw = {k: (wsinks[k] if all_wsink else torch.empty_like(ws[k])) for k in dw}
-            for c0 in range(0, len(dw), 4):
-                ch = dw[c0:c0 + 4]
-                _wgrad_group([gy[k] for k in ch], [xs[k] for k in ch], [gw[k] for k in ch], xs[0], B, Cout, OH, OW, Cout * OH * OW,
-                             Cin, IH, IW, Cin * IH * IW, R, S, stride, pad, Cin * R * S, R * S, int(all_wsink))
-            if not all_wsink:
+            a_bs, x_bs = Cout * OH * OW, Cin * IH * IW
+            if all_wsink and wgrad_queue.enabled:       # parked with their shape-mates (nothing is returned to autograd)
                 for k in dw:
-                    gw_out[k] = gw[k]
-        return (None,) + tuple(gx_out + gw_out + (gb_out if has_bias else []))
+                    wgrad_queue.push((B, Cout, OH, OW, Cin, IH, IW, R, S, stride, pad, Cin * R * S, R * S, a_bs, x_bs), gy[k], xs[k], wsinks[k])
+            else:
+                gw = {k: (wsinks[k] if all_wsink else torch.empty_like(ws[k])) for k in dw}
+                for c0 in range(0, len(dw), 4):
+                    ch = dw[c0:c0 + 4]
+                    _wgrad_group([gy[k] for k in ch], [xs[k] for k in ch], [gw[k] for k in ch], xs[0], B, Cout, OH, OW, a_bs, Cin, IH, IW,
+                                 x_bs, R, S, stride, pad, Cin * R * S, R * S, int(all_wsink))
+                if not all_wsink:
+                    for k in dw:
+                        gw_out[k] = gw[k]
+        return result()
 
 
 def conv2d_group(xs, weights, biases=None, stride=1, padding=0, act=None, slope=0.0, pre_act=None, pre_slope=0.0, defer=False):
@@ -681,7 +713,7 @@ def conv2d_group(xs, weights, biases=None, stride=1, padding=0, act=None, slope=
     See _ConvGroupFn for pre_act / defer (activation backward fused into the consumer's data-gradient epilogue)."""
     G = len(xs)
     has_bias = biases is not None and biases[0] is not None
-    meta = (G, int(stride), int(padding), ACT[act], 1.0, float(slope), has_bias, ACT[pre_act], float(pre_slope), bool(defer))
+    meta = (G, int(stride), int(padding), ACT[act], 1.0, float(slope), has_bias, False, ACT[pre_act], float(pre_slope), bool(defer))
     out = _ConvGroupFn.apply(meta, *xs, *weights, *(biases if has_bias else ()))
     return list(out)
 
@@ -692,8 +724,9 @@ def conv2d(x, w, bias=None, stride=1, padding=0, act=None, residual=None, act_a=
     act='lrelu': act_b is the negative slope (0 -> the 0.2 of Back2Future).
     defer / pre_act: activation backward of a layer whose output feeds ONLY convolutions is applied by those consumers'
     data-gradient epilogue (producer: defer=True; every consumer: pre_act=<the producer's activation>)."""
-    return _Conv2dFn.apply(x, w, bias, residual, int(stride), int(padding), ACT[act], float(act_a), float(act_b),
-                           ACT[pre_act], float(pre_slope), bool(defer))
+    meta = (1, int(stride), int(padding), ACT[act], float(act_a), float(act_b), bias is not None, residual is not None, ACT[pre_act],
+            float(pre_slope), bool(defer))
+    return _ConvGroupFn.apply(meta, x, w, *(t for t in (bias, residual) if t is not None))[0]
 
 
 class _ConvT2dFn(torch.autograd.Function):
@@ -706,12 +739,8 @@ class _ConvT2dFn(torch.autograd.Function):
         OW = (IW - 1) * stride - 2 * pad + S + out_pad
         y = torch.empty(B, Cout, OH, OW, device=x.device, dtype=torch.float32)
         bias_c = None if bias is None else _c(bias)
-        # ConvTranspose2d forward == the transposed-conv arithmetic of cc_conv2d_dgrad with K = Cin, C = Cout
-        E = engine()
-        ws = _ws(E.call("cc_conv2d_dgrad_ws_bytes", B, Cin, IH, IW, Cout, R, S, stride, pad, OH, OW), x)
-        pk = packs.get("dgrad", w, (B, Cin, IH, IW, Cout, R, S, stride, pad, OH, OW, Cout * R * S, R * S))
-        E.call("cc_conv2d_dgrad", x, w, bias_c, y, ws, pk, B, Cin, IH, IW, Cin * IH * IW, Cout, R, S, stride, pad, OH, OW,
-               Cout * OH * OW, Cout * R * S, R * S, act, 1.0, float(act_b), STREAM)
+        # ConvTranspose2d forward == the transposed-conv arithmetic of the data gradient with K = Cin, C = Cout
+        _conv_dgrad([x], [w], [bias_c], [y], None, None, stride, pad, act, 1.0, act_b, "single")
         ctx.save_for_backward(x, w, y if act != 0 else None)
         ctx.cfg = (stride, pad, act, bias is not None)
         ctx.act_b = float(act_b)
@@ -722,8 +751,8 @@ class _ConvT2dFn(torch.autograd.Function):
     def backward(ctx, gy):
         x, w, y = ctx.saved_tensors
         stride, pad, act, has_bias = ctx.cfg
-        E = engine()
-        gy, gy_bs = _slice_or_c(gy) if act != 0 else (_c(gy), 0)       # see _Conv2dFn.backward
+        # a layer with an activation passes gy through the activation backward first: that call reads a concat-gradient slice in place
+        gy = _slice_or_c(gy)[0] if act != 0 else _c(gy)
         B, Cin, IH, IW = x.shape
         _, Cout, R, S = w.shape
         OH, OW = gy.shape[2], gy.shape[3]
@@ -734,8 +763,7 @@ class _ConvT2dFn(torch.autograd.Function):
             gbias = bsink if bsink is not None else torch.empty(Cout, device=x.device, dtype=torch.float32)
         if act != 0 or gbias is not None:
             geff = torch.empty(gy.shape, device=gy.device, dtype=torch.float32) if act != 0 else None
-            _act_bwd_bias([gy], [y if act != 0 else None], [geff], [gbias], x, B, Cout, OH, OW,
-                          gy_bs if act != 0 else Cout * OH * OW, act, 1.0, ctx.act_b, bsink is not None)
+            _act_bwd_bias([gy], [y if act != 0 else None], [geff], [gbias], act, 1.0, ctx.act_b, bsink is not None)
             if geff is not None:
                 gy = geff
         if bsink is not None:
@@ -744,10 +772,7 @@ class _ConvT2dFn(torch.autograd.Function):
         if need[0]:
             # d/dx of a transposed conv is a plain strided conv of gy; the [Cin,Cout,R,S] weight IS its [M,C,R,S] weight
             gx = torch.empty_like(x)
-            ws = _ws(E.call("cc_conv2d_fwd_ws_bytes", B, Cout, OH, OW, Cin, R, S, stride, pad, IH, IW), x)
-            pk = packs.get("fwd", w, (B, Cout, OH, OW, Cin, R, S, stride, pad, IH, IW))
-            E.call("cc_conv2d_fwd", gy, w, None, None, gx, ws, pk, B, Cout, OH, OW, Cout * OH * OW, Cin, R, S, stride, pad, IH, IW,
-                   Cin * IH * IW, 0, 0, 1.0, 0.0, STREAM)
+            _conv_fwd([gy], [w], [None], None, [gx], stride, pad, 0, 1.0, 0.0, single=True)
         if need[1]:
             wsink = _sink(w)
             gw = wsink if wsink is not None else torch.empty_like(w)
@@ -770,13 +795,7 @@ class _BNTrainFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, running_mean, running_var, momentum, eps):
         x = _c(x)
-        B, C, H, W = x.shape
-        E = engine()
-        y = torch.empty_like(x)
-        mean = torch.empty(C, device=x.device, dtype=torch.float32)
-        invstd = torch.empty_like(mean)
-        E.call("cc_bn_train_fwd", x, weight, bias, running_mean, running_var, y, mean, invstd,
-               _ws(E.call("cc_bn_ws_bytes", C), x), B, C, H, W, float(momentum), float(eps), STREAM)
+        y, mean, invstd = _bn_train_fwd(x, weight, bias, running_mean, running_var, momentum, eps)
         ctx.save_for_backward(x, weight, mean, invstd)
         ctx.ptrs = (weight.data_ptr() if weight is not None else 0, bias.data_ptr() if bias is not None else 0,
                     bias is not None)
@@ -787,8 +806,7 @@ class _BNTrainFn(torch.autograd.Function):
         x, weight, mean, invstd = ctx.saved_tensors
         wptr, bptr, has_bias = ctx.ptrs
         gy = _c(gy)
-        B, C, H, W = x.shape
-        E = engine()
+        C = x.shape[1]
         need = ctx.needs_input_grad
         gx = torch.empty_like(x)
         wsink = grad_sinks.get(wptr) if (grad_sinks and weight is not None and need[1]) else None
@@ -799,8 +817,7 @@ class _BNTrainFn(torch.autograd.Function):
         else:
             gw = torch.empty(C, device=x.device, dtype=torch.float32) if (weight is not None and need[1]) else None
             gb = torch.empty(C, device=x.device, dtype=torch.float32) if (has_bias and need[2]) else None
-        E.call("cc_bn_train_bwd", gy, x, weight, mean, invstd, gx, gw, gb, _ws(E.call("cc_bn_ws_bytes", C), x), B, C, H, W,
-               int(sink), STREAM)
+        _bn_train_bwd(gy, x, weight, mean, invstd, gx, gw, gb, sink)
         if sink:
             gw = gb = None
         return gx, gw, gb, None, None, None, None
@@ -812,10 +829,8 @@ class _BNEvalFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, running_mean, running_var, eps):
         x = _c(x)
-        B, C, H, W = x.shape
         y = torch.empty_like(x)
-        engine().call("cc_bn_eval_fwd", x, weight, bias, running_mean, running_var, y, _ws(8 * C, x), B, C, H, W, float(eps), 0,
-                      STREAM)
+        _bn_eval_fwd(x, weight, bias, running_mean, running_var, y, eps)
         need_affine = (weight is not None and weight.requires_grad) or (bias is not None and bias.requires_grad)
         ctx.save_for_backward(weight, running_mean, running_var, x if need_affine else None)
         ctx.eps = float(eps)
@@ -825,12 +840,10 @@ class _BNEvalFn(torch.autograd.Function):
     def backward(ctx, gy):
         weight, running_mean, running_var, x = ctx.saved_tensors
         gy = _c(gy)
-        B, C, H, W = gy.shape
         gx = None
         if ctx.needs_input_grad[0]:
             gx = torch.empty_like(gy)
-            engine().call("cc_bn_eval_fwd", gy, weight, None, running_mean, running_var, gx, _ws(8 * C, gy), B, C, H, W, ctx.eps, 1,
-                          STREAM)
+            _bn_eval_fwd(gy, weight, None, running_mean, running_var, gx, ctx.eps, grad_only=1)
         gw, gb = bn_eval_affine_grads(gy, x, running_mean, running_var, ctx.eps, ctx.needs_input_grad[1], ctx.needs_input_grad[2])
         return gx, gw, gb, None, None, None
 
@@ -874,16 +887,16 @@ class _Up2xFn(torch.autograd.Function):
         x = _c(x)
         B, C, H, W = x.shape
         y = torch.empty(B, C, 2 * H, 2 * W, device=x.device, dtype=torch.float32)
-        engine().call("cc_upsample2x_fwd", x, y, B, C, H, W, C * H * W, 4 * C * H * W, float(scale), STREAM)
+        _up2x_fwd(x, y, scale)
         ctx.geom = (B, C, H, W, float(scale))
         return y
 
     @staticmethod
     def backward(ctx, gy):
         B, C, H, W, scale = ctx.geom
-        gy, gy_bs = _slice_or_c(gy)
+        gy = _slice_or_c(gy)[0]
         gx = torch.empty(B, C, H, W, device=gy.device, dtype=torch.float32)
-        engine().call("cc_upsample2x_bwd", gy, gx, B, C, H, W, gy_bs, C * H * W, scale, 0, STREAM)
+        _up2x_bwd(gy, gx, scale)
         return gx, None
 
 
@@ -916,9 +929,8 @@ class _CorrPairFn(torch.autograd.Function):
         a, b, c = _c(a), _c(b), _c(c)
         B, C, H, W = a.shape
         out = torch.empty(B, 162, H, W, device=a.device, dtype=torch.float32)
-        E = engine()
-        E.call("cc_corr9x9_fwd", a, b, out, inv_b, B, C, H, W, 162, 0, STREAM)
-        E.call("cc_corr9x9_fwd", a, c, out, inv_c, B, C, H, W, 162, 81, STREAM)
+        _corr9x9_fwd(a, b, out, inv_b, 0)
+        _corr9x9_fwd(a, c, out, inv_c, 81)
         ctx.save_for_backward(a, b, c, inv_b, inv_c)
         return out
 
@@ -926,13 +938,11 @@ class _CorrPairFn(torch.autograd.Function):
     def backward(ctx, g):
         a, b, c, inv_b, inv_c = ctx.saved_tensors
         g = _c(g)
-        B, C, H, W = a.shape
-        E = engine()
         ga = torch.empty_like(a)
         gb = torch.empty_like(b) if ctx.needs_input_grad[1] else None
         gc = torch.empty_like(c) if ctx.needs_input_grad[2] else None
-        E.call("cc_corr9x9_bwd", g, a, b, ga, gb, inv_b, B, C, H, W, 162, 0, 0, STREAM)
-        E.call("cc_corr9x9_bwd", g, a, c, ga, gc, inv_c, B, C, H, W, 162, 81, 1, STREAM)
+        _corr9x9_bwd(g, a, b, ga, gb, inv_b, 0, 0)
+        _corr9x9_bwd(g, a, c, ga, gc, inv_c, 81, 1)
         return ga, gb, gc, None, None
 
 
@@ -951,16 +961,15 @@ class _CorrFn(torch.autograd.Function):
     def forward(ctx, a, b):
         B, C, H, W = a.shape
         out = torch.empty(B, 81, H, W, device=a.device, dtype=torch.float32)
-        engine().call("cc_corr9x9_fwd", a, b, out, None, B, C, H, W, 81, 0, STREAM)
+        _corr9x9_fwd(a, b, out, None)
         ctx.save_for_backward(a, b)
         return out
 
     @staticmethod
     def backward(ctx, g):
         a, b = ctx.saved_tensors
-        B, C, H, W = a.shape
         ga, gb = torch.empty_like(a), torch.empty_like(b)
-        engine().call("cc_corr9x9_bwd", _c(g), a, b, ga, gb, None, B, C, H, W, 81, 0, 0, STREAM)
+        _corr9x9_bwd(_c(g), a, b, ga, gb, None)
         return ga, gb
 
 

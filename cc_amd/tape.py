@@ -338,26 +338,7 @@ class Tape:
             return out
         for c0 in range(0, G, 4):
             sl = slice(c0, c0 + 4)
-            ops_gys, ops_ys, ops_ge, ops_gb = gs[sl], (ys[sl] if act != 0 else [None] * len(gs[sl])), geffs[sl], gbs[sl]
-            n = len(ops_gys)
-            a1, a2, a3, a4 = ops._parr(ops_gys), ops._parr(ops_ys), ops._parr(ops_ge), ops._parr(ops_gb)
-            ws = ops._ws(self.E.call("cc_act_bwd_ws_bytes", C) * n, ref)
-            args = (n, ops._addr(a1), ops._addr(a2) if act != 0 else 0, ops._addr(a3) if act != 0 else 0,
-                    ops._addr(a4) if want_b else 0, ws, B, C, H, W, gy_bs, _bs(ops_ys[0]) if act != 0 else C * H * W, C * H * W,
-                    act, act_a, act_b, int(acc))
-            if want_b and acc and ops.wgrad_queue.enabled and not ops._dbg.no_wgrad_defer:
-                ptrs = [t.data_ptr() for t in ops_gb]
-                if ops.wgrad_reduces.targets.intersection(ptrs) or len(set(ptrs)) != len(ptrs):
-                    ops.wgrad_reduces._cur().flush()
-                ops.wgrad_reduces.targets.update(ptrs)
-                red = (ctypes.c_long * (16 * n))()
-                nred = ctypes.c_int(0)
-                self.E.call("cc_act_bwd_bias_group_defer", *args, ctypes.addressof(red), n, ctypes.addressof(nred), STREAM)
-                if nred.value:
-                    ops.wgrad_reduces.keep.append((ws, ops_gb, ops_gys))
-                    ops.wgrad_reduces.desc.extend(red[:16 * nred.value])
-            else:
-                self.E.call("cc_act_bwd_bias_group", *args, STREAM)
+            ops._act_bwd_bias(gs[sl], ys[sl] if act != 0 else [None] * len(gs[sl]), geffs[sl], gbs[sl], act, act_a, act_b, acc)
         return geffs if act != 0 else list(gs)
 
     # ------------------------------------------------------------------ weight gradients
@@ -391,7 +372,6 @@ class Tape:
     def conv_group(self, xs, ws_, bs, stride, pad, act=None, act_a=1.0, act_b=0.0, residuals=None, outs=None):
         """[act(conv2d(x_k, w_k) + b_k + r_k)]: nn.Conv2d with the activation (and a residual add) in the epilogue.
         outs: optional destination views (channel slices of concat buffers)."""
-        E = self.E
         G = len(xs)
         act = ACT[act] if not isinstance(act, int) else act
         has_bias = bs is not None and bs[0] is not None
@@ -405,23 +385,9 @@ class Tape:
         rs = [r.t for r in residuals] if residuals is not None else None
         res_bs = _bs(rs[0]) if rs is not None else 0
         uniform = all(_bs(x.t) == x_bs for x in xs) and all(_bs(y) == y_bs for y in ys) and (rs is None or all(_bs(r) == res_bs for r in rs))
-        geom = (B, Cin, IH, IW, Cout, R, S, stride, pad, OH, OW)
-
-        def launch(idx):
-            n = len(idx)
-            wsb = ops._ws(E.call("cc_conv2d_fwd_group_ws_bytes", n, *geom), xs[0].t)
-            pks = [ops.packs.get("fwd", ws_[k], geom) for k in idx]
-            ax, aw, ab = ops._parr([xs[k].t for k in idx]), ops._parr([ws_[k] for k in idx]), ops._parr([bs[k] if has_bias else None for k in idx])
-            ar = ops._parr([rs[k] for k in idx]) if rs is not None else None
-            ay, ap = ops._parr([ys[k] for k in idx]), ops._parr(pks)
-            E.call("cc_conv2d_fwd_group", n, ops._addr(ax), ops._addr(aw), ops._addr(ab), ops._addr(ar) if ar is not None else 0,
-                   ops._addr(ay), wsb, ops._addr(ap), B, Cin, IH, IW, _bs(xs[idx[0]].t), Cout, R, S, stride, pad, OH, OW, _bs(ys[idx[0]]),
-                   _bs(rs[idx[0]]) if rs is not None else 0, act, float(act_a), float(act_b), STREAM)
-        if uniform:
-            launch(list(range(G)))
-        else:
-            for k in range(G):
-                launch([k])
+        for idx in ([list(range(G))] if uniform else [[k] for k in range(G)]):
+            ops._conv_fwd([xs[k].t for k in idx], [ws_[k] for k in idx], [bs[k] if has_bias else None for k in idx],
+                          [rs[k] for k in idx] if rs is not None else None, [ys[k] for k in idx], stride, pad, act, act_a, act_b)
         youts = [self._tt(y, act=act, act_a=float(act_a), act_b=float(act_b)) for y in ys]
         self._use(*xs)
         if residuals is not None:
@@ -453,7 +419,6 @@ class Tape:
                 for k in live:
                     res_[k].add_alias(gz[k])
             # data gradients: grouped when the epilogue operands agree, else one by one
-            dgeom = (B, Cout, OH, OW, Cin, R, S, stride, pad, IH, IW)
             plan = {}
             for k in live:
                 xs_[k].from_conv(lambda gx, add, mul, k=k: plan.__setitem__(k, (gx, add, mul)))
@@ -477,18 +442,10 @@ class Tape:
                     groups.append((sg, [k]))
                     last[tgt] = len(groups) - 1
             for sg, idx in groups:
-                n = len(idx)
                 has_add, has_mul = sg[0], sg[1]
-                wsb = ops._ws(E.call("cc_conv2d_dgrad_group_ws_bytes", n, *dgeom), xs_[0].t)
-                pks = [ops.packs.get("dgrad", ws_[k], dgeom + (Cin * R * S, R * S)) for k in idx]
-                a1, a2, a3 = ops._parr([gz[k] for k in idx]), ops._parr([ws_[k] for k in idx]), ops._parr([plan[k][0] for k in idx])
-                a4 = ops._parr([plan[k][2] for k in idx]) if has_mul else None
-                a5 = ops._parr([plan[k][1] for k in idx]) if has_add else None
-                a6 = ops._parr(pks)
-                E.call("cc_conv2d_dgrad_group_add", n, ops._addr(a1), ops._addr(a2), ops._addr(a3), ops._addr(a4) if has_mul else 0,
-                       ops._addr(a5) if has_add else 0, wsb, ops._addr(a6), B, Cout, OH, OW, sg[2], Cin, R, S, stride, pad, IH, IW,
-                       sg[3], sg[5] if has_mul else 0, sg[4], Cin * R * S, R * S, sg[6] if has_mul else 0,
-                       sg[7] if has_mul else 1.0, sg[8] if has_mul else 0.0, STREAM)
+                ops._conv_dgrad([gz[k] for k in idx], [ws_[k] for k in idx], None, [plan[k][0] for k in idx],
+                                [plan[k][2] for k in idx] if has_mul else None, [plan[k][1] for k in idx] if has_add else None,
+                                stride, pad, *((sg[6], sg[7], sg[8]) if has_mul else (0, 1.0, 0.0)), spelling="add")
             self._wgrad([gz[k] for k in live], [xs_[k].t for k in live], [ws_[k] for k in live],
                         (B, Cout, OH, OW, Cin, IH, IW, R, S, stride, pad, Cin * R * S, R * S))
 
@@ -498,18 +455,13 @@ class Tape:
     # ------------------------------------------------------------------ transposed convolution
     def conv_transpose(self, x, w, b, stride, pad, out_pad, act=None, act_b=0.0, out=None):
         """act(conv_transpose2d(x, w) + b) (nn.ConvTranspose2d): the transposed arithmetic of the data-gradient kernel."""
-        E = self.E
         act = ACT[act] if not isinstance(act, int) else act
         B, Cin, IH, IW = x.t.shape
         _, Cout, R, S = w.shape
         OH = (IH - 1) * stride - 2 * pad + R + out_pad
         OW = (IW - 1) * stride - 2 * pad + S + out_pad
         y = out if out is not None else _new((B, Cout, OH, OW), x.t)
-        tgeom = (B, Cin, IH, IW, Cout, R, S, stride, pad, OH, OW)
-        wsb = ops._ws(E.call("cc_conv2d_dgrad_ws_bytes", *tgeom), x.t)
-        pk = ops.packs.get("dgrad", w, tgeom + (Cout * R * S, R * S))
-        E.call("cc_conv2d_dgrad", x.t, w, b, y, wsb, pk, B, Cin, IH, IW, _bs(x.t), Cout, R, S, stride, pad, OH, OW, _bs(y),
-               Cout * R * S, R * S, act, 1.0, float(act_b), STREAM)
+        ops._conv_dgrad([x.t], [w], [b], [y], None, None, stride, pad, act, 1.0, act_b, spelling="single")
         yt = self._tt(y, act=act, act_a=1.0, act_b=float(act_b))
         self._use(x)
         if not self.record:
@@ -524,11 +476,7 @@ class Tape:
             # d/dx of a transposed conv is a plain strided conv of gz; the [Cin,Cout,R,S] weight IS its [M,C,R,S] weight
 
             def launch(gx, add, mul):
-                fgeom = (B, Cout, OH, OW, Cin, R, S, stride, pad, IH, IW)
-                ws2 = ops._ws(E.call("cc_conv2d_fwd_ws_bytes", *fgeom), x.t)
-                pk2 = ops.packs.get("fwd", w, fgeom)
-                E.call("cc_conv2d_fwd", gz, w, None, add, gx, ws2, pk2, B, Cout, OH, OW, _bs(gz), Cin, R, S, stride, pad, IH, IW, _bs(gx),
-                       _bs(add) if add is not None else 0, 0, 1.0, 0.0, STREAM)
+                ops._conv_fwd([gz], [w], [None], [add] if add is not None else None, [gx], stride, pad, 0, 1.0, 0.0, single=True)
                 assert mul is None
             # (the forward-arithmetic entry has no act'(mul) epilogue: let a later contributor of x apply it)
             x.from_conv(launch, can_mul=False)
@@ -538,7 +486,6 @@ class Tape:
 
     # ------------------------------------------------------------------ batch norm (training mode), up-sampling
     def batch_norm(self, x, mod):
-        E = self.E
         if not mod.training:
             y = ops.batch_norm(x.t, mod.weight, mod.bias, mod.running_mean, mod.running_var, None, False, mod.momentum, mod.eps)
             yt = self._tt(y)
@@ -549,7 +496,6 @@ class Tape:
                     if g is None:
                         x.skip()
                         return
-                    B, C, H, W = g.shape
                     # affine parameters that still train in eval mode (not the reference's use, but nn.BatchNorm2d allows it)
                     want_w = mod.weight is not None and mod.weight.requires_grad
                     want_b = mod.bias is not None and mod.bias.requires_grad
@@ -562,8 +508,7 @@ class Tape:
 
                     def write(gx, accumulate):
                         dst = gx if not accumulate else torch.empty_like(gx)
-                        E.call("cc_bn_eval_fwd", g.contiguous(), mod.weight, None, mod.running_mean, mod.running_var, dst, ops._ws(8 * C, g),
-                               B, C, H, W, float(mod.eps), 1, STREAM)
+                        ops._bn_eval_fwd(g.contiguous(), mod.weight, None, mod.running_mean, mod.running_var, dst, mod.eps, grad_only=1)
                         if accumulate:
                             gx.add_(dst)
                     x.from_writer(write)
@@ -578,11 +523,7 @@ class Tape:
                 BN_COUNTERS.ran.add(id(mod))        # the trainer bumps all counters of the step with one add
             else:
                 mod.num_batches_tracked.add_(1)
-        y = torch.empty_like(xt)
-        mean = torch.empty(C, device=xt.device, dtype=torch.float32)
-        invstd = torch.empty_like(mean)
-        E.call("cc_bn_train_fwd", xt, mod.weight, mod.bias, mod.running_mean, mod.running_var, y, mean, invstd,
-               ops._ws(E.call("cc_bn_ws_bytes", C), xt), B, C, H, W, float(mod.momentum), float(mod.eps), STREAM)
+        y, mean, invstd = ops._bn_train_fwd(xt, mod.weight, mod.bias, mod.running_mean, mod.running_var, mod.momentum, mod.eps)
         yt = self._tt(y)
         self._use(x)
         if not self.record:
@@ -602,8 +543,7 @@ class Tape:
 
             def write(gx, accumulate):
                 dst = gx if not accumulate else torch.empty_like(gx)
-                E.call("cc_bn_train_bwd", g, xt, mod.weight, mean, invstd, dst, gw, gb, ops._ws(E.call("cc_bn_ws_bytes", C), xt),
-                       B, C, H, W, int(acc_w or acc_b), STREAM)
+                ops._bn_train_bwd(g, xt, mod.weight, mean, invstd, dst, gw, gb, acc_w or acc_b)
                 if accumulate:
                     gx.add_(dst)
             if x.needs:
@@ -616,10 +556,9 @@ class Tape:
 
     def upsample2x(self, x, scale=1.0, out=None):
         """scale * F.interpolate(x, scale_factor=2, mode='bilinear', align_corners=False) in one launch."""
-        E = self.E
         B, C, H, W = x.t.shape
         y = out if out is not None else _new((B, C, 2 * H, 2 * W), x.t)
-        E.call("cc_upsample2x_fwd", x.t, y, B, C, H, W, _bs(x.t), _bs(y), float(scale), STREAM)
+        ops._up2x_fwd(x.t, y, scale)
         yt = self._tt(y)
         self._use(x)
         if self.record:
@@ -628,23 +567,20 @@ class Tape:
                 if g is None:
                     x.skip()
                     return
-                x.from_writer(lambda gx, acc: E.call("cc_upsample2x_bwd", g, gx, B, C, H, W, _bs(g), _bs(gx), float(scale), int(acc), STREAM))
+                x.from_writer(lambda gx, acc: ops._up2x_bwd(g, gx, scale, acc))
             self._node(bwd)
         return yt
 
     # ------------------------------------------------------------------ cost volume, feature warp (Back2Future)
     def corr_pair(self, a, b, c, inv_b, inv_c, out=None):
         """cat(correlate(a, b)[:, perm_b], correlate(a, c)[:, perm_c]) written at channels 0..161 of `out`'s buffer."""
-        E = self.E
         B, C, H, W = a.t.shape
         at, bt, ct = [t.t if t.t.is_contiguous() else t.t.contiguous() for t in (a, b, c)]
         if out is None:
             out = _new((B, 162, H, W), at)
-        # the kernels address out[n, off + ch] as base + (n * total + off + ch) * H * W: passing the SLICE's first element as
-        # base with the wide buffer's channel count addresses a channel slice of a concat buffer in place
-        tot = _bs(out) // (H * W)
-        E.call("cc_corr9x9_fwd", at, bt, out, inv_b, B, C, H, W, tot, 0, STREAM)
-        E.call("cc_corr9x9_fwd", at, ct, out, inv_c, B, C, H, W, tot, 81, STREAM)
+        # (a channel slice of a concat buffer is addressed in place: ops._corr9x9_fwd)
+        ops._corr9x9_fwd(at, bt, out, inv_b, 0)
+        ops._corr9x9_fwd(at, ct, out, inv_c, 81)
         yt = self._tt(out)
         self._use(a, b, c)
         if self.record:
@@ -653,10 +589,9 @@ class Tape:
                 if g is None:
                     a.skip(), b.skip(), c.skip()
                     return
-                gtot = _bs(g) // (H * W)
                 ga, gb_, gc = torch.empty_like(at), torch.empty_like(bt), torch.empty_like(ct)
-                E.call("cc_corr9x9_bwd", g, at, bt, ga, gb_ if b.needs else None, inv_b, B, C, H, W, gtot, 0, 0, STREAM)
-                E.call("cc_corr9x9_bwd", g, at, ct, ga, gc if c.needs else None, inv_c, B, C, H, W, gtot, 81, 1, STREAM)
+                ops._corr9x9_bwd(g, at, bt, ga, gb_ if b.needs else None, inv_b, 0, 0)
+                ops._corr9x9_bwd(g, at, ct, ga, gc if c.needs else None, inv_c, 81, 1)
                 a.add_alias(ga)
                 b.add_alias(gb_) if b.needs else b.skip()
                 c.add_alias(gc) if c.needs else c.skip()

@@ -19,33 +19,35 @@ LB, LH, LW = 2, 64, 128
 class ArgLog:
     """tests/grad_guard_cases.py CallLog extended to the arguments: [name, [args]] per call.  An address is logged as "p" (0 when
     null), the stream not at all; a job table (first argument `jobs`) as njobs rows [H, W, [slots]], a slot being 0, "p" or the
-    integer it carries (flags, channel counts); cc_scale_acc_jobs' table as rows [n floats, accumulate]."""
+    integer it carries (flags, channel counts); cc_scale_acc_jobs' table as rows [n floats, accumulate].  Subclasses choose the
+    calls they keep (keeps) and how an argument is written down (arg): tests/conv_calls.py."""
 
     def __enter__(self):
         self.e, self.calls = engine(), []
         self.orig = self.e.call
 
         def call(name, *a):
-            types, names = self.e.sigs[name][1], self.e.sigs[name][2]
-            rec = []
-            for v, ty, an in zip(a, types, names):
-                if an == "stream" or v is STREAM:
-                    continue
-                if an == "jobs":
-                    tab = (ctypes.c_long * (10 * a[1])).from_address(v)
-                    rec.append([[tab[10 * j + 8], tab[10 * j + 9], [self._slot(tab[10 * j + k]) for k in range(8)]]
-                                for j in range(a[1])])
-                elif an == "jobs_host":
-                    tab = (ctypes.c_long * (4 * a[1])).from_address(v)
-                    rec.append([[tab[4 * j + 2], tab[4 * j + 3]] for j in range(a[1])])
-                elif ty is ctypes.c_void_p:
-                    rec.append(0 if (v is None or (isinstance(v, int) and v == 0)) else "p")
-                else:
-                    rec.append(v)
-            self.calls.append([name, rec])
+            if self.keeps(name):
+                types, names = self.e.sigs[name][1], self.e.sigs[name][2]
+                self.calls.append([name, [self.arg(name, a, v, ty, an) for v, ty, an in zip(a, types, names)
+                                          if not (an == "stream" or v is STREAM)]])
             return self.orig(name, *a)
         self.e.call = call
         return self
+
+    def keeps(self, name):
+        return True
+
+    def arg(self, name, a, v, ty, an):
+        if an == "jobs":
+            tab = (ctypes.c_long * (10 * a[1])).from_address(v)
+            return [[tab[10 * j + 8], tab[10 * j + 9], [self._slot(tab[10 * j + k]) for k in range(8)]] for j in range(a[1])]
+        if an == "jobs_host":
+            tab = (ctypes.c_long * (4 * a[1])).from_address(v)
+            return [[tab[4 * j + 2], tab[4 * j + 3]] for j in range(a[1])]
+        if ty is ctypes.c_void_p:
+            return 0 if (v is None or (isinstance(v, int) and v == 0)) else "p"
+        return v
 
     @staticmethod
     def _slot(v):

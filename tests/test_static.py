@@ -39,3 +39,22 @@ def test_no_undefined_names():
         [os.path.join(ROOT, "bench.py"), os.path.join(ROOT, "__graft_entry__.py")]
     bad = {os.path.relpath(f, ROOT): u for f in files for u in [_undefined(f)] if u}
     assert not bad, bad
+
+
+# the entry points of the launcher families of cc_amd/ops.py (conv forward / data gradient, activation backward + bias sums,
+# batch norm, x2 up-sampling, the 9x9 cost volume): each is spelled out -- name and argument list -- in exactly one place
+LAUNCHER_ENTRIES = ["cc_conv2d_fwd", "cc_conv2d_fwd_group", "cc_conv2d_dgrad", "cc_conv2d_dgrad_group", "cc_conv2d_dgrad_group_add",
+                    "cc_act_bwd_bias_group", "cc_act_bwd_bias_group_defer", "cc_bn_train_fwd", "cc_bn_train_bwd", "cc_bn_eval_fwd",
+                    "cc_upsample2x_fwd", "cc_upsample2x_bwd", "cc_corr9x9_fwd", "cc_corr9x9_bwd"]
+
+
+def test_launcher_entries_are_spelled_once():
+    import re
+    src = {os.path.relpath(f, ROOT): open(f).read() for f in glob.glob(os.path.join(ROOT, "cc_amd", "*.py"))}
+    sites = {}
+    for f, text in src.items():
+        for m in re.finditer(r"\bcall\(\s*[\"'](cc_\w+)[\"']", text):
+            sites.setdefault(m.group(1), []).append(f)
+    for name in LAUNCHER_ENTRIES:
+        assert sites.get(name) == ["cc_amd/ops.py"], (name, sites.get(name))
+    assert not any("_Conv2dFn" in text for text in src.values())

@@ -57,7 +57,7 @@ def main():
             macs = B * H * W * Cin * Cout * k * k
         else:
             w = torch.randn(Cout, Cin, k, k, device=dev) * 0.05
-            fwd_hip = lambda: ops._Conv2dFn.apply(x, w, None, None, st, pad, 1, 1.0, 0.0)
+            fwd_hip = lambda: ops.conv2d(x, w, None, st, pad, "relu")
             fwd_ref = lambda: F.relu(F.conv2d(x, w, None, st, pad))
             OH, OW = (H + 2 * pad - k) // st + 1, (W + 2 * pad - k) // st + 1
             macs = B * OH * OW * Cin * Cout * k * k
@@ -72,7 +72,7 @@ def main():
             if tr:
                 y = ops._ConvT2dFn.apply(xg, wg, None, st, pad, op, 1) if f_hip else F.relu(F.conv_transpose2d(xg, wg, None, st, pad, op))
             else:
-                y = ops._Conv2dFn.apply(xg, wg, None, None, st, pad, 1, 1.0, 0.0) if f_hip else F.relu(F.conv2d(xg, wg, None, st, pad))
+                y = ops.conv2d(xg, wg, None, st, pad, "relu") if f_hip else F.relu(F.conv2d(xg, wg, None, st, pad))
             gy = torch.ones_like(y)
             torch.autograd.grad(y, [xg, wg], gy)
         t_hb = timeit(lambda: fb(True), 3)
