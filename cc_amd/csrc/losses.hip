@@ -123,23 +123,23 @@ __global__ __launch_bounds__(256) void k_pyramid_tile_multi(PyrMulti t, int nlev
 }
 
 // ------------------------------------------------------------------ occlusion masks
-// loss_functions.py:343-352 occlusion_masks: occ = sum_c(f_fw + f_bw) > 0.08*(|f_fw|^2 + |f_bw|^2) + 1
-// (signed sum; occ_fw == occ_bw).  Output is (1 - occ), the factor the losses multiply by.
-__device__ __forceinline__ float noocc(float bu, float bv, float fu, float fv) {
-    const float mag = (fu * fu + fv * fv) + (bu * bu + bv * bv);
-    const float thr = 0.08f * mag + 1.0f;
-    const float s = (fu + bu) + (fv + bv);
-    return (s > thr) ? 0.f : 1.f;
+// The pixel bodies (*_px) are shared by a single-call kernel and its job-table form further down: each kernel keeps only where
+// (b, p) comes from, the early exit, the pixels-per-work-item loop, the block reduction and where the partial sums go.
+// loss_functions.py:343-352 occlusion_masks (ccjobs::noocc, jobs.h): (1 - occ), the factor the losses multiply by
+using ccjobs::noocc;
+
+__device__ __forceinline__ void flow_noocc_px(const float* __restrict__ flow_bw, const float* __restrict__ flow_fw,
+                                              float* __restrict__ out, int b, int p, int HW) {
+    const float* fb = flow_bw + (size_t)b * 2 * HW + p;
+    const float* ff = flow_fw + (size_t)b * 2 * HW + p;
+    out[(size_t)b * HW + p] = noocc(fb[0], fb[HW], ff[0], ff[HW]);
 }
 
 __global__ __launch_bounds__(256) void k_flow_noocc(const float* __restrict__ flow_bw, const float* __restrict__ flow_fw,
                                                     float* __restrict__ out, int HW) {
     const int p = blockIdx.x * 256 + threadIdx.x;
     if (p >= HW) return;
-    const int b = blockIdx.y;
-    const float* fb = flow_bw + (size_t)b * 2 * HW + p;
-    const float* ff = flow_fw + (size_t)b * 2 * HW + p;
-    out[(size_t)b * HW + p] = noocc(fb[0], fb[HW], ff[0], ff[HW]);
+    flow_noocc_px(flow_bw, flow_fw, out, (int)blockIdx.y, p, HW);
 }
 
 // loss_functions.py:132-137 depth_occlusion_masks: four rigid flows (pose2flow with the FULL-resolution
@@ -193,6 +193,40 @@ __device__ __forceinline__ float edge_w(const float* __restrict__ im, int HW, in
     return expf(-(a / 3.f));
 }
 
+// pixel p of plane bc = (image b, channel): its terms are added to `part`, its gradient written.  wgt: the level's edge weights
+// [B,2,H,W] = (w(p, p + 1), w(p, p + W)) from k_edge_weights_jobs -- four loads instead of 24 + four exp() -- or null
+__device__ __forceinline__ void edge_smooth_px(const float* __restrict__ img, const float* __restrict__ pred, float* __restrict__ gpred,
+                                               const float* __restrict__ wgt, int bc, int b, int p, int H, int W, int HW, float inv_nx,
+                                               float inv_ny, float gscale, float& part) {
+    const int y = p / W, x = p - y * W;
+    const float* im = img + (size_t)b * 3 * HW;
+    const float* pr = pred + (size_t)bc * HW;
+    const float* wg = wgt ? wgt + (size_t)b * 2 * HW : nullptr;
+    const float v = pr[p];
+    float g = 0.f;
+    if (y + 1 < H) {                      // term (y, x) of the H-direction sum
+        const float d = v - pr[p + W];
+        const float w = wg ? wg[HW + p] : edge_w(im, HW, p, p + W);
+        part += fabsf(d) * w * inv_nx;
+        g += sgn(d) * w * inv_nx;
+    }
+    if (y > 0) {                          // this pixel is the "+1" operand of term (y-1, x)
+        const float d = pr[p - W] - v;
+        g -= sgn(d) * (wg ? wg[HW + p - W] : edge_w(im, HW, p - W, p)) * inv_nx;
+    }
+    if (x + 1 < W) {
+        const float d = v - pr[p + 1];
+        const float w = wg ? wg[p] : edge_w(im, HW, p, p + 1);
+        part += fabsf(d) * w * inv_ny;
+        g += sgn(d) * w * inv_ny;
+    }
+    if (x > 0) {
+        const float d = pr[p - 1] - v;
+        g -= sgn(d) * (wg ? wg[p - 1] : edge_w(im, HW, p - 1, p)) * inv_ny;
+    }
+    if (gpred) gpred[(size_t)bc * HW + p] = g * gscale;
+}
+
 __global__ __launch_bounds__(256) void k_edge_smooth(const float* __restrict__ img, const float* __restrict__ pred,
                                                      float* __restrict__ gpred, float* __restrict__ partials, int C, int H,
                                                      int W, float inv_nx, float inv_ny, float gscale) {
@@ -201,34 +235,7 @@ __global__ __launch_bounds__(256) void k_edge_smooth(const float* __restrict__ i
     const int p = blockIdx.x * 256 + threadIdx.x;
     const int bc = blockIdx.y, b = bc / C;
     float part[1] = {0.f};
-    if (p < HW) {
-        const int y = p / W, x = p - y * W;
-        const float* im = img + (size_t)b * 3 * HW;
-        const float* pr = pred + (size_t)bc * HW;
-        const float v = pr[p];
-        float g = 0.f;
-        if (y + 1 < H) {                      // term (y, x) of the H-direction sum
-            const float d = v - pr[p + W];
-            const float w = edge_w(im, HW, p, p + W);
-            part[0] += fabsf(d) * w * inv_nx;
-            g += sgn(d) * w * inv_nx;
-        }
-        if (y > 0) {                          // this pixel is the "+1" operand of term (y-1, x)
-            const float d = pr[p - W] - v;
-            g -= sgn(d) * edge_w(im, HW, p - W, p) * inv_nx;
-        }
-        if (x + 1 < W) {
-            const float d = v - pr[p + 1];
-            const float w = edge_w(im, HW, p, p + 1);
-            part[0] += fabsf(d) * w * inv_ny;
-            g += sgn(d) * w * inv_ny;
-        }
-        if (x > 0) {
-            const float d = pr[p - 1] - v;
-            g -= sgn(d) * edge_w(im, HW, p - 1, p) * inv_ny;
-        }
-        if (gpred) gpred[(size_t)bc * HW + p] = g * gscale;
-    }
+    if (p < HW) edge_smooth_px(img, pred, gpred, nullptr, bc, b, p, H, W, HW, inv_nx, inv_ny, gscale, part[0]);
     cc::block_sum_256<1>(part, red);
     if (threadIdx.x == 0) partials[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = part[0];
 }
@@ -282,18 +289,22 @@ __global__ __launch_bounds__(256) void k_smooth2(const float* __restrict__ pred,
 
 // ------------------------------------------------------------------ BCE losses
 // loss_functions.py:148-155 explainability_loss: F.binary_cross_entropy(mask, 1) = mean(-max(log(mask), -100))
+// element i -> its term
+__device__ __forceinline__ float bce_ones_px(const float* __restrict__ mask, float* __restrict__ gmask, size_t i, float inv_n,
+                                             float gscale) {
+    const float m = mask[i];
+    const float lg = fmaxf(logf(m), -100.f);
+    // ATen binary_cross_entropy_backward: (x - y) / max((1 - x) * x, 1e-12), y = 1
+    if (gmask) gmask[i] = ((m - 1.f) / fmaxf((1.f - m) * m, 1e-12f)) * inv_n * gscale;
+    return -lg * inv_n;
+}
+
 __global__ __launch_bounds__(256) void k_bce_ones(const float* __restrict__ mask, float* __restrict__ gmask,
                                                   float* __restrict__ partials, int n, float inv_n, float gscale) {
     __shared__ float red[4];
     const int i = blockIdx.x * 256 + threadIdx.x;
     float part[1] = {0.f};
-    if (i < n) {
-        const float m = mask[i];
-        const float lg = fmaxf(logf(m), -100.f);
-        part[0] = -lg * inv_n;
-        // ATen binary_cross_entropy_backward: (x - y) / max((1 - x) * x, 1e-12), y = 1
-        if (gmask) gmask[i] = ((m - 1.f) / fmaxf((1.f - m) * m, 1e-12f)) * inv_n * gscale;
-    }
+    if (i < n) part[0] = bce_ones_px(mask, gmask, (size_t)i, inv_n, gscale);
     cc::block_sum_256<1>(part, red);
     if (threadIdx.x == 0) partials[blockIdx.x] = part[0];
 }
@@ -301,6 +312,27 @@ __global__ __launch_bounds__(256) void k_bce_ones(const float* __restrict__ mask
 // loss_functions.py:221-261 consensus_depth_flow_mask, one scale (census_* = |cam_flow - flow|, train.py:475-476):
 //   census_d = prod_c(census_mask_d < THRESH)  OR  exp_target_d                 (d in {bwd, fwd})
 //   target   = (bwd, bwd, fwd, fwd);  loss = -mean(w1*t*log(e+eps) + w0*(1-t)*log(1-e+eps)), w=[wbce, 1-wbce]
+struct ConsensusBce { float thresh, w0, w1, inv_n, gscale; };
+__device__ __forceinline__ void consensus_bce_px(const float* __restrict__ exp_mask, const float* __restrict__ census_bwd,
+                                                 const float* __restrict__ census_fwd, const float* __restrict__ tgt_bwd,
+                                                 const float* __restrict__ tgt_fwd, float* __restrict__ gmask, int b, int p, int HW,
+                                                 const ConsensusBce& k, float& part) {
+    const size_t f = (size_t)b * 2 * HW + p;
+    const float cb = (census_bwd[f] < k.thresh && census_bwd[f + HW] < k.thresh) ? 1.f : 0.f;
+    const float cf = (census_fwd[f] < k.thresh && census_fwd[f + HW] < k.thresh) ? 1.f : 0.f;
+    const float tb = 1.f - (1.f - cb) * (1.f - tgt_bwd[(size_t)b * HW + p]);
+    const float tf = 1.f - (1.f - cf) * (1.f - tgt_fwd[(size_t)b * HW + p]);
+    const float t[4] = {tb, tb, tf, tf};
+#pragma unroll
+    for (int c = 0; c < 4; c++) {
+        const size_t o = ((size_t)b * 4 + c) * HW + p;
+        const float e = exp_mask[o];
+        const float a1 = e + 1e-8f, a0 = (1.f - e) + 1e-8f;
+        part -= (k.w1 * (t[c] * logf(a1)) + k.w0 * ((1.f - t[c]) * logf(a0))) * k.inv_n;
+        if (gmask) gmask[o] = -(k.w1 * t[c] / a1 - k.w0 * (1.f - t[c]) / a0) * k.inv_n * k.gscale;
+    }
+}
+
 __global__ __launch_bounds__(256) void k_consensus_bce(const float* __restrict__ exp_mask, const float* __restrict__ census_bwd,
                                                        const float* __restrict__ census_fwd, const float* __restrict__ tgt_bwd,
                                                        const float* __restrict__ tgt_fwd, float* __restrict__ gmask,
@@ -310,22 +342,7 @@ __global__ __launch_bounds__(256) void k_consensus_bce(const float* __restrict__
     const int p = blockIdx.x * 256 + threadIdx.x;
     const int b = blockIdx.y;
     float part[1] = {0.f};
-    if (p < HW) {
-        const size_t f = (size_t)b * 2 * HW + p;
-        const float cb = (census_bwd[f] < thresh && census_bwd[f + HW] < thresh) ? 1.f : 0.f;
-        const float cf = (census_fwd[f] < thresh && census_fwd[f + HW] < thresh) ? 1.f : 0.f;
-        const float tb = 1.f - (1.f - cb) * (1.f - tgt_bwd[(size_t)b * HW + p]);
-        const float tf = 1.f - (1.f - cf) * (1.f - tgt_fwd[(size_t)b * HW + p]);
-        const float t[4] = {tb, tb, tf, tf};
-#pragma unroll
-        for (int c = 0; c < 4; c++) {
-            const size_t o = ((size_t)b * 4 + c) * HW + p;
-            const float e = exp_mask[o];
-            const float a1 = e + 1e-8f, a0 = (1.f - e) + 1e-8f;
-            part[0] -= (w1 * (t[c] * logf(a1)) + w0 * ((1.f - t[c]) * logf(a0))) * inv_n;
-            if (gmask) gmask[o] = -(w1 * t[c] / a1 - w0 * (1.f - t[c]) / a0) * inv_n * gscale;
-        }
-    }
+    if (p < HW) consensus_bce_px(exp_mask, census_bwd, census_fwd, tgt_bwd, tgt_fwd, gmask, b, p, HW, {thresh, w0, w1, inv_n, gscale}, part[0]);
     cc::block_sum_256<1>(part, red);
     if (threadIdx.x == 0) partials[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = part[0];
 }
@@ -397,38 +414,30 @@ __global__ __launch_bounds__(256) void k_scale_acc_jobs(ScaleAccTab t, const flo
 }
 
 // ------------------------------------------------------------------ job-table forms (all pyramid levels in one launch, jobs.h)
-#define CC_JOB_PIXEL(t, j, b, p, HW)                                        \
-    int first__;                                                            \
-    const int j = ccjobs::find(t, (int)blockIdx.x, first__);                \
-    const int HW = t.H[j] * t.W[j], nb__ = (HW + 255) >> 8;                 \
-    const int local__ = (int)blockIdx.x - first__;                          \
-    const int b = local__ / nb__, p = (local__ - b * nb__) * 256 + (int)threadIdx.x;
-
+// Each kernel finds its job and piece (ccjobs::piece / pieces, jobs.h), reads the job's slots and calls the pixel body of its
+// single-call kernel above.
 // occlusion_masks per level: slots 0 flow_bw [B,2,H,W], 1 flow_fw, 2 out [B,1,H,W]
 __global__ __launch_bounds__(256) void k_flow_noocc_jobs(JobTab t) {
-    CC_JOB_PIXEL(t, j, b, p, HW)
-    if (p >= HW) return;
-    const float* fb = ccjobs::ptr<const float>(t, j, 0) + (size_t)b * 2 * HW + p;
-    const float* ff = ccjobs::ptr<const float>(t, j, 1) + (size_t)b * 2 * HW + p;
-    ccjobs::ptr<float>(t, j, 2)[(size_t)b * HW + p] = noocc(fb[0], fb[HW], ff[0], ff[HW]);
+    const ccjobs::Piece w = ccjobs::piece<false>(t);
+    if (w.p >= w.HW) return;
+    flow_noocc_px(ccjobs::ptr<const float>(t, w.j, 0), ccjobs::ptr<const float>(t, w.j, 1), ccjobs::ptr<float>(t, w.j, 2), w.b, w.p, w.HW);
 }
 
 // consensus target per level: slots 0 err_cam_fwd, 1 err_cam_bwd, 2 err_flow_fwd, 3 valid_cam_fwd, 4 valid_cam_bwd, 5 target
 __global__ __launch_bounds__(256) void k_consensus_combine_jobs(JobTab t, float wrig) {
-    CC_JOB_PIXEL(t, j, b, p, HW)
-    if (p >= HW) return;
-    const size_t i = (size_t)b * HW + p;
-    const float vcf = ccjobs::ptr<const float>(t, j, 3)[i], vcb = ccjobs::ptr<const float>(t, j, 4)[i];
-    const float valid = 1.f - (1.f - vcf) * (1.f - vcb);
-    const float cam_err = fminf(ccjobs::ptr<const float>(t, j, 0)[i], ccjobs::ptr<const float>(t, j, 1)[i]) * valid;
-    ccjobs::ptr<float>(t, j, 5)[i] = (wrig * cam_err <= (ccjobs::ptr<const float>(t, j, 2)[i] + 1e-8f)) ? 1.f : 0.f;
+    const ccjobs::Piece w = ccjobs::piece<false>(t);
+    if (w.p >= w.HW) return;
+    ccjobs::consensus_combine_px(ccjobs::ptr<const float>(t, w.j, 0), ccjobs::ptr<const float>(t, w.j, 1), ccjobs::ptr<const float>(t, w.j, 2),
+                                 ccjobs::ptr<const float>(t, w.j, 3), ccjobs::ptr<const float>(t, w.j, 4), ccjobs::ptr<float>(t, w.j, 5), wrig,
+                                 (size_t)w.b * w.HW + w.p);
 }
 
 // end of a photometric loss's gradient pass, per level: gdepth = sum over reference frames of the per-frame depth gradients
 // (reference order r = 0..R-1), gmask[:, c] *= scale[c] (the per-term normalisers known only after the reduction).
 // slots 0 gd_all [R][B][HW] (or 0), 1 gdepth [B][HW], 2 gmask [B][MC][HW] (or 0), 3 scales (MC floats)
 __global__ __launch_bounds__(256) void k_sum_refs_scale_jobs(JobTab t, int R, int MC) {
-    CC_JOB_PIXEL(t, j, b, p, HW)
+    const ccjobs::Piece w = ccjobs::piece<false>(t);
+    const int j = w.j, b = w.b, p = w.p, HW = w.HW;
     if (p >= HW) return;
     const float* gd = ccjobs::ptr<const float>(t, j, 0);
     if (gd) {
@@ -452,9 +461,9 @@ __global__ __launch_bounds__(256) void k_sum_refs_scale_jobs(JobTab t, int R, in
 // w(p, p + W)), 0 beyond the last column / row.  The smoothness terms of a step (depth, two flows, the 4-channel masks: 9 planes per
 // image and scale) share them instead of evaluating exp(-|dI| / 3) four times per pixel and plane (same expression, same bits).
 __global__ __launch_bounds__(256) void k_edge_weights_jobs(JobTab t) {
-    CC_JOB_PIXEL(t, j, b, p, HW)
+    const ccjobs::Piece w = ccjobs::piece<false>(t);
+    const int j = w.j, b = w.b, p = w.p, H = w.H, W = w.W, HW = w.HW;
     if (p >= HW) return;
-    const int W = t.W[j], H = t.H[j];
     const int y = p / W, x = p - y * W;
     const float* im = ccjobs::ptr<const float>(t, j, 0) + (size_t)b * 3 * HW;
     float* o = ccjobs::ptr<float>(t, j, 1) + (size_t)b * 2 * HW;
@@ -469,106 +478,53 @@ __global__ __launch_bounds__(256) void k_edge_weights_jobs(JobTab t) {
 template <int PPT>
 __global__ __launch_bounds__(256) void k_edge_smooth_jobs(JobTab t, int C, float gscale) {
     __shared__ float red[4];
-    int local__;
-    const int j = ccjobs::find_xcd(t, (int)blockIdx.x, local__);
-    const int HW = t.H[j] * t.W[j], nb1 = (HW + 255) >> 8, nb__ = (nb1 + PPT - 1) / PPT;
-    const int bc = local__ / nb__, blk = local__ - bc * nb__;
-    const int Cj = C ? C : (int)t.slot[j][4];
+    const ccjobs::Pieces w = ccjobs::pieces<PPT, true>(t);          // (w.b: the plane, image b = bc / Cj)
+    const int Cj = C ? C : (int)t.slot[w.j][4];
     const int planes = C ? t.B : t.B * Cj;
-    const int H = t.H[j], W = t.W[j], b = bc / Cj;
+    const int H = w.H, W = w.W, bc = w.b, b = bc / Cj;
     const float inv_nx = 1.f / ((float)planes * (H - 1) * W), inv_ny = 1.f / ((float)planes * H * (W - 1));
     float part[1] = {0.f};
 #pragma unroll
     for (int k = 0; k < PPT; k++) {
-      const int p = (blk * PPT + k) * 256 + (int)threadIdx.x;
-      if (p < HW) {
-        const int y = p / W, x = p - y * W;
-        const float* im = ccjobs::ptr<const float>(t, j, 0) + (size_t)b * 3 * HW;
-        const float* pr = ccjobs::ptr<const float>(t, j, 1) + (size_t)bc * HW;
-        float* gpred = ccjobs::ptr<float>(t, j, 2);
-        // slot 5 (optional): the level's edge weights [B,2,H,W] from k_edge_weights_jobs -- four loads instead of 24 + four exp()
-        const float* wg = t.slot[j][5] ? ccjobs::ptr<const float>(t, j, 5) + (size_t)b * 2 * HW : nullptr;
-        const float v = pr[p];
-        float g = 0.f;
-        if (y + 1 < H) {
-            const float d = v - pr[p + W];
-            const float w = wg ? wg[HW + p] : edge_w(im, HW, p, p + W);
-            part[0] += fabsf(d) * w * inv_nx;
-            g += sgn(d) * w * inv_nx;
-        }
-        if (y > 0) {
-            const float d = pr[p - W] - v;
-            g -= sgn(d) * (wg ? wg[HW + p - W] : edge_w(im, HW, p - W, p)) * inv_nx;
-        }
-        if (x + 1 < W) {
-            const float d = v - pr[p + 1];
-            const float w = wg ? wg[p] : edge_w(im, HW, p, p + 1);
-            part[0] += fabsf(d) * w * inv_ny;
-            g += sgn(d) * w * inv_ny;
-        }
-        if (x > 0) {
-            const float d = pr[p - 1] - v;
-            g -= sgn(d) * (wg ? wg[p - 1] : edge_w(im, HW, p - 1, p)) * inv_ny;
-        }
-        if (gpred) gpred[(size_t)bc * HW + p] = g * gscale;
-      }
+        const int p = (w.blk * PPT + k) * 256 + (int)threadIdx.x;
+        // slot 5 (optional): the level's edge weights from k_edge_weights_jobs
+        if (p < w.HW)
+            edge_smooth_px(ccjobs::ptr<const float>(t, w.j, 0), ccjobs::ptr<const float>(t, w.j, 1), ccjobs::ptr<float>(t, w.j, 2),
+                           ccjobs::ptr<const float>(t, w.j, 5), bc, b, p, H, W, w.HW, inv_nx, inv_ny, gscale, part[0]);
     }
     cc::block_sum_256<1>(part, red);
     // the partial areas keep their 256-pixel granularity (the host lays them out back to back per job and sums them all): this
     // workgroup's sum goes to the first of its PPT places, zeros to the others
     if ((int)threadIdx.x < PPT) {
-        const int idx = blk * PPT + (int)threadIdx.x;
-        if (idx < nb1) ccjobs::ptr<float>(t, j, 3)[(size_t)bc * nb1 + idx] = threadIdx.x == 0 ? part[0] : 0.f;
+        const int idx = w.blk * PPT + (int)threadIdx.x;
+        if (idx < w.nb) ccjobs::ptr<float>(t, w.j, 3)[(size_t)bc * w.nb + idx] = threadIdx.x == 0 ? part[0] : 0.f;
     }
 }
 
 // explainability BCE, all levels: slots 0 mask (n = B*C*H*W elements: table B = batch * C), 1 gmask (or 0), 2 partials
 __global__ __launch_bounds__(256) void k_bce_ones_jobs(JobTab t, float gscale) {
     __shared__ float red[4];
-    CC_JOB_PIXEL(t, j, bc, p, HW)
-    const float inv_n = 1.f / ((float)t.B * HW);
+    const ccjobs::Piece w = ccjobs::piece<false>(t);
     float part[1] = {0.f};
-    if (p < HW) {
-        const size_t i = (size_t)bc * HW + p;
-        const float m = ccjobs::ptr<const float>(t, j, 0)[i];
-        const float lg = fmaxf(logf(m), -100.f);
-        part[0] = -lg * inv_n;
-        float* gmask = ccjobs::ptr<float>(t, j, 1);
-        if (gmask) gmask[i] = ((m - 1.f) / fmaxf((1.f - m) * m, 1e-12f)) * inv_n * gscale;
-    }
+    if (w.p < w.HW)
+        part[0] = bce_ones_px(ccjobs::ptr<const float>(t, w.j, 0), ccjobs::ptr<float>(t, w.j, 1), (size_t)w.b * w.HW + w.p,
+                              1.f / ((float)t.B * w.HW), gscale);
     cc::block_sum_256<1>(part, red);
-    if (threadIdx.x == 0) ccjobs::ptr<float>(t, j, 2)[local__] = part[0];
+    if (threadIdx.x == 0) ccjobs::ptr<float>(t, w.j, 2)[w.b * w.nb + (w.p >> 8)] = part[0];        // (work-item 0: p >> 8 = the piece)
 }
 
 // consensus weighted BCE, all levels: slots 0 exp_mask [B,4,H,W], 1 census_bwd [B,2,H,W], 2 census_fwd, 3 tgt_bwd [B,1,H,W],
 // 4 tgt_fwd, 5 gmask (or 0), 6 partials
 __global__ __launch_bounds__(256) void k_consensus_bce_jobs(JobTab t, float thresh, float w0, float w1, float gscale) {
     __shared__ float red[4];
-    CC_JOB_PIXEL(t, j, b, p, HW)
-    const float inv_n = 1.f / ((float)t.B * 4 * HW);
+    const ccjobs::Piece w = ccjobs::piece<false>(t);
     float part[1] = {0.f};
-    if (p < HW) {
-        const float* exp_mask = ccjobs::ptr<const float>(t, j, 0);
-        const float* census_bwd = ccjobs::ptr<const float>(t, j, 1);
-        const float* census_fwd = ccjobs::ptr<const float>(t, j, 2);
-        float* gmask = ccjobs::ptr<float>(t, j, 5);
-        const size_t f = (size_t)b * 2 * HW + p;
-        const float cb = (census_bwd[f] < thresh && census_bwd[f + HW] < thresh) ? 1.f : 0.f;
-        const float cf = (census_fwd[f] < thresh && census_fwd[f + HW] < thresh) ? 1.f : 0.f;
-        const float tb = 1.f - (1.f - cb) * (1.f - ccjobs::ptr<const float>(t, j, 3)[(size_t)b * HW + p]);
-        const float tf = 1.f - (1.f - cf) * (1.f - ccjobs::ptr<const float>(t, j, 4)[(size_t)b * HW + p]);
-        const float tg[4] = {tb, tb, tf, tf};
-#pragma unroll
-        for (int c = 0; c < 4; c++) {
-            const size_t o = ((size_t)b * 4 + c) * HW + p;
-            const float e = exp_mask[o];
-            const float a1 = e + 1e-8f, a0 = (1.f - e) + 1e-8f;
-            part[0] -= (w1 * (tg[c] * logf(a1)) + w0 * ((1.f - tg[c]) * logf(a0))) * inv_n;
-            if (gmask) gmask[o] = -(w1 * tg[c] / a1 - w0 * (1.f - tg[c]) / a0) * inv_n * gscale;
-        }
-    }
+    if (w.p < w.HW)
+        consensus_bce_px(ccjobs::ptr<const float>(t, w.j, 0), ccjobs::ptr<const float>(t, w.j, 1), ccjobs::ptr<const float>(t, w.j, 2),
+                         ccjobs::ptr<const float>(t, w.j, 3), ccjobs::ptr<const float>(t, w.j, 4), ccjobs::ptr<float>(t, w.j, 5), w.b,
+                         w.p, w.HW, {thresh, w0, w1, 1.f / ((float)t.B * 4 * w.HW), gscale}, part[0]);
     cc::block_sum_256<1>(part, red);
-    if (threadIdx.x == 0) ccjobs::ptr<float>(t, j, 6)[local__] = part[0];
+    if (threadIdx.x == 0) ccjobs::ptr<float>(t, w.j, 6)[w.b * w.nb + (w.p >> 8)] = part[0];
 }
 
 // small element-wise glue of train.py:458,475-476,488 over all pyramid levels in one launch (table B = planes per job):
@@ -580,7 +536,8 @@ __global__ __launch_bounds__(256) void k_consensus_bce_jobs(JobTab t, float thre
 //   op 5: out = ((a * 0.5 + 0.5) - mean_c) / std_c, ImageNet statistics, c = plane % 3   slots a, out
 //         (Back2Future.normalize, models/back2future.py:118-132: three images of one step in one launch)
 __global__ __launch_bounds__(256) void k_elementwise_jobs(JobTab t, int op, int c0, int nc, int MC) {
-    CC_JOB_PIXEL(t, j, q, p, HW)
+    const ccjobs::Piece w = ccjobs::piece<false>(t);
+    const int j = w.j, q = w.b, p = w.p, HW = w.HW;
     if (p >= HW) return;
     const size_t i = (size_t)q * HW + p;
     if (op == 0) {
@@ -790,14 +747,9 @@ int cc_scale_acc_jobs(const long* jobs_host, int njobs, const float* scalar_dev,
 /* ---- job-table forms (jobs: HOST array of njobs x 10 longs {slot0..7, H, W}; njobs <= 24; slots per kernel above).
  * The *_fwd_bwd_jobs losses write one partial sum per block into the per-job partial areas, which the caller lays out
  * back to back (job after job) starting at `partials`; one finalize launch adds their sum to loss_accum. */
-static int loss_jobs_tab(ccjobs::JobTab& t, const long* jobs, int njobs, int B) {
-    if (!jobs || njobs <= 0 || njobs > ccjobs::MAXJOBS || B <= 0) return -1;
-    return ccjobs::fill(t, jobs, njobs, B, ccjobs::pix_blocks);
-}
-
 int cc_flow_noocc_jobs(const long* jobs, int njobs, int B, void* stream) {
     ccjobs::JobTab t;
-    const int nblk = loss_jobs_tab(t, jobs, njobs, B);
+    const int nblk = ccjobs::table(t, jobs, njobs, B, ccjobs::pix_blocks);
     if (nblk <= 0) return CC_ERR_ARG;
     hipLaunchKernelGGL(k_flow_noocc_jobs, dim3((unsigned)nblk), dim3(256), 0, (hipStream_t)stream, t);
     CC_CHECK_LAUNCH();
@@ -806,7 +758,7 @@ int cc_flow_noocc_jobs(const long* jobs, int njobs, int B, void* stream) {
 
 int cc_consensus_target_jobs(const long* jobs, int njobs, int B, float wrig, void* stream) {
     ccjobs::JobTab t;
-    const int nblk = loss_jobs_tab(t, jobs, njobs, B);
+    const int nblk = ccjobs::table(t, jobs, njobs, B, ccjobs::pix_blocks);
     if (nblk <= 0) return CC_ERR_ARG;
     hipLaunchKernelGGL(k_consensus_combine_jobs, dim3((unsigned)nblk), dim3(256), 0, (hipStream_t)stream, t, wrig);
     CC_CHECK_LAUNCH();
@@ -815,7 +767,7 @@ int cc_consensus_target_jobs(const long* jobs, int njobs, int B, float wrig, voi
 
 int cc_sum_refs_scale_jobs(const long* jobs, int njobs, int B, int R, int MC, void* stream) {
     ccjobs::JobTab t;
-    const int nblk = loss_jobs_tab(t, jobs, njobs, B);
+    const int nblk = ccjobs::table(t, jobs, njobs, B, ccjobs::pix_blocks);
     if (nblk <= 0) return CC_ERR_ARG;
     hipLaunchKernelGGL(k_sum_refs_scale_jobs, dim3((unsigned)nblk), dim3(256), 0, (hipStream_t)stream, t, R, MC);
     CC_CHECK_LAUNCH();
@@ -824,7 +776,7 @@ int cc_sum_refs_scale_jobs(const long* jobs, int njobs, int B, int R, int MC, vo
 
 int cc_elementwise_jobs(const long* jobs, int njobs, int planes, int op, int c0, int nc, int MC, void* stream) {
     ccjobs::JobTab t;
-    const int nblk = loss_jobs_tab(t, jobs, njobs, planes);
+    const int nblk = ccjobs::table(t, jobs, njobs, planes, ccjobs::pix_blocks);
     if (nblk <= 0 || op < 0 || op > 5) return CC_ERR_ARG;
     hipLaunchKernelGGL(k_elementwise_jobs, dim3((unsigned)nblk), dim3(256), 0, (hipStream_t)stream, t, op, c0, nc, MC);
     CC_CHECK_LAUNCH();
@@ -833,7 +785,7 @@ int cc_elementwise_jobs(const long* jobs, int njobs, int planes, int op, int c0,
 
 size_t cc_loss_jobs_num_blocks(const long* jobs, int njobs, int planes) {
     ccjobs::JobTab t;
-    const int nblk = loss_jobs_tab(t, jobs, njobs, planes);
+    const int nblk = ccjobs::table(t, jobs, njobs, planes, ccjobs::pix_blocks);
     return nblk > 0 ? (size_t)nblk : 0;
 }
 
@@ -842,20 +794,18 @@ int cc_edge_smooth_fwd_bwd_jobs(const long* jobs, int njobs, int B, int C, float
     ccjobs::JobTab t;
     int nblk, npart = -1;
     if (C > 0) {
-        nblk = loss_jobs_tab(t, jobs, njobs, B * C);
+        nblk = ccjobs::table(t, jobs, njobs, B * C, ccjobs::pix_blocks);
         npart = nblk;
     } else {
         // per-job channel counts (slot 4): job j owns B * C_j * ceil(H W / 256) blocks
-        if (C < 0 || !jobs || njobs <= 0 || njobs > ccjobs::MAXJOBS || B <= 0) return CC_ERR_ARG;
-        nblk = ccjobs::fill(t, jobs, njobs, B, ccjobs::pix_blocks);
+        if (C < 0 || ccjobs::table(t, jobs, njobs, B, ccjobs::pix_blocks) < 0) return CC_ERR_ARG;
         int tot = 0;
         npart = 0;
         for (int j = 0; j < njobs; j++) {
             const int cj = (int)t.slot[j][4];
             if (cj <= 0) return CC_ERR_ARG;
-            const int nb1 = ccjobs::pix_blocks(t.H[j], t.W[j]);
-            tot += B * cj * ((nb1 + 3) / 4);          // four 256-pixel pieces per workgroup
-            npart += B * cj * nb1;                    // partial sums keep the 256-pixel layout
+            tot += B * cj * ccjobs::pix_blocks_ppt<4>(t.H[j], t.W[j]);     // four 256-pixel pieces per workgroup
+            npart += B * cj * ccjobs::pix_blocks(t.H[j], t.W[j]);          // partial sums keep the 256-pixel layout
             t.blk_end[j] = tot;
         }
         nblk = tot;
@@ -871,7 +821,7 @@ int cc_edge_smooth_fwd_bwd_jobs(const long* jobs, int njobs, int B, int C, float
 
 int cc_edge_weights_jobs(const long* jobs, int njobs, int B, void* stream) {
     ccjobs::JobTab t;
-    const int nblk = loss_jobs_tab(t, jobs, njobs, B);
+    const int nblk = ccjobs::table(t, jobs, njobs, B, ccjobs::pix_blocks);
     if (nblk <= 0) return CC_ERR_ARG;
     hipLaunchKernelGGL(k_edge_weights_jobs, dim3((unsigned)nblk), dim3(256), 0, (hipStream_t)stream, t);
     CC_CHECK_LAUNCH();
@@ -880,7 +830,7 @@ int cc_edge_weights_jobs(const long* jobs, int njobs, int B, void* stream) {
 
 int cc_bce_ones_fwd_bwd_jobs(const long* jobs, int njobs, int planes, float* partials, float* loss_accum, float gscale, void* stream) {
     ccjobs::JobTab t;
-    const int nblk = loss_jobs_tab(t, jobs, njobs, planes);
+    const int nblk = ccjobs::table(t, jobs, njobs, planes, ccjobs::pix_blocks);
     if (nblk <= 0) return CC_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(k_bce_ones_jobs, dim3((unsigned)nblk), dim3(256), 0, s, t, gscale);
@@ -892,7 +842,7 @@ int cc_bce_ones_fwd_bwd_jobs(const long* jobs, int njobs, int planes, float* par
 int cc_consensus_bce_fwd_bwd_jobs(const long* jobs, int njobs, int B, float* partials, float* loss_accum, float thresh, float wbce,
                                   float gscale, void* stream) {
     ccjobs::JobTab t;
-    const int nblk = loss_jobs_tab(t, jobs, njobs, B);
+    const int nblk = ccjobs::table(t, jobs, njobs, B, ccjobs::pix_blocks);
     if (nblk <= 0) return CC_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(k_consensus_bce_jobs, dim3((unsigned)nblk), dim3(256), 0, s, t, thresh, wbce, 1.f - wbce, gscale);

@@ -655,16 +655,14 @@ __global__ __launch_bounds__(256) void k_photo_finalize(const float* __restrict_
     }
 }
 
-// loss_functions.py:189-193: target = (wrig * min(err_cf, err_cb) * (valid_cf OR valid_cb) <= err_ff + 1e-8)
+// loss_functions.py:189-193 over n elements (ccjobs::consensus_combine_px, jobs.h; the job-table form is in losses.hip)
 __global__ __launch_bounds__(256) void k_consensus_combine(const float* __restrict__ err_cf, const float* __restrict__ err_cb,
                                                            const float* __restrict__ err_ff, const float* __restrict__ v_cf,
                                                            const float* __restrict__ v_cb, float* __restrict__ target,
                                                            float wrig, int n) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    const float valid = 1.f - (1.f - v_cf[i]) * (1.f - v_cb[i]);
-    const float cam_err = fminf(err_cf[i], err_cb[i]) * valid;
-    target[i] = (wrig * cam_err <= (err_ff[i] + 1e-8f)) ? 1.f : 0.f;
+    ccjobs::consensus_combine_px(err_cf, err_cb, err_ff, v_cf, v_cb, target, wrig, (size_t)i);
 }
 
 inline dim3 tile_grid(int B, int H, int W) { return dim3((W + TS - 1) / TS, (H + TS - 1) / TS, B); }
@@ -755,10 +753,10 @@ static int tile_blocks(int H, int W) { return ((W + TS - 1) / TS) * ((H + TS - 1
 int cc_ssim_photo_fwd_jobs(const long* jobs, int njobs, int B, int mask_b_complement, int want_grad, float wssim, float q,
                            float lambda_oob, float* loss_accum, float* scale_out, float* nan_flag, const float* gauss13_host,
                            void* stream) {
-    if (!jobs || njobs <= 0 || njobs > ccjobs::MAXJOBS || B <= 0) return CC_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
     JobTab t;
-    const int nblk = ccjobs::fill(t, jobs, njobs, B, tile_blocks);
+    const int nblk = ccjobs::table(t, jobs, njobs, B, tile_blocks);
+    if (nblk <= 0) return CC_ERR_ARG;
     PhotoCommon c = {mask_b_complement, want_grad, wssim, q};
     hipLaunchKernelGGL(k_ssim_photo_jobs, dim3((unsigned)nblk), dim3(256), 0, s, t, c, make_gauss(gauss13_host));
     hipLaunchKernelGGL(k_photo_finalize_jobs, dim3(1), dim3(1024), 0, s, t, wssim, q, lambda_oob, loss_accum, scale_out, nan_flag);
@@ -767,18 +765,18 @@ int cc_ssim_photo_fwd_jobs(const long* jobs, int njobs, int B, int mask_b_comple
 }
 
 int cc_ssim_photo_bwd_jobs(const long* jobs, int njobs, int B, const float* gauss13_host, void* stream) {
-    if (!jobs || njobs <= 0 || njobs > ccjobs::MAXJOBS || B <= 0) return CC_ERR_ARG;
     JobTab t;
-    const int nblk = ccjobs::fill(t, jobs, njobs, B, tile_blocks);
+    const int nblk = ccjobs::table(t, jobs, njobs, B, tile_blocks);
+    if (nblk <= 0) return CC_ERR_ARG;
     hipLaunchKernelGGL(k_ssim_adjoint_jobs, dim3((unsigned)nblk), dim3(256), 0, (hipStream_t)stream, t, make_gauss(gauss13_host));
     CC_CHECK_LAUNCH();
     return CC_OK;
 }
 
 int cc_ssim_err_fwd_jobs(const long* jobs, int njobs, int B, float wssim, const float* gauss13_host, void* stream) {
-    if (!jobs || njobs <= 0 || njobs > ccjobs::MAXJOBS || B <= 0) return CC_ERR_ARG;
     JobTab t;
-    const int nblk = ccjobs::fill(t, jobs, njobs, B, tile_blocks);
+    const int nblk = ccjobs::table(t, jobs, njobs, B, tile_blocks);
+    if (nblk <= 0) return CC_ERR_ARG;
     hipLaunchKernelGGL(k_ssim_err_jobs, dim3((unsigned)nblk), dim3(256), 0, (hipStream_t)stream, t, wssim, make_gauss(gauss13_host));
     CC_CHECK_LAUNCH();
     return CC_OK;

@@ -142,6 +142,21 @@ __device__ __forceinline__ void rigid_backward(const float* __restrict__ P, cons
 }
 
 // ------------------------------------------------------------------ rigid (inverse_warp / pose2flow)
+// The pixel bodies below are the arithmetic of pixel p of image b, once: the single-call kernel and the job-table kernel of a pair
+// (further down) both call them and keep only where (b, p) comes from, the early exit, the pixels-per-work-item loop, the block
+// reduction and where the partial sums go.
+template <bool AC, bool BORDER>
+__device__ __forceinline__ void inverse_warp_fwd_px(const float* __restrict__ img, const float* __restrict__ depth,
+                                                    const float* __restrict__ P, const float* __restrict__ Kinv,
+                                                    float* __restrict__ out, int C, int b, int p, int H, int W, int HW) {
+    const int y = p / W, x = p - y * W;
+    Rigid r;
+    rigid_project(P + 12 * b, Kinv + 9 * b, (float)x, (float)y, depth[(size_t)b * HW + p], W, H, !BORDER, r);
+    Bilinear t;
+    bilinear_setup<AC, BORDER>(r.xn, r.yn, W, H, t);
+    sample_channels(img + (size_t)b * C * HW, out + (size_t)b * C * HW + p, C, HW, W, t);
+}
+
 template <bool AC, bool BORDER>
 __global__ __launch_bounds__(256) void k_inverse_warp_fwd(const float* __restrict__ img, const float* __restrict__ depth,
                                                           const float* __restrict__ P, const float* __restrict__ Kinv,
@@ -149,14 +164,7 @@ __global__ __launch_bounds__(256) void k_inverse_warp_fwd(const float* __restric
     const int b = blockIdx.y, HW = H * W;
     const int p = blockIdx.x * 256 + threadIdx.x;
     if (p >= HW) return;
-    const int y = p / W, x = p - y * W;
-    Rigid r;
-    rigid_project(P + 12 * b, Kinv + 9 * b, (float)x, (float)y, depth[(size_t)b * HW + p], W, H, !BORDER, r);
-    Bilinear t;
-    bilinear_setup<AC, BORDER>(r.xn, r.yn, W, H, t);
-    const float* src = img + (size_t)b * C * HW;
-    float* dst = out + (size_t)b * C * HW + p;
-    sample_channels(src, dst, C, HW, W, t);
+    inverse_warp_fwd_px<AC, BORDER>(img, depth, P, Kinv, out, C, b, p, H, W, HW);
 }
 
 // d(sum_c gout_c * sample_c)/d(ix, iy) (ATen grid_sampler_2d_backward, bilinear)
@@ -206,6 +214,23 @@ __device__ __forceinline__ void sample_grad(const float* __restrict__ src, const
     }
 }
 
+// -> this pixel's d/d depth and its 12 contributions to dL/dP (assigned, not added: the caller sums)
+template <bool AC, bool BORDER>
+__device__ __forceinline__ void inverse_warp_bwd_px(const float* __restrict__ gout, const float* __restrict__ img,
+                                                    const float* __restrict__ depth, const float* __restrict__ P,
+                                                    const float* __restrict__ Kinv, float* __restrict__ gimg, int C, int b, int p,
+                                                    int H, int W, int HW, float& gd, float (&gP)[12]) {
+    const int y = p / W, x = p - y * W;
+    Rigid r;
+    rigid_project(P + 12 * b, Kinv + 9 * b, (float)x, (float)y, depth[(size_t)b * HW + p], W, H, !BORDER, r);
+    Bilinear t;
+    bilinear_setup<AC, BORDER>(r.xn, r.yn, W, H, t);
+    float gix, giy;
+    sample_grad(img + (size_t)b * C * HW, gout + (size_t)b * C * HW + p, C, HW, W, t, gimg ? gimg + (size_t)b * C * HW : nullptr, gix,
+                giy);
+    rigid_backward(P + 12 * b, r, gix * t.gmx, giy * t.gmy, W, H, gd, gP);
+}
+
 template <bool AC, bool BORDER>
 __global__ __launch_bounds__(256) void k_inverse_warp_bwd(const float* __restrict__ gout, const float* __restrict__ img,
                                                           const float* __restrict__ depth, const float* __restrict__ P,
@@ -219,15 +244,8 @@ __global__ __launch_bounds__(256) void k_inverse_warp_bwd(const float* __restric
 #pragma unroll
     for (int i = 0; i < 12; i++) gP[i] = 0.f;
     if (p < HW) {
-        const int y = p / W, x = p - y * W;
-        Rigid r;
-        rigid_project(P + 12 * b, Kinv + 9 * b, (float)x, (float)y, depth[(size_t)b * HW + p], W, H, !BORDER, r);
-        Bilinear t;
-        bilinear_setup<AC, BORDER>(r.xn, r.yn, W, H, t);
-        float gix, giy, gd;
-        sample_grad(img + (size_t)b * C * HW, gout + (size_t)b * C * HW + p, C, HW, W, t,
-                    gimg ? gimg + (size_t)b * C * HW : nullptr, gix, giy);
-        rigid_backward(P + 12 * b, r, gix * t.gmx, giy * t.gmy, W, H, gd, gP);
+        float gd;
+        inverse_warp_bwd_px<AC, BORDER>(gout, img, depth, P, Kinv, gimg, C, b, p, H, W, HW, gd, gP);
         gdepth[(size_t)b * HW + p] = gd;
     }
     cc::block_sum_256<12>(gP, red);
@@ -258,18 +276,24 @@ __global__ __launch_bounds__(64) void k_reduce_gP(const float* __restrict__ part
     }
 }
 
-__global__ __launch_bounds__(256) void k_pose2flow_fwd(const float* __restrict__ depth, const float* __restrict__ P,
-                                                       const float* __restrict__ Kinv, float* __restrict__ flow, int H,
-                                                       int W, int rewrite) {
-    const int b = blockIdx.y, HW = H * W;
-    const int p = blockIdx.x * 256 + threadIdx.x;
-    if (p >= HW) return;
+__device__ __forceinline__ void pose2flow_fwd_px(const float* __restrict__ depth, const float* __restrict__ P,
+                                                 const float* __restrict__ Kinv, float* __restrict__ flow, int rewrite, int b, int p,
+                                                 int H, int W, int HW) {
     const int y = p / W, x = p - y * W;
     Rigid r;
     rigid_project(P + 12 * b, Kinv + 9 * b, (float)x, (float)y, depth[(size_t)b * HW + p], W, H, rewrite != 0, r);
     // inverse_warp.py:217-218
     flow[((size_t)b * 2 + 0) * HW + p] = (float)(W - 1) * (r.xn / 2.0f + 0.5f) - (float)x;
     flow[((size_t)b * 2 + 1) * HW + p] = (float)(H - 1) * (r.yn / 2.0f + 0.5f) - (float)y;
+}
+
+__global__ __launch_bounds__(256) void k_pose2flow_fwd(const float* __restrict__ depth, const float* __restrict__ P,
+                                                       const float* __restrict__ Kinv, float* __restrict__ flow, int H,
+                                                       int W, int rewrite) {
+    const int b = blockIdx.y, HW = H * W;
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= HW) return;
+    pose2flow_fwd_px(depth, P, Kinv, flow, rewrite, b, p, H, W, HW);
 }
 
 __global__ __launch_bounds__(256) void k_pose2flow_bwd(const float* __restrict__ gflow, const float* __restrict__ depth,
@@ -319,25 +343,55 @@ __device__ __forceinline__ void flow_coords(float x, float y, float u, float v, 
     }
 }
 
-// fs: constant the flow is multiplied by first (Back2Future warps with `up_flow * 0.625 ...` / its negation, back2future.py:196-285)
+// fs: constant the flow is multiplied by first (Back2Future warps with `up_flow * 0.625 ...` / its negation, back2future.py:196-285;
+// 1 in the job-table form).  The pixel's sampling taps and d(xn, yn)/d(u, v):
+template <bool AC, bool BORDER, bool FEATURE>
+__device__ __forceinline__ void flow_taps(const float* __restrict__ flow, float fs, int b, int p, int H, int W, int HW, Bilinear& t,
+                                          float& dxn, float& dyn) {
+    const int y = p / W, x = p - y * W;
+    float xn, yn;
+    flow_coords<FEATURE>((float)x, (float)y, flow[((size_t)b * 2) * HW + p] * fs, flow[((size_t)b * 2 + 1) * HW + p] * fs, W, H, xn,
+                         yn, dxn, dyn);
+    bilinear_setup<AC, BORDER>(xn, yn, W, H, t);
+}
+
+// channels [c0, c0 + nc) of the warped image
+template <bool AC, bool BORDER, bool FEATURE>
+__device__ __forceinline__ void flow_warp_fwd_px(const float* __restrict__ img, const float* __restrict__ flow,
+                                                 float* __restrict__ out, int C, int c0, int nc, float fs, int b, int p, int H, int W,
+                                                 int HW) {
+    Bilinear t;
+    float dxn, dyn;
+    flow_taps<AC, BORDER, FEATURE>(flow, fs, b, p, H, W, HW, t, dxn, dyn);
+    const float* src = img + (size_t)b * C * HW;
+    float* dst = out + (size_t)b * C * HW + p;
+    sample_channels(src + (size_t)c0 * HW, dst + (size_t)c0 * HW, nc, HW, W, t);
+}
+
+// -> this pixel's d/d flow
+template <bool AC, bool BORDER, bool FEATURE>
+__device__ __forceinline__ void flow_warp_bwd_px(const float* __restrict__ gout, const float* __restrict__ img,
+                                                 const float* __restrict__ flow, float* __restrict__ gimg, int C, float fs, int b, int p,
+                                                 int H, int W, int HW, float& gu, float& gv) {
+    Bilinear t;
+    float dxn, dyn, gix, giy;
+    flow_taps<AC, BORDER, FEATURE>(flow, fs, b, p, H, W, HW, t, dxn, dyn);
+    sample_grad(img + (size_t)b * C * HW, gout + (size_t)b * C * HW + p, C, HW, W, t, gimg ? gimg + (size_t)b * C * HW : nullptr, gix,
+                giy);
+    gu = gix * t.gmx * dxn * fs;
+    gv = giy * t.gmy * dyn * fs;
+}
+
 template <bool AC, bool BORDER, bool FEATURE>
 __global__ __launch_bounds__(256) void k_flow_warp_fwd(const float* __restrict__ img, const float* __restrict__ flow,
                                                        float* __restrict__ out, int C, int H, int W, float fs) {
     const int b = blockIdx.y, HW = H * W;
     const int p = blockIdx.x * 256 + threadIdx.x;
     if (p >= HW) return;
-    const int y = p / W, x = p - y * W;
-    float xn, yn, dxn, dyn;
-    flow_coords<FEATURE>((float)x, (float)y, flow[((size_t)b * 2) * HW + p] * fs, flow[((size_t)b * 2 + 1) * HW + p] * fs, W, H, xn,
-                         yn, dxn, dyn);
-    Bilinear t;
-    bilinear_setup<AC, BORDER>(xn, yn, W, H, t);
-    const float* src = img + (size_t)b * C * HW;
-    float* dst = out + (size_t)b * C * HW + p;
     // gridDim.z > 1: channel groups (many-channel feature maps on small pyramid levels need more than HW work-items)
     const int cper = (C + (int)gridDim.z - 1) / (int)gridDim.z;
     const int c0 = (int)blockIdx.z * cper, c1 = (c0 + cper < C) ? c0 + cper : C;
-    if (c0 < c1) sample_channels(src + (size_t)c0 * HW, dst + (size_t)c0 * HW, c1 - c0, HW, W, t);
+    flow_warp_fwd_px<AC, BORDER, FEATURE>(img, flow, out, C, c0, c1 - c0, fs, b, p, H, W, HW);
 }
 
 template <bool AC, bool BORDER, bool FEATURE>
@@ -347,18 +401,11 @@ __global__ __launch_bounds__(256) void k_flow_warp_bwd(const float* __restrict__
     const int b = blockIdx.y, HW = H * W;
     const int p = blockIdx.x * 256 + threadIdx.x;
     if (p >= HW) return;
-    const int y = p / W, x = p - y * W;
-    float xn, yn, dxn, dyn;
-    flow_coords<FEATURE>((float)x, (float)y, flow[((size_t)b * 2) * HW + p] * fs, flow[((size_t)b * 2 + 1) * HW + p] * fs, W, H, xn,
-                         yn, dxn, dyn);
-    Bilinear t;
-    bilinear_setup<AC, BORDER>(xn, yn, W, H, t);
-    float gix, giy;
-    sample_grad(img + (size_t)b * C * HW, gout + (size_t)b * C * HW + p, C, HW, W, t,
-                gimg ? gimg + (size_t)b * C * HW : nullptr, gix, giy);
+    float gu, gv;
+    flow_warp_bwd_px<AC, BORDER, FEATURE>(gout, img, flow, gimg, C, fs, b, p, H, W, HW, gu, gv);
     if (gflow) {
-        gflow[((size_t)b * 2) * HW + p] = gix * t.gmx * dxn * fs;
-        gflow[((size_t)b * 2 + 1) * HW + p] = giy * t.gmy * dyn * fs;
+        gflow[((size_t)b * 2) * HW + p] = gu;
+        gflow[((size_t)b * 2 + 1) * HW + p] = gv;
     }
 }
 
@@ -414,19 +461,9 @@ __global__ __launch_bounds__(256) void k_feature_warp_bwd4(const float* __restri
 // loss_functions.py:132-137 depth_occlusion_masks in ONE pass: the four rigid flows (pose2flow with the full-resolution K,
 // inverse_warp.py:195-220, no OOB rewrite) stay in registers, then occlusion_masks (:343-352) on the pairs (1,2) and (0,3)
 // -> (1 - occ) for refs 0..3, [B,4,H,W].  Replaces 4 cc_pose2flow_fwd launches + cc_rigid_noocc and the [4,B,2,H,W] buffer.
-__device__ __forceinline__ float noocc_pair(float bu, float bv, float fu, float fv) {
-    const float mag = (fu * fu + fv * fv) + (bu * bu + bv * bv);
-    const float thr = 0.08f * mag + 1.0f;
-    const float s = (fu + bu) + (fv + bv);
-    return (s > thr) ? 0.f : 1.f;
-}
-
-__global__ __launch_bounds__(256) void k_rigid_noocc_fused(const float* __restrict__ depth, const float* __restrict__ P4,
-                                                           const float* __restrict__ Kinv, float* __restrict__ out, int B, int H,
-                                                           int W) {
-    const int b = blockIdx.y, HW = H * W;
-    const int p = blockIdx.x * 256 + threadIdx.x;
-    if (p >= HW) return;
+__device__ __forceinline__ void rigid_noocc_px(const float* __restrict__ depth, const float* __restrict__ P4,
+                                               const float* __restrict__ Kinv, float* __restrict__ out, int B, int b, int p, int H,
+                                               int W, int HW) {
     const int y = p / W, x = p - y * W;
     const float d = depth[(size_t)b * HW + p];
     float u[4], v[4];
@@ -437,8 +474,8 @@ __global__ __launch_bounds__(256) void k_rigid_noocc_fused(const float* __restri
         u[r] = (float)(W - 1) * (rg.xn / 2.0f + 0.5f) - (float)x;
         v[r] = (float)(H - 1) * (rg.yn / 2.0f + 0.5f) - (float)y;
     }
-    const float m12 = noocc_pair(u[1], v[1], u[2], v[2]);
-    const float m03 = noocc_pair(u[0], v[0], u[3], v[3]);
+    const float m12 = ccjobs::noocc(u[1], v[1], u[2], v[2]);
+    const float m03 = ccjobs::noocc(u[0], v[0], u[3], v[3]);
     float* o = out + (size_t)b * 4 * HW + p;
     o[0] = m03;
     o[HW] = m12;
@@ -446,40 +483,36 @@ __global__ __launch_bounds__(256) void k_rigid_noocc_fused(const float* __restri
     o[3 * HW] = m03;
 }
 
+__global__ __launch_bounds__(256) void k_rigid_noocc_fused(const float* __restrict__ depth, const float* __restrict__ P4,
+                                                           const float* __restrict__ Kinv, float* __restrict__ out, int B, int H,
+                                                           int W) {
+    const int b = blockIdx.y, HW = H * W;
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= HW) return;
+    rigid_noocc_px(depth, P4, Kinv, out, B, b, p, H, W, HW);
+}
+
 // ------------------------------------------------------------------ job-table forms (all pyramid levels x reference frames
-// of one loss in ONE launch; jobs.h).  Same per-pixel arithmetic as the single-call kernels above (shared device functions).
+// of one loss in ONE launch; jobs.h).  Each kernel finds its job and pieces (ccjobs::pieces / piece), reads the job's slots and
+// calls the pixel body of its single-call kernel above: there is no second copy of the per-pixel arithmetic.
 // Round 5: WPPT pixels per work-item, 256 apart (a workgroup = WPPT consecutive 256-pixel pieces of one image).  The 24 jobs of a
 // loss pass are 9-18 k workgroups of 256 pixels; job search, slot pointers, the P / Kinv rows and (backward) the block reduction are
 // per-workgroup costs, and the pixels of a work-item are independent load chains (measured on the smoothness kernel: 99 -> 57 us).
 constexpr int WPPT = 4;
-#define CC_WARP_JOB_BLOCK(t, j, b, blk, H, W, HW, nb1)                                      \
-    int local__;                                                                            \
-    const int j = ccjobs::find_xcd(t, (int)blockIdx.x, local__);                            \
-    const int H = t.H[j], W = t.W[j], HW = H * W, nb1 = (HW + 255) >> 8;                    \
-    const int nb4__ = (nb1 + WPPT - 1) / WPPT;                                              \
-    const int b = local__ / nb4__, blk = local__ - b * nb4__;
-
 // rigid fwd slots: 0 img [B,C,H,W], 1 depth [B,H,W], 2 P [B,12], 3 Kinv [B,9], 4 out
 template <bool AC, bool BORDER>
 __global__ __launch_bounds__(256) void k_inverse_warp_fwd_jobs(JobTab t, int C) {
-    CC_WARP_JOB_BLOCK(t, j, b, blk, H, W, HW, nb1)
-    const float* __restrict__ img = ccjobs::ptr<const float>(t, j, 0);
-    const float* __restrict__ depth = ccjobs::ptr<const float>(t, j, 1);
-    const float* __restrict__ P = ccjobs::ptr<const float>(t, j, 2);
-    const float* __restrict__ Kinv = ccjobs::ptr<const float>(t, j, 3);
-    float* __restrict__ out = ccjobs::ptr<float>(t, j, 4);
-    const float* src = img + (size_t)b * C * HW;
+    const ccjobs::Pieces w = ccjobs::pieces<WPPT, true>(t);
+    const float* __restrict__ img = ccjobs::ptr<const float>(t, w.j, 0);
+    const float* __restrict__ depth = ccjobs::ptr<const float>(t, w.j, 1);
+    const float* __restrict__ P = ccjobs::ptr<const float>(t, w.j, 2);
+    const float* __restrict__ Kinv = ccjobs::ptr<const float>(t, w.j, 3);
+    float* __restrict__ out = ccjobs::ptr<float>(t, w.j, 4);
 #pragma unroll
     for (int k = 0; k < WPPT; k++) {
-        const int p = (blk * WPPT + k) * 256 + (int)threadIdx.x;
-        if (p >= HW) break;
-        const int y = p / W, x = p - y * W;
-        Rigid r;
-        rigid_project(P + 12 * b, Kinv + 9 * b, (float)x, (float)y, depth[(size_t)b * HW + p], W, H, !BORDER, r);
-        Bilinear bl;
-        bilinear_setup<AC, BORDER>(r.xn, r.yn, W, H, bl);
-        float* dst = out + (size_t)b * C * HW + p;
-        sample_channels(src, dst, C, HW, W, bl);
+        const int p = (w.blk * WPPT + k) * 256 + (int)threadIdx.x;
+        if (p >= w.HW) break;
+        inverse_warp_fwd_px<AC, BORDER>(img, depth, P, Kinv, out, C, w.b, p, w.H, w.W, w.HW);
     }
 }
 
@@ -487,42 +520,35 @@ __global__ __launch_bounds__(256) void k_inverse_warp_fwd_jobs(JobTab t, int C) 
 template <bool AC, bool BORDER>
 __global__ __launch_bounds__(256) void k_inverse_warp_bwd_jobs(JobTab t, int C) {
     __shared__ float red[4 * 12];
-    CC_WARP_JOB_BLOCK(t, j, b, blk, H, W, HW, nb)
-    const float* __restrict__ gout = ccjobs::ptr<const float>(t, j, 0);
-    const float* __restrict__ img = ccjobs::ptr<const float>(t, j, 1);
-    const float* __restrict__ depth = ccjobs::ptr<const float>(t, j, 2);
-    const float* __restrict__ P = ccjobs::ptr<const float>(t, j, 3);
-    const float* __restrict__ Kinv = ccjobs::ptr<const float>(t, j, 4);
-    float* __restrict__ gdepth = ccjobs::ptr<float>(t, j, 5);
-    float* __restrict__ gP_part = ccjobs::ptr<float>(t, j, 6);
+    const ccjobs::Pieces w = ccjobs::pieces<WPPT, true>(t);
+    const float* __restrict__ gout = ccjobs::ptr<const float>(t, w.j, 0);
+    const float* __restrict__ img = ccjobs::ptr<const float>(t, w.j, 1);
+    const float* __restrict__ depth = ccjobs::ptr<const float>(t, w.j, 2);
+    const float* __restrict__ P = ccjobs::ptr<const float>(t, w.j, 3);
+    const float* __restrict__ Kinv = ccjobs::ptr<const float>(t, w.j, 4);
+    float* __restrict__ gdepth = ccjobs::ptr<float>(t, w.j, 5);
+    float* __restrict__ gP_part = ccjobs::ptr<float>(t, w.j, 6);
     float gP[12];
 #pragma unroll
     for (int i = 0; i < 12; i++) gP[i] = 0.f;
 #pragma unroll
     for (int k = 0; k < WPPT; k++) {
-        const int p = (blk * WPPT + k) * 256 + (int)threadIdx.x;
-        if (p < HW) {
-            const int y = p / W, x = p - y * W;
-            Rigid r;
-            rigid_project(P + 12 * b, Kinv + 9 * b, (float)x, (float)y, depth[(size_t)b * HW + p], W, H, !BORDER, r);
-            Bilinear bl;
-            bilinear_setup<AC, BORDER>(r.xn, r.yn, W, H, bl);
-            float gix, giy, gd;
-            sample_grad(img + (size_t)b * C * HW, gout + (size_t)b * C * HW + p, C, HW, W, bl, nullptr, gix, giy);
-            float g1[12];                                 // (rigid_backward assigns: this pixel's contribution)
-            rigid_backward(P + 12 * b, r, gix * bl.gmx, giy * bl.gmy, W, H, gd, g1);
+        const int p = (w.blk * WPPT + k) * 256 + (int)threadIdx.x;
+        if (p < w.HW) {
+            float gd, g1[12];
+            inverse_warp_bwd_px<AC, BORDER>(gout, img, depth, P, Kinv, nullptr, C, w.b, p, w.H, w.W, w.HW, gd, g1);
 #pragma unroll
             for (int i = 0; i < 12; i++) gP[i] += g1[i];
-            gdepth[(size_t)b * HW + p] = gd;
+            gdepth[(size_t)w.b * w.HW + p] = gd;
         }
     }
     cc::block_sum_256<12>(gP, red);
     // the pose-gradient partials keep their [B][ceil(HW / 256)][12] layout (the host sizes it, k_pose_grad_jobs sums it): this
     // workgroup's sums go to the first of its WPPT rows, zeros to the others
     if ((int)threadIdx.x < WPPT) {
-        const int row = blk * WPPT + (int)threadIdx.x;
-        if (row < nb) {
-            float* o = gP_part + ((size_t)b * nb + row) * 12;
+        const int row = w.blk * WPPT + (int)threadIdx.x;
+        if (row < w.nb) {
+            float* o = gP_part + ((size_t)w.b * w.nb + row) * 12;
 #pragma unroll
             for (int i = 0; i < 12; i++) o[i] = threadIdx.x == 0 ? gP[i] : 0.f;
         }
@@ -532,95 +558,51 @@ __global__ __launch_bounds__(256) void k_inverse_warp_bwd_jobs(JobTab t, int C) 
 // flow fwd slots: 0 img, 1 flow [B,2,H,W], 2 out;   flow bwd slots: 0 gout, 1 img, 2 flow, 3 gflow
 template <bool AC, bool BORDER>
 __global__ __launch_bounds__(256) void k_flow_warp_fwd_jobs(JobTab t, int C) {
-    CC_WARP_JOB_BLOCK(t, j, b, blk, H, W, HW, nb1)
-    const float* __restrict__ img = ccjobs::ptr<const float>(t, j, 0);
-    const float* __restrict__ flow = ccjobs::ptr<const float>(t, j, 1);
-    float* __restrict__ out = ccjobs::ptr<float>(t, j, 2);
-    const float* src = img + (size_t)b * C * HW;
+    const ccjobs::Pieces w = ccjobs::pieces<WPPT, true>(t);
+    const float* __restrict__ img = ccjobs::ptr<const float>(t, w.j, 0);
+    const float* __restrict__ flow = ccjobs::ptr<const float>(t, w.j, 1);
+    float* __restrict__ out = ccjobs::ptr<float>(t, w.j, 2);
 #pragma unroll
     for (int k = 0; k < WPPT; k++) {
-        const int p = (blk * WPPT + k) * 256 + (int)threadIdx.x;
-        if (p >= HW) break;
-        const int y = p / W, x = p - y * W;
-        float xn, yn, dxn, dyn;
-        flow_coords<false>((float)x, (float)y, flow[((size_t)b * 2) * HW + p], flow[((size_t)b * 2 + 1) * HW + p], W, H, xn, yn, dxn, dyn);
-        Bilinear bl;
-        bilinear_setup<AC, BORDER>(xn, yn, W, H, bl);
-        float* dst = out + (size_t)b * C * HW + p;
-        sample_channels(src, dst, C, HW, W, bl);
+        const int p = (w.blk * WPPT + k) * 256 + (int)threadIdx.x;
+        if (p >= w.HW) break;
+        flow_warp_fwd_px<AC, BORDER, false>(img, flow, out, C, 0, C, 1.f, w.b, p, w.H, w.W, w.HW);
     }
 }
 
 template <bool AC, bool BORDER>
 __global__ __launch_bounds__(256) void k_flow_warp_bwd_jobs(JobTab t, int C) {
     // (one pixel per work-item: with WPPT = 4 this kernel was slower, 26.0 vs 23.4 us -- no block reduction to amortise)
-    int local;
-    const int j = ccjobs::find_xcd(t, (int)blockIdx.x, local);
-    const int H = t.H[j], W = t.W[j], HW = H * W, nb = (HW + 255) >> 8;
-    const int b = local / nb, p = (local - b * nb) * 256 + (int)threadIdx.x;
-    if (p >= HW) return;
-    const float* __restrict__ gout = ccjobs::ptr<const float>(t, j, 0);
-    const float* __restrict__ img = ccjobs::ptr<const float>(t, j, 1);
-    const float* __restrict__ flow = ccjobs::ptr<const float>(t, j, 2);
-    float* __restrict__ gflow = ccjobs::ptr<float>(t, j, 3);
-    const int y = p / W, x = p - y * W;
-    float xn, yn, dxn, dyn;
-    flow_coords<false>((float)x, (float)y, flow[((size_t)b * 2) * HW + p], flow[((size_t)b * 2 + 1) * HW + p], W, H, xn, yn, dxn, dyn);
-    Bilinear bl;
-    bilinear_setup<AC, BORDER>(xn, yn, W, H, bl);
-    float gix, giy;
-    sample_grad(img + (size_t)b * C * HW, gout + (size_t)b * C * HW + p, C, HW, W, bl, nullptr, gix, giy);
-    gflow[((size_t)b * 2) * HW + p] = gix * bl.gmx * dxn;
-    gflow[((size_t)b * 2 + 1) * HW + p] = giy * bl.gmy * dyn;
+    const ccjobs::Piece w = ccjobs::piece<true>(t);
+    if (w.p >= w.HW) return;
+    float* __restrict__ gflow = ccjobs::ptr<float>(t, w.j, 3);
+    float gu, gv;
+    flow_warp_bwd_px<AC, BORDER, false>(ccjobs::ptr<const float>(t, w.j, 0), ccjobs::ptr<const float>(t, w.j, 1),
+                                        ccjobs::ptr<const float>(t, w.j, 2), nullptr, C, 1.f, w.b, w.p, w.H, w.W, w.HW, gu, gv);
+    gflow[((size_t)w.b * 2) * w.HW + w.p] = gu;
+    gflow[((size_t)w.b * 2 + 1) * w.HW + w.p] = gv;
 }
 
 // depth_occlusion_masks of every level: slots 0 depth [B,H,W], 1 P4 [4,B,12] (full-resolution K, Q4), 2 Kinv, 3 out [B,4,H,W]
 __global__ __launch_bounds__(256) void k_rigid_noocc_jobs(JobTab t) {
-    int first;
-    const int j = ccjobs::find(t, (int)blockIdx.x, first);
-    const int H = t.H[j], W = t.W[j], HW = H * W, nb = (HW + 255) >> 8;
-    const int local = (int)blockIdx.x - first;
-    const int b = local / nb, p = (local - b * nb) * 256 + (int)threadIdx.x;
-    if (p >= HW) return;
-    const float* __restrict__ depth = ccjobs::ptr<const float>(t, j, 0);
-    const float* __restrict__ P4 = ccjobs::ptr<const float>(t, j, 1);
-    const float* __restrict__ Kinv = ccjobs::ptr<const float>(t, j, 2);
-    float* __restrict__ out = ccjobs::ptr<float>(t, j, 3);
-    const int y = p / W, x = p - y * W;
-    const float d = depth[(size_t)b * HW + p];
-    float u[4], v[4];
-#pragma unroll
-    for (int r = 0; r < 4; r++) {
-        Rigid rg;
-        rigid_project(P4 + ((size_t)r * t.B + b) * 12, Kinv + 9 * b, (float)x, (float)y, d, W, H, false, rg);
-        u[r] = (float)(W - 1) * (rg.xn / 2.0f + 0.5f) - (float)x;
-        v[r] = (float)(H - 1) * (rg.yn / 2.0f + 0.5f) - (float)y;
-    }
-    const float m12 = noocc_pair(u[1], v[1], u[2], v[2]);
-    const float m03 = noocc_pair(u[0], v[0], u[3], v[3]);
-    float* o = out + (size_t)b * 4 * HW + p;
-    o[0] = m03;
-    o[HW] = m12;
-    o[2 * HW] = m12;
-    o[3 * HW] = m03;
+    const ccjobs::Piece w = ccjobs::piece<false>(t);
+    if (w.p >= w.HW) return;
+    rigid_noocc_px(ccjobs::ptr<const float>(t, w.j, 0), ccjobs::ptr<const float>(t, w.j, 1), ccjobs::ptr<const float>(t, w.j, 2),
+                   ccjobs::ptr<float>(t, w.j, 3), t.B, w.b, w.p, w.H, w.W, w.HW);
 }
 
 // pose2flow of every level (train.py:470-471 flows_cam_fwd / _bwd): slots 0 depth, 1 P [B,12], 2 Kinv, 3 flow [B,2,H,W]
 __global__ __launch_bounds__(256) void k_pose2flow_fwd_jobs(JobTab t, int rewrite) {
-    CC_WARP_JOB_BLOCK(t, j, b, blk, H, W, HW, nb1)
-    const float* __restrict__ depth = ccjobs::ptr<const float>(t, j, 0);
-    const float* __restrict__ P = ccjobs::ptr<const float>(t, j, 1);
-    const float* __restrict__ Kinv = ccjobs::ptr<const float>(t, j, 2);
-    float* __restrict__ flow = ccjobs::ptr<float>(t, j, 3);
+    const ccjobs::Pieces w = ccjobs::pieces<WPPT, true>(t);
+    const float* __restrict__ depth = ccjobs::ptr<const float>(t, w.j, 0);
+    const float* __restrict__ P = ccjobs::ptr<const float>(t, w.j, 1);
+    const float* __restrict__ Kinv = ccjobs::ptr<const float>(t, w.j, 2);
+    float* __restrict__ flow = ccjobs::ptr<float>(t, w.j, 3);
 #pragma unroll
     for (int k = 0; k < WPPT; k++) {
-        const int p = (blk * WPPT + k) * 256 + (int)threadIdx.x;
-        if (p >= HW) break;
-        const int y = p / W, x = p - y * W;
-        Rigid r;
-        rigid_project(P + 12 * b, Kinv + 9 * b, (float)x, (float)y, depth[(size_t)b * HW + p], W, H, rewrite != 0, r);
-        flow[((size_t)b * 2 + 0) * HW + p] = (float)(W - 1) * (r.xn / 2.0f + 0.5f) - (float)x;
-        flow[((size_t)b * 2 + 1) * HW + p] = (float)(H - 1) * (r.yn / 2.0f + 0.5f) - (float)y;
+        const int p = (w.blk * WPPT + k) * 256 + (int)threadIdx.x;
+        if (p >= w.HW) break;
+        pose2flow_fwd_px(depth, P, Kinv, flow, rewrite, w.b, p, w.H, w.W, w.HW);
     }
 }
 
@@ -800,15 +782,18 @@ __global__ __launch_bounds__(256) void k_fx_to_float(const unsigned long long* _
 
 }  // namespace
 
-#define CC_DISPATCH_AC_PAD(KERN, ac, border, ...)                                                            \
+// launch KERN<ac, MORE...> / KERN<ac, border, MORE...> with the run-time flags as template arguments.  MORE: the template arguments
+// behind them, in parentheses with their leading comma -- () for none, (, false) for one
+#define CC_UNPAREN(...) __VA_ARGS__
+#define CC_DISPATCH_AC(KERN, MORE, ac, ...)                                                                  \
     do {                                                                                                     \
-        if (ac) {                                                                                            \
-            if (border) hipLaunchKernelGGL(HIP_KERNEL_NAME(KERN<true, true>), __VA_ARGS__);                  \
-            else hipLaunchKernelGGL(HIP_KERNEL_NAME(KERN<true, false>), __VA_ARGS__);                        \
-        } else {                                                                                             \
-            if (border) hipLaunchKernelGGL(HIP_KERNEL_NAME(KERN<false, true>), __VA_ARGS__);                 \
-            else hipLaunchKernelGGL(HIP_KERNEL_NAME(KERN<false, false>), __VA_ARGS__);                       \
-        }                                                                                                    \
+        if (ac) hipLaunchKernelGGL(HIP_KERNEL_NAME(KERN<true CC_UNPAREN MORE>), __VA_ARGS__);                \
+        else hipLaunchKernelGGL(HIP_KERNEL_NAME(KERN<false CC_UNPAREN MORE>), __VA_ARGS__);                  \
+    } while (0)
+#define CC_DISPATCH_AC_PAD(KERN, MORE, ac, border, ...)                                                      \
+    do {                                                                                                     \
+        if (border) CC_DISPATCH_AC(KERN, (, true CC_UNPAREN MORE), ac, __VA_ARGS__);                         \
+        else CC_DISPATCH_AC(KERN, (, false CC_UNPAREN MORE), ac, __VA_ARGS__);                               \
     } while (0)
 
 extern "C" {
@@ -860,7 +845,7 @@ int cc_inverse_warp_fwd(const float* img, const float* depth, const float* P, co
                         int H, int W, int padding_border, int align_corners, void* stream) {
     if (B <= 0 || C <= 0 || H < 2 || W < 2) return CC_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
-    CC_DISPATCH_AC_PAD(k_inverse_warp_fwd, align_corners, padding_border, pix_grid(B, H, W), dim3(256), 0, s, img, depth,
+    CC_DISPATCH_AC_PAD(k_inverse_warp_fwd, (), align_corners, padding_border, pix_grid(B, H, W), dim3(256), 0, s, img, depth,
                        P, Kinv, out, C, H, W);
     CC_CHECK_LAUNCH();
     return CC_OK;
@@ -872,7 +857,7 @@ int cc_inverse_warp_bwd(const float* gout, const float* img, const float* depth,
     if (B <= 0 || C <= 0 || H < 2 || W < 2) return CC_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
     dim3 g = pix_grid(B, H, W);
-    CC_DISPATCH_AC_PAD(k_inverse_warp_bwd, align_corners, padding_border, g, dim3(256), 0, s, gout, img, depth, P, Kinv,
+    CC_DISPATCH_AC_PAD(k_inverse_warp_bwd, (), align_corners, padding_border, g, dim3(256), 0, s, gout, img, depth, P, Kinv,
                        gdepth, ws_partials, gimg_or_null, C, H, W);
     hipLaunchKernelGGL(k_reduce_gP, dim3(B), dim3(64), 0, s, (const float*)ws_partials, gP, (int)g.x, 0);
     CC_CHECK_LAUNCH();
@@ -911,13 +896,7 @@ int cc_flow_warp_fwd(const float* img, const float* flow, float* out, int B, int
     if (B <= 0 || C <= 0 || H < 2 || W < 2) return CC_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
     dim3 g = pix_grid(B, H, W);
-    if (align_corners) {
-        if (padding_border) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_flow_warp_fwd<true, true, false>), g, dim3(256), 0, s, img, flow, out, C, H, W, 1.f);
-        else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_flow_warp_fwd<true, false, false>), g, dim3(256), 0, s, img, flow, out, C, H, W, 1.f);
-    } else {
-        if (padding_border) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_flow_warp_fwd<false, true, false>), g, dim3(256), 0, s, img, flow, out, C, H, W, 1.f);
-        else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_flow_warp_fwd<false, false, false>), g, dim3(256), 0, s, img, flow, out, C, H, W, 1.f);
-    }
+    CC_DISPATCH_AC_PAD(k_flow_warp_fwd, (, false), align_corners, padding_border, g, dim3(256), 0, s, img, flow, out, C, H, W, 1.f);
     CC_CHECK_LAUNCH();
     return CC_OK;
 }
@@ -927,13 +906,8 @@ int cc_flow_warp_bwd(const float* gout, const float* img, const float* flow, flo
     if (B <= 0 || C <= 0 || H < 2 || W < 2) return CC_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
     dim3 g = pix_grid(B, H, W);
-    if (align_corners) {
-        if (padding_border) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_flow_warp_bwd<true, true, false>), g, dim3(256), 0, s, gout, img, flow, gflow_or_null, gimg_or_null, C, H, W, 1.f);
-        else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_flow_warp_bwd<true, false, false>), g, dim3(256), 0, s, gout, img, flow, gflow_or_null, gimg_or_null, C, H, W, 1.f);
-    } else {
-        if (padding_border) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_flow_warp_bwd<false, true, false>), g, dim3(256), 0, s, gout, img, flow, gflow_or_null, gimg_or_null, C, H, W, 1.f);
-        else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_flow_warp_bwd<false, false, false>), g, dim3(256), 0, s, gout, img, flow, gflow_or_null, gimg_or_null, C, H, W, 1.f);
-    }
+    CC_DISPATCH_AC_PAD(k_flow_warp_bwd, (, false), align_corners, padding_border, g, dim3(256), 0, s, gout, img, flow, gflow_or_null,
+                       gimg_or_null, C, H, W, 1.f);
     CC_CHECK_LAUNCH();
     return CC_OK;
 }
@@ -945,8 +919,7 @@ int cc_feature_warp_fwd(const float* feat, const float* flow, float* out, int B,
     hipStream_t s = (hipStream_t)stream;
     dim3 g = pix_grid(B, H, W);
     if (C >= 16) g.z = 4;
-    if (align_corners) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_flow_warp_fwd<true, true, true>), g, dim3(256), 0, s, feat, flow, out, C, H, W, flow_scale);
-    else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_flow_warp_fwd<false, true, true>), g, dim3(256), 0, s, feat, flow, out, C, H, W, flow_scale);
+    CC_DISPATCH_AC(k_flow_warp_fwd, (, true, true), align_corners, g, dim3(256), 0, s, feat, flow, out, C, H, W, flow_scale);
     CC_CHECK_LAUNCH();
     return CC_OK;
 }
@@ -959,13 +932,13 @@ int cc_feature_warp_bwd(const float* gout, const float* feat, const float* flow,
     dim3 g = pix_grid(B, H, W);
     if (C >= 16) {
         dim3 g4((unsigned)((H * W + 63) / 64), (unsigned)B);
-        if (align_corners) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_feature_warp_bwd4<true>), g4, dim3(256), 0, s, gout, feat, flow, gflow_or_null, gfeat_or_null, C, H, W, flow_scale);
-        else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_feature_warp_bwd4<false>), g4, dim3(256), 0, s, gout, feat, flow, gflow_or_null, gfeat_or_null, C, H, W, flow_scale);
+        CC_DISPATCH_AC(k_feature_warp_bwd4, (), align_corners, g4, dim3(256), 0, s, gout, feat, flow, gflow_or_null, gfeat_or_null, C, H, W,
+                       flow_scale);
         CC_CHECK_LAUNCH();
         return CC_OK;
     }
-    if (align_corners) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_flow_warp_bwd<true, true, true>), g, dim3(256), 0, s, gout, feat, flow, gflow_or_null, gfeat_or_null, C, H, W, flow_scale);
-    else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_flow_warp_bwd<false, true, true>), g, dim3(256), 0, s, gout, feat, flow, gflow_or_null, gfeat_or_null, C, H, W, flow_scale);
+    CC_DISPATCH_AC(k_flow_warp_bwd, (, true, true), align_corners, g, dim3(256), 0, s, gout, feat, flow, gflow_or_null, gfeat_or_null, C, H,
+                   W, flow_scale);
     CC_CHECK_LAUNCH();
     return CC_OK;
 }
@@ -987,8 +960,8 @@ int cc_feature_warp_bwd_det(const float* gout, const float* feat, const float* f
     hipLaunchKernelGGL(k_fx_zero, dim3((unsigned)((n + 2 + 1023) / 1024)), dim3(256), 0, s, (unsigned long long*)ws, n + 2);
     hipLaunchKernelGGL(k_fx_absmax, dim3((unsigned)((n + 4095) / 4096)), dim3(256), 0, s, gout, mx, n);
     dim3 g4((unsigned)((H * W + 63) / 64), (unsigned)B);
-    if (align_corners) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_feature_warp_bwd4<true>), g4, dim3(256), 0, s, gout, feat, flow, gflow_or_null, (float*)nullptr, C, H, W, flow_scale, fx, (const unsigned*)mx);
-    else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_feature_warp_bwd4<false>), g4, dim3(256), 0, s, gout, feat, flow, gflow_or_null, (float*)nullptr, C, H, W, flow_scale, fx, (const unsigned*)mx);
+    CC_DISPATCH_AC(k_feature_warp_bwd4, (), align_corners, g4, dim3(256), 0, s, gout, feat, flow, gflow_or_null, (float*)nullptr, C, H, W,
+                   flow_scale, fx, (const unsigned*)mx);
     hipLaunchKernelGGL(k_fx_to_float, dim3((unsigned)((n + 1023) / 1024)), dim3(256), 0, s, (const unsigned long long*)fx, (const unsigned*)mx, gfeat, n, accumulate);
     CC_CHECK_LAUNCH();
     return CC_OK;
@@ -996,21 +969,12 @@ int cc_feature_warp_bwd_det(const float* gout, const float* feat, const float* f
 
 /* ---- job-table forms: `jobs` = HOST array of njobs x 10 longs {slot0..slot7, H, W} (slot meaning per entry point, see
  * include/ccengine.h); every job spans B batch items; njobs <= 24. */
-static int warp_jobs_tab(ccjobs::JobTab& t, const long* jobs, int njobs, int B) {
-    if (!jobs || njobs <= 0 || njobs > ccjobs::MAXJOBS || B <= 0) return -1;
-    return ccjobs::fill(t, jobs, njobs, B, ccjobs::pix_blocks);
-}
-// ... for the kernels that give every work-item WPPT pixels (256 apart): ceil(ceil(H W / 256) / WPPT) workgroups per image
-static int warp_jobs_tab4(ccjobs::JobTab& t, const long* jobs, int njobs, int B) {
-    if (!jobs || njobs <= 0 || njobs > ccjobs::MAXJOBS || B <= 0) return -1;
-    return ccjobs::fill(t, jobs, njobs, B, [](int H, int W) { return (ccjobs::pix_blocks(H, W) + WPPT - 1) / WPPT; });
-}
 
 int cc_inverse_warp_fwd_jobs(const long* jobs, int njobs, int B, int C, int padding_border, int align_corners, void* stream) {
     ccjobs::JobTab t;
-    const int nblk = warp_jobs_tab4(t, jobs, njobs, B);
+    const int nblk = ccjobs::table(t, jobs, njobs, B, ccjobs::pix_blocks_ppt<WPPT>);
     if (nblk <= 0) return CC_ERR_ARG;
-    CC_DISPATCH_AC_PAD(k_inverse_warp_fwd_jobs, align_corners, padding_border, dim3((unsigned)nblk), dim3(256), 0,
+    CC_DISPATCH_AC_PAD(k_inverse_warp_fwd_jobs, (), align_corners, padding_border, dim3((unsigned)nblk), dim3(256), 0,
                        (hipStream_t)stream, t, C);
     CC_CHECK_LAUNCH();
     return CC_OK;
@@ -1018,9 +982,9 @@ int cc_inverse_warp_fwd_jobs(const long* jobs, int njobs, int B, int C, int padd
 
 int cc_inverse_warp_bwd_jobs(const long* jobs, int njobs, int B, int C, int padding_border, int align_corners, void* stream) {
     ccjobs::JobTab t;
-    const int nblk = warp_jobs_tab4(t, jobs, njobs, B);
+    const int nblk = ccjobs::table(t, jobs, njobs, B, ccjobs::pix_blocks_ppt<WPPT>);
     if (nblk <= 0) return CC_ERR_ARG;
-    CC_DISPATCH_AC_PAD(k_inverse_warp_bwd_jobs, align_corners, padding_border, dim3((unsigned)nblk), dim3(256), 0,
+    CC_DISPATCH_AC_PAD(k_inverse_warp_bwd_jobs, (), align_corners, padding_border, dim3((unsigned)nblk), dim3(256), 0,
                        (hipStream_t)stream, t, C);
     CC_CHECK_LAUNCH();
     return CC_OK;
@@ -1028,9 +992,9 @@ int cc_inverse_warp_bwd_jobs(const long* jobs, int njobs, int B, int C, int padd
 
 int cc_flow_warp_fwd_jobs(const long* jobs, int njobs, int B, int C, int padding_border, int align_corners, void* stream) {
     ccjobs::JobTab t;
-    const int nblk = warp_jobs_tab4(t, jobs, njobs, B);
+    const int nblk = ccjobs::table(t, jobs, njobs, B, ccjobs::pix_blocks_ppt<WPPT>);
     if (nblk <= 0) return CC_ERR_ARG;
-    CC_DISPATCH_AC_PAD(k_flow_warp_fwd_jobs, align_corners, padding_border, dim3((unsigned)nblk), dim3(256), 0,
+    CC_DISPATCH_AC_PAD(k_flow_warp_fwd_jobs, (), align_corners, padding_border, dim3((unsigned)nblk), dim3(256), 0,
                        (hipStream_t)stream, t, C);
     CC_CHECK_LAUNCH();
     return CC_OK;
@@ -1038,9 +1002,9 @@ int cc_flow_warp_fwd_jobs(const long* jobs, int njobs, int B, int C, int padding
 
 int cc_flow_warp_bwd_jobs(const long* jobs, int njobs, int B, int C, int padding_border, int align_corners, void* stream) {
     ccjobs::JobTab t;
-    const int nblk = warp_jobs_tab(t, jobs, njobs, B);
+    const int nblk = ccjobs::table(t, jobs, njobs, B, ccjobs::pix_blocks);
     if (nblk <= 0) return CC_ERR_ARG;
-    CC_DISPATCH_AC_PAD(k_flow_warp_bwd_jobs, align_corners, padding_border, dim3((unsigned)nblk), dim3(256), 0,
+    CC_DISPATCH_AC_PAD(k_flow_warp_bwd_jobs, (), align_corners, padding_border, dim3((unsigned)nblk), dim3(256), 0,
                        (hipStream_t)stream, t, C);
     CC_CHECK_LAUNCH();
     return CC_OK;
@@ -1048,7 +1012,7 @@ int cc_flow_warp_bwd_jobs(const long* jobs, int njobs, int B, int C, int padding
 
 int cc_rigid_noocc_jobs(const long* jobs, int njobs, int B, void* stream) {
     ccjobs::JobTab t;
-    const int nblk = warp_jobs_tab(t, jobs, njobs, B);
+    const int nblk = ccjobs::table(t, jobs, njobs, B, ccjobs::pix_blocks);
     if (nblk <= 0) return CC_ERR_ARG;
     hipLaunchKernelGGL(k_rigid_noocc_jobs, dim3((unsigned)nblk), dim3(256), 0, (hipStream_t)stream, t);
     CC_CHECK_LAUNCH();
@@ -1057,7 +1021,7 @@ int cc_rigid_noocc_jobs(const long* jobs, int njobs, int B, void* stream) {
 
 int cc_pose2flow_fwd_jobs(const long* jobs, int njobs, int B, int rewrite_oob, void* stream) {
     ccjobs::JobTab t;
-    const int nblk = warp_jobs_tab4(t, jobs, njobs, B);
+    const int nblk = ccjobs::table(t, jobs, njobs, B, ccjobs::pix_blocks_ppt<WPPT>);
     if (nblk <= 0) return CC_ERR_ARG;
     hipLaunchKernelGGL(k_pose2flow_fwd_jobs, dim3((unsigned)nblk), dim3(256), 0, (hipStream_t)stream, t, rewrite_oob);
     CC_CHECK_LAUNCH();

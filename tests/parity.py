@@ -1784,3 +1784,213 @@ def check_rigid_chain(dev, B=2, R=2, C=3):
                     sp.append(torch.autograd.grad((o * go[0].to(dt)).sum(), p)[0])
                 T.term("single:gpose %s" % tag, g1[2], sp[0], sp[1])
     T.done()
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Every single-call loss-path kernel against the row of a job table that runs the same pixel body (csrc/warp.hip, losses.hip)
+SINGLE_JOB_SHAPES = ((8, 26), (20, 53))        # 208 pixels: one ragged 256-pixel piece; 1060: five pieces, odd width
+SINGLE_JOB_SEEDS = (3, 4)                      # _rigid_recipe seeds at which 25-75 % of the samples land inside (asserted below)
+
+
+def check_single_call_equals_job_row(dev):
+    """One job-table launch with two rows (SINGLE_JOB_SHAPES, B = 2, C = 3) per *_jobs entry point of the loss path, and the
+    single-call entry point on each row's tensors.  Inputs: _rigid_recipe('moderate') poses and depths through cc_pose_proj_fwd, the
+    flows are the rigid flows of those poses (a quarter to three quarters of the samples inside the image, asserted), random upstream
+    gradients; the warps in all four (align_corners, padding_border) combinations, pose2flow with and without the rewrite.
+
+    Every per-pixel output is torch.equal between the two forms: out, gdepth, gflow, flow, the masks, gpred, gmask, target.
+
+    Reduced outputs are torch.equal exactly where both forms add the same values in the same order (block_sum_256 over one value per
+    work-item, a work-item that held a single live pixel):
+      cc_edge_smooth_fwd_bwd_jobs, C > 0 (k_edge_smooth_jobs<1>)   every partial sum of both rows; and the loss: k_reduce_add over
+      cc_consensus_bce_fwd_bwd_jobs                                  the single calls' partials laid out back to back is the table's sum
+      cc_inverse_warp_bwd_jobs (WPPT = 4)                            partial row k of [B][nb][12] where piece k is the only live piece
+      cc_edge_smooth_fwd_bwd_jobs, C = 0 (k_edge_smooth_jobs<4>)     of its workgroup: k = 0 of row 0 (nb = 1), k = 4 of row 1 (nb = 5)
+      cc_bce_ones_fwd_bwd_jobs                                       never: the single call runs flat over B C H W (256 elements across
+                                                                     plane borders), the table form piece by piece of each plane
+    Where the layouts differ the layout is asserted: rows k % 4 != 0 of the WPPT / PPT = 4 forms' partial areas are exactly zero,
+    every partial area is written over its whole documented extent and not beyond (NaN sentinels).  The values of the sums that are
+    added in another order are left to the float64 and golden tests."""
+    from cc_amd._lib import engine, STREAM
+    E = engine()
+    B, C, R = 2, 3, 4
+    hw = SINGLE_JOB_SHAPES
+    nb = [(h * w + 255) // 256 for h, w in hw]
+    assert nb == [1, 5]
+    nan = lambda *s: torch.full(s, float("nan"), device=dev)
+    thresh, wbce, wrig, gscale = 0.5, 0.25, 0.7, 0.75
+
+    rows = []
+    for i, (H, W) in enumerate(hw):
+        g = torch.Generator().manual_seed(70 + i)
+        rn = lambda *s: torch.randn(*s, generator=g)
+        ru = lambda *s: torch.rand(*s, generator=g)
+        _, refs, K, Kinv = syn.sample(B, H, W, seed=1, smooth=1)
+        pose, depth = _rigid_recipe("moderate", B, R, H, W, SINGLE_JOB_SEEDS[i])
+        P = torch.empty(B * R, 12, device=dev)
+        E.call("cc_pose_proj_fwd", pose.view(B * R, 6).to(dev), 6, K.repeat_interleave(R, 0).reshape(B * R, 9).contiguous().to(dev), P, B * R, 1.0, STREAM)
+        d = dict(H=H, W=W, img=refs[0][:, :C].contiguous(), depth=depth, P4=P.cpu().view(B, R, 12).transpose(0, 1).contiguous(),
+                 Kinv=Kinv.reshape(B, 9).contiguous(), gout=rn(B, C, H, W), pred=rn(B, C, H, W), mask=torch.sigmoid(rn(B, C, H, W)),
+                 exp_mask=torch.sigmoid(rn(B, 4, H, W)), census_b=ru(B, 2, H, W) * 0.7, census_f=ru(B, 2, H, W) * 0.7,
+                 tgt_b=(ru(B, 1, H, W) < 0.5).float(), tgt_f=(ru(B, 1, H, W) < 0.5).float(),
+                 err_cf=ru(B, 1, H, W), err_cb=ru(B, 1, H, W), err_ff=ru(B, 1, H, W) * 0.5,
+                 v_cf=(ru(B, 1, H, W) < 0.5).float(), v_cb=(ru(B, 1, H, W) < 0.5).float())
+        d = {k: v.to(dev) if torch.is_tensor(v) else v for k, v in d.items()}
+        d["P"] = d["P4"][0].contiguous()
+        # the flows of the flow-driven kernels: the rigid flows of frames 0 and 1 (the single call: an input like any other here)
+        for k, r in (("flow", 0), ("flow_bw", 1)):
+            d[k] = nan(B, 2, H, W)
+            E.call("cc_pose2flow_fwd", d["depth"], d["P4"][r].contiguous(), d["Kinv"], d[k], B, H, W, 0, STREAM)
+        f = d["flow"].cpu()
+        ys, xs = torch.meshgrid(torch.arange(H, dtype=torch.float32), torch.arange(W, dtype=torch.float32), indexing="ij")
+        inside = float(((xs + f[:, 0] >= 0) & (xs + f[:, 0] <= W - 1) & (ys + f[:, 1] >= 0) & (ys + f[:, 1] <= H - 1)).float().mean())
+        print("single/jobs row %d (%dx%d): %.3f of the samples inside the image" % (i, H, W, inside))
+        assert 0.25 <= inside <= 0.75, (i, inside)
+        rows.append(d)
+
+    def jobs(name, slots, *args):
+        """ONE launch of `name` over the two rows; slots(d) -> the row's slot list"""
+        jb = LF._Jobs()
+        for d in rows:
+            jb.add(slots(d), d["H"], d["W"])
+        E.call(name, jb.pack(), len(jb), *args)
+
+    def eq(tag, a, b):
+        assert a.shape == b.shape, (tag, a.shape, b.shape)
+        assert not bool(torch.isnan(a).any() | torch.isnan(b).any()), (tag, "an element was not written")
+        assert torch.equal(a, b), (tag, "differs in %d elements, max %.3e" % (int((a != b).sum()), float((a - b).abs().max())))
+
+    def outs(shape_of):
+        """-> (table form's outputs, single calls' outputs), one NaN-filled tensor per row each"""
+        return [nan(*shape_of(d)) for d in rows], [nan(*shape_of(d)) for d in rows]
+
+    def partial_area(per_row):
+        """one NaN-filled buffer holding the rows' partial areas back to back (+ a guard element) -> buffer, offsets"""
+        offs = [0]
+        for n in per_row:
+            offs.append(offs[-1] + n)
+        return nan(offs[-1] + 1), offs
+
+    def grouped_partials(tag, pj, ps, i):
+        """pj, ps [..., nb, N]: the table form's (4 pieces per workgroup) and the single call's partial rows of table row i"""
+        for k in range(nb[i]):
+            if k % 4:
+                assert bool((pj[..., k, :] == 0).all()), (tag, i, k, "not exactly zero")
+            elif k + 1 == nb[i]:
+                eq("%s partial row %d of table row %d" % (tag, k, i), pj[..., k, :], ps[..., k, :])
+            else:
+                assert not bool(torch.isnan(pj[..., k, :]).any()), (tag, i, k)
+
+    BCHW = lambda d: (B, C, d["H"], d["W"])
+    # ---- the warps
+    for ac in (0, 1):
+        for border in (0, 1):
+            tag = "ac=%d border=%d" % (ac, border)
+            oj, os_ = outs(BCHW)
+            jobs("cc_inverse_warp_fwd_jobs", lambda d: [d["img"], d["depth"], d["P"], d["Kinv"], oj[rows.index(d)]], B, C, border, ac, STREAM)
+            for i, d in enumerate(rows):
+                E.call("cc_inverse_warp_fwd", d["img"], d["depth"], d["P"], d["Kinv"], os_[i], B, C, d["H"], d["W"], border, ac, STREAM)
+                eq("inverse_warp_fwd out %s row %d" % (tag, i), oj[i], os_[i])
+                assert float((oj[i] != 0).float().mean()) > 0.2 or border, (tag, i)
+
+            gj, gs = outs(lambda d: (B, d["H"], d["W"]))
+            pj, ps = [nan(B, n, 12) for n in nb], [nan(B, n, 12) for n in nb]
+            jobs("cc_inverse_warp_bwd_jobs", lambda d: [d["gout"], d["img"], d["depth"], d["P"], d["Kinv"], gj[rows.index(d)], pj[rows.index(d)]],
+                 B, C, border, ac, STREAM)
+            for i, d in enumerate(rows):
+                E.call("cc_inverse_warp_bwd", d["gout"], d["img"], d["depth"], d["P"], d["Kinv"], gs[i], nan(B, 12), None, ps[i], B, C,
+                       d["H"], d["W"], border, ac, STREAM)
+                eq("inverse_warp_bwd gdepth %s row %d" % (tag, i), gj[i], gs[i])
+                grouped_partials("inverse_warp_bwd %s" % tag, pj[i], ps[i], i)
+
+            oj, os_ = outs(BCHW)
+            jobs("cc_flow_warp_fwd_jobs", lambda d: [d["img"], d["flow"], oj[rows.index(d)]], B, C, border, ac, STREAM)
+            gj, gs = outs(lambda d: (B, 2, d["H"], d["W"]))
+            jobs("cc_flow_warp_bwd_jobs", lambda d: [d["gout"], d["img"], d["flow"], gj[rows.index(d)]], B, C, border, ac, STREAM)
+            for i, d in enumerate(rows):
+                E.call("cc_flow_warp_fwd", d["img"], d["flow"], os_[i], B, C, d["H"], d["W"], border, ac, STREAM)
+                E.call("cc_flow_warp_bwd", d["gout"], d["img"], d["flow"], gs[i], None, B, C, d["H"], d["W"], border, ac, STREAM)
+                eq("flow_warp_fwd out %s row %d" % (tag, i), oj[i], os_[i])
+                eq("flow_warp_bwd gflow %s row %d" % (tag, i), gj[i], gs[i])
+
+    # ---- rigid flows and the occlusion masks
+    for rewrite in (0, 1):
+        fj, fs = outs(lambda d: (B, 2, d["H"], d["W"]))
+        jobs("cc_pose2flow_fwd_jobs", lambda d: [d["depth"], d["P"], d["Kinv"], fj[rows.index(d)]], B, rewrite, STREAM)
+        for i, d in enumerate(rows):
+            E.call("cc_pose2flow_fwd", d["depth"], d["P"], d["Kinv"], fs[i], B, d["H"], d["W"], rewrite, STREAM)
+            eq("pose2flow_fwd flow rewrite=%d row %d" % (rewrite, i), fj[i], fs[i])
+    mj, ms = outs(lambda d: (B, 4, d["H"], d["W"]))
+    jobs("cc_rigid_noocc_jobs", lambda d: [d["depth"], d["P4"], d["Kinv"], mj[rows.index(d)]], B, STREAM)
+    nj, ns = outs(lambda d: (B, 1, d["H"], d["W"]))
+    jobs("cc_flow_noocc_jobs", lambda d: [d["flow_bw"], d["flow"], nj[rows.index(d)]], B, STREAM)
+    tj, ts = outs(lambda d: (B, 1, d["H"], d["W"]))
+    jobs("cc_consensus_target_jobs", lambda d: [d["err_cf"], d["err_cb"], d["err_ff"], d["v_cf"], d["v_cb"], tj[rows.index(d)]], B, wrig, STREAM)
+    for i, d in enumerate(rows):
+        H, W = d["H"], d["W"]
+        E.call("cc_rigid_noocc_fused", d["depth"], d["P4"], d["Kinv"], ms[i], B, H, W, STREAM)
+        E.call("cc_flow_noocc", d["flow_bw"], d["flow"], ns[i], B, H, W, STREAM)
+        E.call("cc_consensus_target", d["err_cf"], d["err_cb"], d["err_ff"], d["v_cf"], d["v_cb"], ts[i], wrig, B * H * W, STREAM)
+        eq("rigid_noocc masks row %d" % i, mj[i], ms[i])
+        eq("flow_noocc mask row %d" % i, nj[i], ns[i])
+        eq("consensus target row %d" % i, tj[i], ts[i])
+        for nm, m in (("rigid_noocc", ms[i]), ("flow_noocc", ns[i]), ("consensus target", ts[i])):
+            assert 0.0 < float(m.mean()) < 1.0, (nm, i, "a constant mask compares nothing")
+
+    def same_loss(tag, loss_j, ps, n):
+        """the table's loss = k_reduce_add over the rows' partial sums back to back: the same kernel over the single calls' partials"""
+        acc = torch.zeros(1, device=dev)
+        E.call("cc_reduce_add", torch.cat([p.reshape(-1) for p in ps]).contiguous(), n, 1.0, acc, STREAM)
+        eq(tag, loss_j, acc)
+
+    # ---- edge-aware smoothness: one piece per workgroup (C > 0), four (C = 0: per-job channel counts in slot 4)
+    for ppt in (1, 4):
+        tag = "edge_smooth<%d>" % ppt
+        gj, gs = outs(BCHW)
+        part, offs = partial_area([B * C * n for n in nb])
+        loss_j = torch.zeros(1, device=dev)
+        extra = (lambda d: []) if ppt == 1 else (lambda d: [C, None])
+        jobs("cc_edge_smooth_fwd_bwd_jobs", lambda d: [d["img"], d["pred"], gj[rows.index(d)], LF._off(part, offs[rows.index(d)])] + extra(d),
+             B, C if ppt == 1 else 0, part, loss_j, gscale, STREAM)
+        assert bool(torch.isnan(part[-1])) and not bool(torch.isnan(part[:-1]).any()), (tag, "extent of the partial areas")
+        ps = [nan(B * C, n) for n in nb]
+        for i, d in enumerate(rows):
+            E.call("cc_edge_smooth_fwd_bwd", d["img"], d["pred"], gs[i], ps[i], torch.zeros(1, device=dev), gscale, B, C, d["H"], d["W"], STREAM)
+            eq("%s gpred row %d" % (tag, i), gj[i], gs[i])
+            pj = part[offs[i]:offs[i + 1]].view(B * C, nb[i])
+            if ppt == 1:
+                eq("%s partials row %d" % (tag, i), pj, ps[i])
+            else:
+                grouped_partials(tag, pj.unsqueeze(-1), ps[i].unsqueeze(-1), i)
+        if ppt == 1:
+            same_loss(tag + " loss", loss_j, ps, offs[-1])
+        assert bool(torch.isfinite(loss_j).all()) and float(loss_j) > 0, (tag, loss_j)
+
+    # ---- explainability BCE: per-pixel gradient only (the sums are laid out differently, see the docstring)
+    gj, gs = outs(BCHW)
+    part, offs = partial_area([B * C * n for n in nb])
+    loss_j = torch.zeros(1, device=dev)
+    jobs("cc_bce_ones_fwd_bwd_jobs", lambda d: [d["mask"], gj[rows.index(d)], LF._off(part, offs[rows.index(d)])], B * C, part, loss_j, gscale, STREAM)
+    assert bool(torch.isnan(part[-1])) and not bool(torch.isnan(part[:-1]).any()), "bce_ones: one partial sum per 256-pixel piece of a plane"
+    for i, d in enumerate(rows):
+        n = B * C * d["H"] * d["W"]
+        ps = nan((n + 255) // 256 + 1)
+        E.call("cc_bce_ones_fwd_bwd", d["mask"], gs[i], ps, torch.zeros(1, device=dev), gscale, n, STREAM)
+        assert bool(torch.isnan(ps[-1])) and not bool(torch.isnan(ps[:-1]).any()), "bce_ones: one partial sum per 256 elements"
+        eq("bce_ones gmask row %d" % i, gj[i], gs[i])
+    assert bool(torch.isfinite(loss_j).all()) and float(loss_j) > 0, loss_j
+
+    # ---- consensus BCE
+    gj, gs = outs(lambda d: (B, 4, d["H"], d["W"]))
+    part, offs = partial_area([B * n for n in nb])
+    loss_j = torch.zeros(1, device=dev)
+    jobs("cc_consensus_bce_fwd_bwd_jobs", lambda d: [d["exp_mask"], d["census_b"], d["census_f"], d["tgt_b"], d["tgt_f"], gj[rows.index(d)],
+                                                     LF._off(part, offs[rows.index(d)])], B, part, loss_j, thresh, wbce, gscale, STREAM)
+    assert bool(torch.isnan(part[-1])) and not bool(torch.isnan(part[:-1]).any()), "consensus_bce: extent of the partial areas"
+    ps = [nan(B, n) for n in nb]
+    for i, d in enumerate(rows):
+        E.call("cc_consensus_bce_fwd_bwd", d["exp_mask"], d["census_b"], d["census_f"], d["tgt_b"], d["tgt_f"], gs[i], ps[i],
+               torch.zeros(1, device=dev), thresh, wbce, gscale, B, d["H"], d["W"], STREAM)
+        eq("consensus_bce gmask row %d" % i, gj[i], gs[i])
+        eq("consensus_bce partials row %d" % i, part[offs[i]:offs[i + 1]].view(B, nb[i]), ps[i])
+    same_loss("consensus_bce loss", loss_j, ps, offs[-1])

@@ -257,6 +257,10 @@ def test_rigid_chain_float64_pinned():
     parity.check_rigid_chain("cpu")
 
 
+def test_single_call_equals_job_row():
+    parity.check_single_call_equals_job_row("cpu")
+
+
 def test_bias_gradient_table():
     parity.check_bias_grad_table("cpu")
 

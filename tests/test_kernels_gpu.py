@@ -256,6 +256,10 @@ def test_rigid_chain_float64_pinned():
     parity.check_rigid_chain("cuda")
 
 
+def test_single_call_equals_job_row():
+    parity.check_single_call_equals_job_row("cuda")
+
+
 def test_bias_gradient_table():
     parity.check_bias_grad_table("cuda")
     parity.check_bias_grad_table("cuda", cases=((4, 64, 64, 208, 0), (4, 16, 256, 832, 1), (4, 512, 2, 7, 0), (4, 32, 128, 416, 33)) * 9)

@@ -1,13 +1,18 @@
 #!/usr/bin/env python
 """Compare the gfx950 device code of two checkouts kernel by kernel (no GPU needed).
 
-  python tools/isa_diff.py OLD_TREE NEW_TREE [--allow-removed REGEX] [--allow-added REGEX] [--show N]
+  python tools/isa_diff.py OLD_TREE NEW_TREE [--opcodes] [--allow-removed REGEX] [--allow-added REGEX] [--show N]
 
 Compiles every cc_amd/csrc/*.hip of both trees to assembly with the flags of cc_amd/build.py (tools/isa_scan.py compile_asm) and
 matches the kernels by symbol name across files, so a kernel may move to another translation unit.  Two kernels are equal when
 their instruction streams are equal -- comments stripped, local labels renumbered (a function's index in its file is part of
 .LBB<n>_<m>) -- and all their .amdhsa_* descriptor values (registers, LDS, scratch, ...) are.  Exit status 0: every kernel present
-on both sides is equal and the sets of kernels differ only by what the two REGEXes (matched against the demangled name) allow."""
+on both sides is equal and the sets of kernels differ only by what the two REGEXes (matched against the demangled name) allow.
+
+--opcodes: for a change that moves code between functions without changing it, after which the scheduler may order independent
+instructions differently and name registers differently.  Two kernels are then equal when their .amdhsa_* values and the MULTISET
+of their instruction mnemonics (labels and directives left out) are equal; every kernel is printed with both verdicts, so that the
+strictly equal ones can be told from the merely opcode-equal ones."""
 import argparse
 import glob
 import os
@@ -15,6 +20,7 @@ import re
 import subprocess
 import sys
 import tempfile
+from collections import Counter
 from concurrent.futures import ThreadPoolExecutor
 
 from isa_scan import FILT, compile_asm
@@ -36,6 +42,11 @@ def normalise(lines):
             continue
         out.append(re.sub(r"\.L([A-Za-z_]+?)\d+_(\d+)", r".L\1_\2", ln))
     return out
+
+
+def opcodes(body):
+    """normalised lines -> Counter of mnemonics"""
+    return Counter(ln.split()[0] for ln in body if not ln.endswith(":") and not ln.startswith("."))
 
 
 def kernels_of(asm_path):
@@ -93,6 +104,7 @@ def main():
     ap.add_argument("new_tree")
     ap.add_argument("--allow-removed", default=None, help="kernels (demangled name, regex) that may be missing from NEW_TREE")
     ap.add_argument("--allow-added", default=None, help="kernels (demangled name, regex) that may be new in NEW_TREE")
+    ap.add_argument("--opcodes", action="store_true", help="equal = same descriptors and same multiset of mnemonics; print both verdicts")
     ap.add_argument("--show", type=int, default=20, help="differing lines printed per kernel")
     a = ap.parse_args()
     with tempfile.TemporaryDirectory() as tmp:
@@ -116,7 +128,17 @@ def main():
         n = sorted(n, key=lambda fv: fv[1][0])
         for (fo, (bo, do)), (fn, (bn, dn)) in zip(o, n):
             moved += fo != fn
-            if bo == bn and do == dn:
+            strict = bo == bn and do == dn
+            if a.opcodes:
+                loose = do == dn and opcodes(bo) == opcodes(bn)
+                print("%s strict %-5s opcodes %-5s %s  (%s)" % ("ok  " if loose else "DIFF", "equal" if strict else "DIFF",
+                                                               "equal" if loose else "DIFF", names[k], fn))
+                if loose:
+                    continue
+                d = opcodes(bn)
+                d.subtract(opcodes(bo))
+                print("       opcodes new - old: %s" % {m: c for m, c in sorted(d.items()) if c})
+            elif strict:
                 continue
             bad += 1
             print("DIFF kernel    %s  (%s -> %s)" % (names[k], fo, fn))
