@@ -1371,10 +1371,10 @@ def _leaf_as(t, dt, d="cpu"):
 class _RigidTerms:
     """The comparisons of one check: every figure is printed and noted first, the bars are asserted together at the end."""
 
-    def __init__(self, check):
-        self.check, self.bad = check, []
+    def __init__(self, check, prefix="rigid"):
+        self.check, self.prefix, self.bad = check, prefix, []
 
-    def term(self, name, v_dev, v_32, v_64, keep=None):
+    def term(self, name, v_dev, v_32, v_64, keep=None, floor=RIGID_FLOOR):
         z = v_64.detach() if keep is None else v_64.detach()[keep]
         if float(z.abs().max()) == 0:
             # nothing reaches this term (every coordinate rewritten or clipped): exactly zero on every side, no ratio to take
@@ -1385,16 +1385,16 @@ class _RigidTerms:
             return
         e_dev, e_32 = _e64(v_dev, v_64, keep), _e64(v_32, v_64, keep)
         ratio = e_dev / e_32 if e_32 > 0 else float("inf") if e_dev > 0 else 0.0
-        key = "rigid:%s:%s" % (self.check, name.split(" ")[0])
+        key = "%s:%s:%s" % (self.prefix, self.check, name.split(" ")[0])
         _note(key + ":e_dev", e_dev)
         _note(key + ":e_32", e_32)
-        ok = e_dev <= RIGID_MARGIN * e_32 + RIGID_FLOOR
+        ok = e_dev <= RIGID_MARGIN * e_32 + floor
         print("%-64s e_dev %.3e  e_32 %.3e  ratio %6.2f  %s" % (self.check + ":" + name, e_dev, e_32, ratio, "ok" if ok else "OVER THE BAR"))
         if not ok:
             self.bad.append((name, e_dev, e_32))
 
     def done(self):
-        assert not self.bad, (self.check, "e_dev > 4 * e_32 + 2^-23", self.bad)
+        assert not self.bad, (self.check, "e_dev > 4 * e_32 + floor (2^-23; k * 2^-24 for the sums of the ssim checks)", self.bad)
 
 
 def _rigid_poses(B, R, seed):
@@ -1810,7 +1810,7 @@ def check_single_call_equals_job_row(dev):
                                                                      plane borders), the table form piece by piece of each plane
     Where the layouts differ the layout is asserted: rows k % 4 != 0 of the WPPT / PPT = 4 forms' partial areas are exactly zero,
     every partial area is written over its whole documented extent and not beyond (NaN sentinels).  The values of the sums that are
-    added in another order are left to the float64 and golden tests."""
+    added in another order are left to the float64 and golden tests.  (The SSIM family: check_ssim_single_call_equals_job_row.)"""
     from cc_amd._lib import engine, STREAM
     E = engine()
     B, C, R = 2, 3, 4
@@ -1994,3 +1994,418 @@ def check_single_call_equals_job_row(dev):
         eq("consensus_bce gmask row %d" % i, gj[i], gs[i])
         eq("consensus_bce partials row %d" % i, part[offs[i]:offs[i + 1]].view(B, nb[i]), ps[i])
     same_loss("consensus_bce loss", loss_j, ps, offs[-1])
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The SSIM / photometric kernels (csrc/ssim.hip) against float64, per entry point, through the C ABI.
+# Bars: the formula of the rigid checks, e_dev <= RIGID_MARGIN * e_32 + floor with e = max|x - f64| / max|f64| over the WHOLE
+# tensor (these kernels take no sampling decision: nothing is left out).  Both fp32 sides evaluate the same formula and differ in
+# summation order (separable 13 + 13 taps against 169, E[xx] + E[yy] filtered together), fmaf and the 1-ulp v_rcp_f32.
+# floor = 2^-23 for per-pixel tensors; for sums of non-negative values k * 2^-24, k = the additions on the longest path from a
+# pixel to the result (every intermediate is at most the result, so each addition rounds by at most 2^-24 of it; the handful of
+# products and quotients behind the sums are left to the 4 * e_32 part):
+#   partials    12   ssim_tile_body: s_rob / s_sl take 4 pixels x 3 channels per work item
+#              + 6   block_sum_256: wave_sum, six __shfl_xor levels
+#              + 2   block_sum_256: (w0 + w1) + (w2 + w3)                                                        = 20
+#   loss_accum  20
+#              + 1   k_photo_finalize: one addition per thread (nblk <= 256 here; k_photo_finalize_jobs: nblk <= 64, per lane)
+#              + 8   block_sum_256 (the job form: wave_sum, 6)
+#              + 1   v0 / n3 + wssim * (v1 / n3)
+#              + 1   term += the lambda_oob part
+#              + 1   loss_accum[0] += term (the job form: up to 3, acc += terms[j] in job order: 20 + 1 + 6 + 2 + 3) = 32
+#   scale_out   4    (1 - wssim) * (n1 / v2) / n3: no inexact addition at all (v2 is a sum of 0 / 1 below 2^24), what is left are
+#                    its own four roundings -- fewer than the 4 + 8 + 1 + 8 additions on the path of the count
+# (wssim, q and lambda_oob are fp32 values on all three sides: the C ABI takes floats, and 1 - 0.997 in float64 is 7e-6 away from
+# 1 - float32(0.997).)
+SSIM_K_PARTIALS, SSIM_K_LOSS, SSIM_K_SCALE = 20, 32, 4
+SSIM_MIN_COND = 10.0            # min(sigma1_sq + sigma2_sq + C2) / C2 of the float64 reference
+SSIM_SHAPES = (
+    # TS = 32, HALO = 6 (ssim.hip).  colsafe: ox0 >= 8 and ox0 + 40 <= W
+    (2, 40, 72),    # W % 4 == 0: VEC.  3 x 2 tiles, last tile column 8 wide, last tile row 8 high; tile column 1 is colsafe
+                    # (32 + 40 <= 72); 12 tiles per job: tile_of's deal-out with q = 1, r = 4
+    (2, 33, 74),    # W % 4 == 2: `pairs`, tile column 1 colsafe (32 + 40 <= 74); the second tile row is ONE image row
+    (1, 35, 45),    # odd W: the scalar form of load_row16 / load4 / store4 / the adjoint's staging loop; two tile columns
+    (2, 8, 26),     # the coarsest level of an 832-wide frame: `pairs`, one tile
+    (2, 2, 3),      # smaller than the 6-pixel halo in both directions
+)
+SSIM_SMOOTH = (0, 1)
+SSIM_SEEDS = {}                 # (B, H, W, smooth) -> seed of syn.frames where seed 3 misses SSIM_MIN_COND (none does)
+PHOTO_ARGS = tuple(tuple(float(np.float32(v)) for v in a) for a in ((0.997, 0.5, 0.0), (0.5, 0.4, 0.3)))      # wssim, q, lambda_oob
+PHOTO_SENTINEL = -77.0
+PHOTO_LOSS0 = 2.0 ** -10        # loss_accum before the call (the entry point adds to it): small against the second argument set's
+                                # term (~0.5), comparable to the first one's (~5e-3)
+
+
+def _ssim_cond(x, y):
+    import torch.nn.functional as F
+    x, y = x.double(), y.double()
+    win = L.ssim_window(13, 3).double()
+    f = lambda t: F.conv2d(t, win, padding=6, groups=3)
+    return float((f(x * x) - f(x).pow(2) + f(y * y) - f(y).pow(2) + 0.03 ** 2).min()) / 0.03 ** 2
+
+
+def _ssim_frames(B, H, W, smooth):
+    """frames 0 and 1 of syn.frames at the recorded seed; the conditioning is asserted on float64"""
+    fr = syn.frames(B, H, W, seed=SSIM_SEEDS.get((B, H, W, smooth), 3), n_frames=2, smooth=smooth)
+    cond = _ssim_cond(fr[0], fr[1])
+    print("ssim inputs %dx%dx%d smooth=%d: min(sigma1_sq + sigma2_sq + C2) / C2 = %.1f" % (B, H, W, smooth, cond))
+    assert cond >= SSIM_MIN_COND, (B, H, W, smooth, cond)
+    return fr[0], fr[1]
+
+
+def _at_offset(t, off):
+    """t's values in a fresh contiguous tensor that starts `off` floats behind a 16-byte boundary"""
+    buf = torch.empty(t.numel() + 4, dtype=t.dtype, device=t.device)
+    assert buf.data_ptr() % 16 == 0
+    v = buf[off:off + t.numel()].view(t.shape)
+    v.copy_(t)
+    assert v.is_contiguous() and v.data_ptr() % 16 == (4 * off) % 16
+    return v
+
+
+def _photo_inputs(B, H, W, smooth):
+    """tgt, warped and the mask tensors of one photometric term.  warped = frame 1 with EXACT zeros in all three channels of a band
+    of columns (28..37: across the border of tile columns 0 and 1, where W allows), of the last image row and of three isolated
+    pixels; one pixel with only two channels zeroed stays valid.  mask_a = channel 2 of A [B,4,H,W] in {0, 1}, mask_b = channel 1 of
+    Bm [B,3,H,W] (sigmoid): with the gradient buffer [B,5,H,W] three different batch strides."""
+    x, y = _ssim_frames(B, H, W, smooth)
+    warped = y.clone()
+    c0, c1 = (28, 38) if W >= 40 else (W // 2, W // 2 + W // 8)
+    warped[:, :, :, c0:c1] = 0
+    warped[:, :, H - 1] = 0
+    for b, r, c in ((0, H // 3, W - 1), (B - 1, H // 2, W // 3), (0, 0, 1)):
+        warped[b, :, r, c] = 0
+    warped[B - 1, :2, 0, 0] = 0
+    assert float(warped[B - 1, 2, 0, 0]) != 0
+    valid = L._valid(warped.double())
+    assert float(valid[B - 1, 0, 0, 0]) == 1 and float(valid[0, 0, 0, 1]) == 0
+    share = float(valid.mean())
+    print("photo inputs %dx%dx%d smooth=%d: valid share %.3f" % (B, H, W, smooth, share))
+    assert 0.3 <= share <= 0.9, share
+    assert _ssim_cond(x, warped) >= SSIM_MIN_COND
+    g = torch.Generator().manual_seed(1000 * H + 10 * W + smooth)
+    return dict(B=B, H=H, W=W, tgt=x, warped=warped, A=(torch.rand(B, 4, H, W, generator=g) < 0.7).float(),
+                Bm=torch.sigmoid(torch.randn(B, 3, H, W, generator=g)), pre=torch.randn(B, 3, H, W, generator=g))
+
+
+def _photo_call(dev, d, args, compl=0, want_grad=1, use_a=True, use_b=True, off=0, off_b=None, flag0=0.0, bwd=(0,)):
+    """cc_ssim_photo_fwd (+ cc_ssim_photo_bwd per entry of `bwd`: its accumulate flag, scale = the device's scale_out) on fresh
+    NaN / sentinel-filled outputs; every tensor `off` floats behind a 16-byte boundary (mask_b: off_b).  -> dict of device tensors"""
+    from cc_amd._lib import engine, STREAM
+    E = engine()
+    B, H, W = d["B"], d["H"], d["W"]
+    HW = H * W
+    wssim, q, lam = args
+    put = lambda t, o=off: _at_offset(t.to(dev), o)
+    nan = lambda *s: put(torch.full(s, float("nan")))
+    tgt, warped = put(d["tgt"]), put(d["warped"])
+    A = put(d["A"]) if use_a else None
+    Bm = put(d["Bm"], off if off_b is None else off_b) if use_b else None
+    G = put(torch.full((B, 5, H, W), PHOTO_SENTINEL)) if (want_grad and use_b) else None
+    nblk = int(E.call("cc_ssim_num_blocks", B, H, W))
+    assert nblk == B * ((H + 31) // 32) * ((W + 31) // 32)
+    part = nan(nblk * 4 + 4)                                        # (+ four guard elements)
+    adj = [nan(B, 3, H, W) for _ in range(4)] if want_grad else [None] * 4
+    loss, scale, flag = torch.full((1,), PHOTO_LOSS0, device=dev), torch.full((1,), float("nan"), device=dev), torch.full((1,), flag0, device=dev)
+    ch = lambda t, c: None if t is None else LF._off(t, c * HW)
+    E.call("cc_ssim_photo_fwd", tgt, warped, ch(A, 2), 4 * HW, ch(Bm, 1), 3 * HW, compl, part, adj[0], adj[1], adj[2], adj[3], ch(G, 1), 5 * HW,
+           want_grad, wssim, q, lam, loss, scale, flag, SS.gauss13_ptr(), B, H, W, STREAM)
+    out = dict(loss=loss, scale=scale, flag=flag, part=part, adj=adj, G=G, gw={}, tgt=tgt, warped=warped)
+    for acc in bwd:
+        gw = put(d["pre"]) if acc else nan(B, 3, H, W)
+        E.call("cc_ssim_photo_bwd", adj[0], adj[1], adj[2], adj[3], tgt, warped, scale, gw, acc, SS.gauss13_ptr(), B, H, W, STREAM)
+        out["gw"][acc] = gw
+    return out
+
+
+def _tile_sums(m):
+    """[B,C,H,W] -> [B * tiles_y * tiles_x]: sums over the channels and the 32 x 32 tiles, in the single call's tile order"""
+    import torch.nn.functional as F
+    B, C, H, W = m.shape
+    th, tw = (H + 31) // 32, (W + 31) // 32
+    p = F.pad(m, (0, tw * 32 - W, 0, th * 32 - H))
+    return p.view(B, C, th, 32, tw, 32).sum((1, 3, 5)).reshape(-1)
+
+
+def _photo_ref(d, args, compl, use_a, use_b, dt):
+    """the oracle's photometric term in dtype dt -> term, scale_out, tile sums (robust, ssim loss, valid), d term / d warped,
+    d term / d mask_b [B,H,W] (or None)"""
+    wssim, q, lam = args
+    tgt, w = d["tgt"].to(dt), _leaf_as(d["warped"], dt)
+    ma = d["A"][:, 2:3].to(dt) if use_a else None
+    mbl = _leaf_as(d["Bm"][:, 1:2], dt) if use_b else None
+    masks = ([ma] if use_a else []) + ([1 - mbl if compl else mbl] if use_b else [])
+    term = L._photo_term(tgt, w, masks, wssim, q, lam)
+    grads = torch.autograd.grad(term, [w] + ([mbl] if use_b else []))
+    with torch.no_grad():
+        valid = L._valid(w)
+        diff, sl = (tgt - w) * valid, 1 - L.ssim(tgt, w) * valid
+        for m in masks:
+            diff, sl = diff * m, sl * m
+        tiles = (_tile_sums(L.robust_l1_per_pix(diff, q=q)), _tile_sums(sl), _tile_sums(valid))
+        scale = (1 - wssim) * (valid.nelement() / valid.sum()) / (3 * valid.nelement())
+    return dict(term=term.detach(), scale=scale, tiles=tiles, gw=grads[0], gmb=grads[1][:, 0] if use_b else None)
+
+
+def _photo_sum_terms(T, tag, o, r32, r64):
+    """loss_accum, scale_out and the per-tile partials of one cc_ssim_photo_fwd call against float64 (the sums' floors)"""
+    T.term("loss_accum " + tag, o["loss"], (PHOTO_LOSS0 + r32["term"]).reshape(1), (PHOTO_LOSS0 + r64["term"]).reshape(1),
+           floor=SSIM_K_LOSS * 2.0 ** -24)
+    T.term("scale_out " + tag, o["scale"], r32["scale"].reshape(1), r64["scale"].reshape(1), floor=SSIM_K_SCALE * 2.0 ** -24)
+    part = o["part"].cpu()
+    assert bool(torch.isnan(part[-4:]).all()) and not bool(torch.isnan(part[:-4]).any()), (tag, "extent of the partials")
+    part = part[:-4].view(-1, 4)
+    for k, nm in ((0, "partials_robust"), (1, "partials_ssim")):
+        T.term("%s %s" % (nm, tag), part[:, k], r32["tiles"][k], r64["tiles"][k], floor=SSIM_K_PARTIALS * 2.0 ** -24)
+    assert torch.equal(part[:, 2].double(), r64["tiles"][2]), (tag, "the valid count of a tile is exact")
+    assert bool((part[:, 3] == 0).all()), (tag, "column 3 of the partials")
+
+
+def check_ssim_map_float64(dev, shapes=SSIM_SHAPES):
+    """cc_ssim_fwd and cc_ssim_bwd (both roles: the second call with the images swapped) against L.ssim in fp32 and float64 and its
+    autograd under a random upstream gradient, at every SSIM_SHAPES shape and both smooth values."""
+    from cc_amd._lib import engine, STREAM
+    E = engine()
+    T = _RigidTerms("map", "ssim")
+    for (B, H, W) in shapes:
+        for smooth in SSIM_SMOOTH:
+            tag = "%dx%dx%d smooth=%d" % (B, H, W, smooth)
+            x, y = _ssim_frames(B, H, W, smooth)
+            go = torch.randn(B, 3, H, W, generator=torch.Generator().manual_seed(4))
+            ref = {}
+            for dt in (torch.float32, torch.float64):
+                xl, yl = _leaf_as(x, dt), _leaf_as(y, dt)
+                s = L.ssim(xl, yl)
+                ref[dt] = (s.detach(),) + torch.autograd.grad(s, [xl, yl], go.to(dt))
+            nan = lambda: torch.full((B, 3, H, W), float("nan"), device=dev)
+            xd, yd, god, out = x.to(dev), y.to(dev), go.to(dev), nan()
+            E.call("cc_ssim_fwd", xd, yd, out, SS.gauss13_ptr(), B, H, W, STREAM)
+            T.term("ssim " + tag, out, ref[torch.float32][0], ref[torch.float64][0])
+            for k, (a, b) in ((2, (xd, yd)), (1, (yd, xd))):          # the gradient goes to the SECOND image of the call
+                sa, sb, sc, g = nan(), nan(), nan(), nan()
+                E.call("cc_ssim_bwd", a, b, god, sa, sb, sc, g, SS.gauss13_ptr(), B, H, W, STREAM)
+                T.term("g_img%d %s" % (k, tag), g, ref[torch.float32][k], ref[torch.float64][k])
+    T.done()
+
+
+PHOTO_FORMS = ((True, True, 0), (True, True, 1), (False, True, 0), (False, True, 1), (True, False, 0), (False, False, 0))  # mask_a, mask_b, b_complement
+
+
+def check_ssim_photo_float64(dev, shapes=SSIM_SHAPES):
+    """cc_ssim_photo_fwd + cc_ssim_photo_bwd against oracle.losses._photo_term in fp32 and float64: loss_accum (started at
+    PHOTO_LOSS0), scale_out, the per-tile partials, gmask * scale_out, the gradient of the warped frame with accumulate 0 and 1;
+    three different batch strides, the null-mask forms, b_complement, q = 0.5 and the powf branches; want_grad = 0 with null
+    pointers gives the same bits."""
+    T = _RigidTerms("photo", "ssim")
+    for (B, H, W) in shapes:
+        for smooth in SSIM_SMOOTH:
+            d = _photo_inputs(B, H, W, smooth)
+            for args in PHOTO_ARGS:
+                for use_a, use_b, compl in PHOTO_FORMS:
+                    tag = "%dx%dx%d smooth=%d wssim=%.3g q=%.2g lambda=%.2g a=%d b=%d compl=%d" % ((B, H, W, smooth) + args + (use_a, use_b, compl))
+                    r32, r64 = (_photo_ref(d, args, compl, use_a, use_b, dt) for dt in (torch.float32, torch.float64))
+                    o = _photo_call(dev, d, args, compl, 1, use_a, use_b, bwd=(0, 1))
+                    assert float(o["flag"]) == 0, tag
+                    _photo_sum_terms(T, tag, o, r32, r64)
+                    T.term("gwarped " + tag, o["gw"][0], r32["gw"], r64["gw"])
+                    T.term("gwarped_accumulate " + tag, o["gw"][1], d["pre"] + r32["gw"], d["pre"].double() + r64["gw"])
+                    if use_b:
+                        G = o["G"].cpu()
+                        assert bool((G[:, [0, 2, 3, 4]] == PHOTO_SENTINEL).all()), (tag, "gmask: a write outside its channel")
+                        T.term("gmask " + tag, G[:, 1] * o["scale"].cpu(), r32["gmb"], r64["gmb"])
+                    if use_a and use_b and compl == 0:
+                        o0 = _photo_call(dev, d, args, compl, 0, use_a, use_b, bwd=())
+                        assert bool(torch.isnan(o0["part"][-4:]).all()) and torch.equal(o0["part"][:-4], o["part"][:-4]), (tag, "want_grad = 0", "part")
+                        for k in ("loss", "scale", "flag"):
+                            assert torch.equal(o0[k], o[k]), (tag, "want_grad = 0", k)
+    T.done()
+
+
+def _err_ref(tgt, warped, wssim, dt):
+    tgt, warped = tgt.to(dt), warped.to(dt)
+    return (1 - wssim) * L.robust_l1_per_pix(tgt - warped).mean(1, keepdim=True) + wssim * (1 - L.ssim(tgt, warped)).mean(1, keepdim=True)
+
+
+def check_ssim_err_float64(dev):
+    """cc_ssim_err_fwd: the consensus error map against float64, the valid map exactly; the warped frames of the photometric check"""
+    from cc_amd._lib import engine, STREAM
+    E = engine()
+    T = _RigidTerms("err", "ssim")
+    for (B, H, W) in SSIM_SHAPES:
+        for smooth in SSIM_SMOOTH:
+            d = _photo_inputs(B, H, W, smooth)
+            for wssim in (PHOTO_ARGS[0][0], PHOTO_ARGS[1][0]):
+                tag = "%dx%dx%d smooth=%d wssim=%.3g" % (B, H, W, smooth, wssim)
+                err, valid = (torch.full((B, 1, H, W), float("nan"), device=dev) for _ in range(2))
+                E.call("cc_ssim_err_fwd", d["tgt"].to(dev), d["warped"].to(dev), err, valid, wssim, SS.gauss13_ptr(), B, H, W, STREAM)
+                T.term("err " + tag, err, _err_ref(d["tgt"], d["warped"], wssim, torch.float32), _err_ref(d["tgt"], d["warped"], wssim, torch.float64))
+                assert torch.equal(valid.cpu(), L._valid(d["warped"])), (tag, "valid")
+    T.done()
+
+
+def check_ssim_load_paths(dev):
+    """The VEC, `pairs` and scalar forms of load_row16 / load4 / store4 / the adjoint's staging loop only move values: at 2x40x72 the
+    same data at offsets of 0, 2 and 1 floats from a 16-byte boundary (and mask_b alone one float off: ssim_vec_ok falls back for the
+    whole launch) gives the same bits in every output of cc_ssim_fwd, cc_ssim_err_fwd, cc_ssim_photo_fwd and cc_ssim_photo_bwd."""
+    from cc_amd._lib import engine, STREAM
+    E = engine()
+    B, H, W = SSIM_SHAPES[0]
+    d = _photo_inputs(B, H, W, 0)
+
+    def same(tag, a, b):
+        a, b = a.cpu(), b.cpu()
+        assert not bool(torch.isnan(a).any()), (tag, "an element was not written")
+        assert torch.equal(a, b), (tag, "differs in %d elements, max %.3e" % (int((a != b).sum()), float((a - b).abs().max())))
+
+    for args in PHOTO_ARGS:
+        base = None
+        for form, off, off_b in (("vec", 0, None), ("pairs", 2, None), ("scalar", 1, None), ("mask_b + 1", 0, 1)):
+            o = _photo_call(dev, d, args, compl=1, off=off, off_b=off_b, bwd=(0, 1))
+            assert o["tgt"].data_ptr() % 16 == 4 * off and float(o["flag"]) == 0
+            o["part"] = o["part"][:-4]
+            if off_b is None:
+                nan = lambda *s: _at_offset(torch.full(s, float("nan"), device=dev), off)
+                o["map"], o["err"], o["valid"] = nan(B, 3, H, W), nan(B, 1, H, W), nan(B, 1, H, W)
+                E.call("cc_ssim_fwd", o["tgt"], o["warped"], o["map"], SS.gauss13_ptr(), B, H, W, STREAM)
+                E.call("cc_ssim_err_fwd", o["tgt"], o["warped"], o["err"], o["valid"], args[0], SS.gauss13_ptr(), B, H, W, STREAM)
+            if base is None:
+                base = o
+                continue
+            for k in ("loss", "scale", "part", "G") + (("map", "err", "valid") if off_b is None else ()):
+                same("%s / vec: %s" % (form, k), o[k], base[k])
+            for k in range(4):
+                same("%s / vec: adjoint map %d" % (form, k), o["adj"][k], base["adj"][k])
+            for acc in (0, 1):
+                same("%s / vec: gwarped accumulate=%d" % (form, acc), o["gw"][acc], base["gw"][acc])
+
+
+SSIM_JOB_SHAPES = ((8, 26), (20, 53), (40, 72))        # 2, 4 and 12 tiles per job at B = 2: 12 = 8 + 4 makes tile_of's deal-out a real permutation
+
+
+def _photo_jobs(dev, rows, args, compl=1, flag0=0.0):
+    """ONE cc_ssim_photo_fwd_jobs / cc_ssim_photo_bwd_jobs / cc_ssim_err_fwd_jobs launch each over `rows` (_photo_inputs dicts),
+    NaN / sentinel-filled outputs with guard elements -> dict of device tensors (lists: one entry per row)"""
+    from cc_amd._lib import engine, STREAM
+    E = engine()
+    B = rows[0]["B"]
+    wssim, q, lam = args
+    n = len(rows)
+    nan = lambda k: torch.full((k,), float("nan"), device=dev)
+    nblk = [B * ((d["H"] + 31) // 32) * ((d["W"] + 31) // 32) for d in rows]
+    offs = [0]
+    for k in nblk:
+        offs.append(offs[-1] + 4 * k)
+    part = nan(offs[-1] + 4)
+    px = [B * 3 * d["H"] * d["W"] for d in rows]
+    dv = [{k: d[k].to(dev) for k in ("tgt", "warped", "A", "Bm")} for d in rows]
+    adj = [nan(4 * p + 1) for p in px]
+    G = [torch.full((B, 5, d["H"], d["W"]), PHOTO_SENTINEL, device=dev) for d in rows]
+    gw, err, valid = [nan(p + 1) for p in px], [nan(p // 3 + 1) for p in px], [nan(p // 3 + 1) for p in px]
+    loss, scale, flag = torch.full((1,), PHOTO_LOSS0, device=dev), nan(n + 1), torch.full((1,), flag0, device=dev)
+    jb = LF._Jobs()
+    for i, d in enumerate(rows):
+        HW = d["H"] * d["W"]
+        jb.add([dv[i]["tgt"], dv[i]["warped"], LF._off(dv[i]["A"], 2 * HW), LF._off(dv[i]["Bm"], HW), LF._off(G[i], HW), adj[i],
+                LF._off(part, offs[i]), 4 | (3 << 8) | (5 << 16)], d["H"], d["W"])
+    E.call("cc_ssim_photo_fwd_jobs", jb.pack(), n, B, compl, 1, wssim, q, lam, loss, scale, flag, SS.gauss13_ptr(), STREAM)
+    jb = LF._Jobs()
+    for i, d in enumerate(rows):
+        jb.add([adj[i], dv[i]["tgt"], dv[i]["warped"], LF._off(scale, i), gw[i]], d["H"], d["W"])
+    E.call("cc_ssim_photo_bwd_jobs", jb.pack(), n, B, SS.gauss13_ptr(), STREAM)
+    jb = LF._Jobs()
+    for i, d in enumerate(rows):
+        jb.add([dv[i]["tgt"], dv[i]["warped"], err[i], valid[i]], d["H"], d["W"])
+    E.call("cc_ssim_err_fwd_jobs", jb.pack(), n, B, wssim, SS.gauss13_ptr(), STREAM)
+    return dict(loss=loss, scale=scale, flag=flag, part=part, offs=offs, adj=adj, G=G, gw=gw, err=err, valid=valid, dv=dv)
+
+
+def check_ssim_single_call_equals_job_row(dev):
+    """check_single_call_equals_job_row for the SSIM family: one launch of cc_ssim_photo_fwd_jobs, cc_ssim_photo_bwd_jobs and
+    cc_ssim_err_fwd_jobs over three rows (SSIM_JOB_SHAPES, B = 2; slot 7 = three different batch strides) and the single calls on
+    each row's tensors.  torch.equal: the four adjoint maps, gmask (with the untouched channels around it), gwarped (both forms
+    scaled by the table's scale_out[j]), err, valid and every row's partials (`local` of tile_of is the single call's tile index,
+    block_sum_256 is the same).  scale_out[j] and the loss come from another reduction (one wave per job, the terms added in job
+    order): held to the float64 bars of check_ssim_photo_float64.  Every area is written over its whole extent (no NaN left) and
+    not beyond (guard elements, sentinels)."""
+    from cc_amd._lib import engine, STREAM
+    E = engine()
+    T = _RigidTerms("jobs", "ssim")
+    B = 2
+    rows = [_photo_inputs(B, H, W, 0) for H, W in SSIM_JOB_SHAPES]
+
+    def eq(tag, a, b):
+        assert a.shape == b.shape, (tag, a.shape, b.shape)
+        assert not bool(torch.isnan(a).any() | torch.isnan(b).any()), (tag, "an element was not written")
+        assert torch.equal(a, b), (tag, "differs in %d elements, max %.3e" % (int((a != b).sum()), float((a - b).abs().max())))
+
+    def body(tag, t):
+        assert bool(torch.isnan(t[-1])), (tag, "a write behind the documented extent")
+        return t[:-1]
+
+    for args in PHOTO_ARGS:
+        for compl in (0, 1):
+            J = _photo_jobs(dev, rows, args, compl)
+            assert float(J["flag"]) == 0
+            assert bool(torch.isnan(J["part"][-4:]).all()) and bool(torch.isnan(J["scale"][-1])), "extent of the partial areas / of scale_out"
+            r32 = [_photo_ref(d, args, compl, True, True, torch.float32) for d in rows]
+            r64 = [_photo_ref(d, args, compl, True, True, torch.float64) for d in rows]
+            for i, d in enumerate(rows):
+                tag = "%dx%d wssim=%.3g q=%.2g compl=%d row %d" % (d["H"], d["W"], args[0], args[1], compl, i)
+                H, W = d["H"], d["W"]
+                S = _photo_call(dev, d, args, compl, bwd=())
+                eq("adjoint maps " + tag, body("adjoint maps " + tag, J["adj"][i]), torch.cat([a.reshape(-1) for a in S["adj"]]))
+                eq("gmask " + tag, J["G"][i], S["G"])
+                assert bool((J["G"][i][:, [0, 2, 3, 4]] == PHOTO_SENTINEL).all()), (tag, "gmask: a write outside its channel")
+                eq("partials " + tag, J["part"][J["offs"][i]:J["offs"][i + 1]], S["part"][:-4])
+                gw = torch.full((B, 3, H, W), float("nan"), device=dev)
+                E.call("cc_ssim_photo_bwd", S["adj"][0], S["adj"][1], S["adj"][2], S["adj"][3], S["tgt"], S["warped"], LF._off(J["scale"], i), gw, 0,
+                       SS.gauss13_ptr(), B, H, W, STREAM)
+                eq("gwarped " + tag, body("gwarped " + tag, J["gw"][i]).view(B, 3, H, W), gw)
+                err, valid = (torch.full((B, 1, H, W), float("nan"), device=dev) for _ in range(2))
+                E.call("cc_ssim_err_fwd", S["tgt"], S["warped"], err, valid, args[0], SS.gauss13_ptr(), B, H, W, STREAM)
+                eq("err " + tag, body("err " + tag, J["err"][i]).view(B, 1, H, W), err)
+                eq("valid " + tag, body("valid " + tag, J["valid"][i]).view(B, 1, H, W), valid)
+                T.term("scale_out " + tag, J["scale"][i:i + 1], r32[i]["scale"].reshape(1), r64[i]["scale"].reshape(1), floor=SSIM_K_SCALE * 2.0 ** -24)
+                T.term("gwarped " + tag, gw, r32[i]["gw"], r64[i]["gw"])
+            tag = "wssim=%.3g q=%.2g compl=%d" % (args[0], args[1], compl)
+            T.term("loss_accum " + tag, J["loss"], (PHOTO_LOSS0 + sum(r["term"] for r in r32)).reshape(1),
+                   (PHOTO_LOSS0 + sum(r["term"] for r in r64)).reshape(1), floor=SSIM_K_LOSS * 2.0 ** -24)
+    T.done()
+
+
+def check_ssim_nan_flag(dev):
+    """The NaN flag of k_photo_finalize / k_photo_finalize_jobs (the deferred form of the reference's `assert loss == loss`) on real
+    input, single call and job table, on the 40x72 row.  (These kernels form no address from data: a non-finite pixel moves no
+    access.)"""
+    B = 2
+    args = PHOTO_ARGS[0]
+    rows = [_photo_inputs(B, H, W, 0) for H, W in SSIM_JOB_SHAPES]
+    d = rows[-1]
+    H, W = d["H"], d["W"]
+    ref = lambda e: float(L._photo_term(e["tgt"], e["warped"], [e["A"][:, 2:3], e["Bm"][:, 1:2]], *args))
+    clean = _photo_call(dev, d, args, bwd=())
+    clean_j = _photo_jobs(dev, rows, args, 0)
+    for o, scale in ((clean, clean["scale"]), (clean_j, clean_j["scale"][:-1])):          # (the table's scale_out ends in a guard element)
+        assert float(o["flag"]) == 0 and bool(torch.isfinite(o["loss"]).all()) and bool(torch.isfinite(scale).all())
+    assert np.isfinite(ref(d))
+    # a flag that is already raised is not cleared by a clean call
+    assert float(_photo_call(dev, d, args, bwd=(), flag0=1.0)["flag"]) == 1
+    assert float(_photo_jobs(dev, rows, args, 0, flag0=1.0)["flag"]) == 1
+    bad_tgt = dict(d, tgt=d["tgt"].clone())
+    bad_tgt["tgt"][B - 1, 2, H - 1, W - 1] = float("nan")          # the last pixel of the ragged corner tile
+    bad_w = dict(d, warped=d["warped"].clone())
+    assert float(L._valid(d["warped"])[0, 0, 5, 5]) == 1
+    bad_w["warped"][0, 1, 5, 5] = float("nan")                     # one channel: NaN != 0, the pixel counts as valid
+    for tag, e in (("NaN in tgt", bad_tgt), ("NaN in warped", bad_w)):
+        assert np.isnan(ref(e)), (tag, "the fp32 oracle's term")
+        o = _photo_call(dev, e, args, bwd=())
+        assert float(o["flag"]) == 1 and bool(torch.isnan(o["loss"]).all()), (tag, "single call", o["flag"], o["loss"])
+        assert torch.equal(o["scale"], clean["scale"]), tag          # (the valid count does not see the NaN)
+        o = _photo_jobs(dev, rows[:-1] + [e], args, 0)
+        assert float(o["flag"]) == 1 and bool(torch.isnan(o["loss"]).all()), (tag, "job table", o["flag"], o["loss"])
+        assert bool(torch.isfinite(o["scale"][:-1]).all()) and torch.equal(o["scale"][:-1], clean_j["scale"][:-1]), (tag, "scale_out of the rows")
+    # warped all zeros: oob = N / 0 = inf and the term is inf on both sides; inf == inf, so the reference's assertion passes too
+    zero = dict(d, warped=torch.zeros_like(d["warped"]))
+    assert ref(zero) == float("inf")
+    for o in (_photo_call(dev, zero, args, bwd=()), _photo_jobs(dev, rows[:-1] + [zero], args, 0)):
+        assert float(o["flag"]) == 0 and float(o["loss"]) == float("inf"), (o["flag"], o["loss"])

@@ -261,6 +261,33 @@ def test_single_call_equals_job_row():
     parity.check_single_call_equals_job_row("cpu")
 
 
+# the SSIM / photometric kernels against the oracle in float64, per entry point (bars: parity.RIGID_MARGIN, parity.SSIM_K_*)
+@pytest.mark.parametrize("shape", parity.SSIM_SHAPES, ids=lambda s: "x".join(map(str, s)))
+def test_ssim_map_float64(shape):
+    parity.check_ssim_map_float64("cpu", (shape,))
+
+
+@pytest.mark.parametrize("shape", parity.SSIM_SHAPES, ids=lambda s: "x".join(map(str, s)))
+def test_ssim_photo_term_float64(shape):
+    parity.check_ssim_photo_float64("cpu", (shape,))
+
+
+def test_ssim_err_maps_float64():
+    parity.check_ssim_err_float64("cpu")
+
+
+def test_ssim_load_paths_give_the_same_bits():
+    parity.check_ssim_load_paths("cpu")
+
+
+def test_ssim_single_call_equals_job_row():
+    parity.check_ssim_single_call_equals_job_row("cpu")
+
+
+def test_ssim_nan_flag_on_real_input():
+    parity.check_ssim_nan_flag("cpu")
+
+
 def test_bias_gradient_table():
     parity.check_bias_grad_table("cpu")
 

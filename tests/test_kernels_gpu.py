@@ -260,6 +260,33 @@ def test_single_call_equals_job_row():
     parity.check_single_call_equals_job_row("cuda")
 
 
+# the SSIM / photometric kernels against the oracle in float64, per entry point (bars: parity.RIGID_MARGIN, parity.SSIM_K_*)
+@pytest.mark.parametrize("shape", parity.SSIM_SHAPES, ids=lambda s: "x".join(map(str, s)))
+def test_ssim_map_float64(shape):
+    parity.check_ssim_map_float64("cuda", (shape,))
+
+
+@pytest.mark.parametrize("shape", parity.SSIM_SHAPES, ids=lambda s: "x".join(map(str, s)))
+def test_ssim_photo_term_float64(shape):
+    parity.check_ssim_photo_float64("cuda", (shape,))
+
+
+def test_ssim_err_maps_float64():
+    parity.check_ssim_err_float64("cuda")
+
+
+def test_ssim_load_paths_give_the_same_bits():
+    parity.check_ssim_load_paths("cuda")
+
+
+def test_ssim_single_call_equals_job_row():
+    parity.check_ssim_single_call_equals_job_row("cuda")
+
+
+def test_ssim_nan_flag_on_real_input():
+    parity.check_ssim_nan_flag("cuda")
+
+
 def test_bias_gradient_table():
     parity.check_bias_grad_table("cuda")
     parity.check_bias_grad_table("cuda", cases=((4, 64, 64, 208, 0), (4, 16, 256, 832, 1), (4, 512, 2, 7, 0), (4, 32, 128, 416, 33)) * 9)
