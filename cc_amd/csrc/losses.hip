@@ -561,6 +561,158 @@ __global__ __launch_bounds__(256) void k_elementwise_jobs(JobTab t, int op, int 
     }
 }
 
+// ------------------------------------------------------------------ spatial normalisation (train.py:455-458, --spatial-normalize)
+// Per pyramid level and sample b: m_b = mean(x_b), dn = x / m_b (loss_functions.py:13-16), depth = 1 / dn (train.py:458) -- the
+// reference's rounding order.  A job's "image" is the N = C*H*W elements of one sample (rows carry (C*H, W)), cut into pieces of
+// SN_PPT * 256 elements, one workgroup each.  Two launches per direction for all levels:
+//   *_sum_jobs    every workgroup adds its piece in fp64 -- a work-item its SN_PPT elements in index order, the work-items in the
+//                 fixed tree of block_sum_f64 -- and stores ONE fp64 partial, unconditionally (nothing is cleared beforehand);
+//   *_apply_jobs  every workgroup adds the partials of ITS sample in index order (each arrives at the same bits), rounds the mean
+//                 to fp32 once and writes its piece.
+// No atomics, no host sync; a piece's place depends on N alone, so a level gives the same bits alone and as one row of a table.
+constexpr int SN_PPT = 16;
+
+__device__ __forceinline__ double block_sum_f64(double v, double* red) {        // red: 4 doubles; every work-item gets the total
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
+    if (lane == 0) red[wid] = v;
+    __syncthreads();
+    const double r = (red[0] + red[1]) + (red[2] + red[3]);
+    __syncthreads();
+    return r;
+}
+
+// part[0] + part[1] + ... + part[np - 1], in that order, in every work-item (staged through LDS 256 at a time: broadcast reads)
+__device__ __forceinline__ double sn_total(const double* __restrict__ part, int np, double* stage) {
+    double s = 0.0;
+    for (int i0 = 0; i0 < np; i0 += 256) {
+        const int n = np - i0 < 256 ? np - i0 : 256;
+        if ((int)threadIdx.x < n) stage[threadIdx.x] = part[i0 + threadIdx.x];
+        __syncthreads();
+        for (int i = 0; i < n; i++) s += stage[i];
+        __syncthreads();
+    }
+    return s;
+}
+
+// forward: slots 0 x [B,N], 1 dn (or 0), 2 depth (or 0), 3 m [B], 4 partials (fp64, [B][pieces])
+__global__ __launch_bounds__(256) void k_spatial_norm_sum_jobs(JobTab t) {
+    __shared__ double red[4];
+    const ccjobs::Pieces w = ccjobs::pieces<SN_PPT, false>(t);
+    const int per = (w.nb + SN_PPT - 1) / SN_PPT;
+    const float* __restrict__ x = ccjobs::ptr<const float>(t, w.j, 0) + (size_t)w.b * w.HW;
+    float v[SN_PPT];
+#pragma unroll
+    for (int k = 0; k < SN_PPT; k++) {
+        const int p = (w.blk * SN_PPT + k) * 256 + (int)threadIdx.x;
+        v[k] = p < w.HW ? x[p] : 0.f;
+    }
+    double acc = 0.0;
+#pragma unroll
+    for (int k = 0; k < SN_PPT; k++) acc += (double)v[k];
+    const double s = block_sum_f64(acc, red);
+    if (threadIdx.x == 0) ccjobs::ptr<double>(t, w.j, 4)[(size_t)w.b * per + w.blk] = s;
+}
+
+__global__ __launch_bounds__(256) void k_spatial_norm_apply_jobs(JobTab t) {
+    __shared__ double stage[256];
+    const ccjobs::Pieces w = ccjobs::pieces<SN_PPT, false>(t);
+    const int per = (w.nb + SN_PPT - 1) / SN_PPT;
+    const size_t base = (size_t)w.b * w.HW;
+    const float* __restrict__ x = ccjobs::ptr<const float>(t, w.j, 0) + base;
+    float v[SN_PPT];
+#pragma unroll
+    for (int k = 0; k < SN_PPT; k++) {
+        const int p = (w.blk * SN_PPT + k) * 256 + (int)threadIdx.x;
+        v[k] = p < w.HW ? x[p] : 0.f;
+    }
+    const float m = (float)(sn_total(ccjobs::ptr<const double>(t, w.j, 4) + (size_t)w.b * per, per, stage) / (double)w.HW);
+    if (w.blk == 0 && threadIdx.x == 0) ccjobs::ptr<float>(t, w.j, 3)[w.b] = m;
+    float* __restrict__ dn = ccjobs::ptr<float>(t, w.j, 1);
+    float* __restrict__ dp = ccjobs::ptr<float>(t, w.j, 2);
+#pragma unroll
+    for (int k = 0; k < SN_PPT; k++) {
+        const int p = (w.blk * SN_PPT + k) * 256 + (int)threadIdx.x;
+        if (p < w.HW) {
+            const float q = v[k] / m;
+            if (dn) dn[base + p] = q;
+            if (dp) dp[base + p] = 1.0f / q;
+        }
+    }
+}
+
+// backward: slots 0 g_dn (or 0), 1 g_depth (or 0), 2 dn, 3 depth, 4 m [B], 5 gx, 6 partials (fp64, [B][pieces])
+//   h = g_dn - g_depth * depth^2,  s_b = sum_j h_j dn_j,  gx_i = (h_i - s_b / N) / m_b      (d dn_j / d x_i = (delta_ij - dn_j / N) / m)
+__device__ __forceinline__ float sn_h(const float* __restrict__ gdn, const float* __restrict__ gdp, const float* __restrict__ dp, size_t i) {
+    if (!gdp) return gdn[i];
+    const float d = dp[i];
+    const float q = gdp[i] * (d * d);
+    return gdn ? gdn[i] - q : -q;
+}
+
+__global__ __launch_bounds__(256) void k_spatial_norm_bwd_sum_jobs(JobTab t) {
+    __shared__ double red[4];
+    const ccjobs::Pieces w = ccjobs::pieces<SN_PPT, false>(t);
+    const int per = (w.nb + SN_PPT - 1) / SN_PPT;
+    const size_t base = (size_t)w.b * w.HW;
+    const float* __restrict__ gdn = ccjobs::ptr<const float>(t, w.j, 0);
+    const float* __restrict__ gdp = ccjobs::ptr<const float>(t, w.j, 1);
+    const float* __restrict__ dn = ccjobs::ptr<const float>(t, w.j, 2);
+    const float* __restrict__ dp = ccjobs::ptr<const float>(t, w.j, 3);
+    float v[SN_PPT];
+#pragma unroll
+    for (int k = 0; k < SN_PPT; k++) {
+        const int p = (w.blk * SN_PPT + k) * 256 + (int)threadIdx.x;
+        v[k] = p < w.HW ? sn_h(gdn, gdp, dp, base + p) * dn[base + p] : 0.f;
+    }
+    double acc = 0.0;
+#pragma unroll
+    for (int k = 0; k < SN_PPT; k++) acc += (double)v[k];
+    const double s = block_sum_f64(acc, red);
+    if (threadIdx.x == 0) ccjobs::ptr<double>(t, w.j, 6)[(size_t)w.b * per + w.blk] = s;
+}
+
+__global__ __launch_bounds__(256) void k_spatial_norm_bwd_apply_jobs(JobTab t) {
+    __shared__ double stage[256];
+    const ccjobs::Pieces w = ccjobs::pieces<SN_PPT, false>(t);
+    const int per = (w.nb + SN_PPT - 1) / SN_PPT;
+    const size_t base = (size_t)w.b * w.HW;
+    const float* __restrict__ gdn = ccjobs::ptr<const float>(t, w.j, 0);
+    const float* __restrict__ gdp = ccjobs::ptr<const float>(t, w.j, 1);
+    const float* __restrict__ dp = ccjobs::ptr<const float>(t, w.j, 3);
+    float h[SN_PPT];
+#pragma unroll
+    for (int k = 0; k < SN_PPT; k++) {
+        const int p = (w.blk * SN_PPT + k) * 256 + (int)threadIdx.x;
+        h[k] = p < w.HW ? sn_h(gdn, gdp, dp, base + p) : 0.f;
+    }
+    const float mean = (float)(sn_total(ccjobs::ptr<const double>(t, w.j, 6) + (size_t)w.b * per, per, stage) / (double)w.HW);
+    const float m = ccjobs::ptr<const float>(t, w.j, 4)[w.b];
+    float* __restrict__ gx = ccjobs::ptr<float>(t, w.j, 5);
+#pragma unroll
+    for (int k = 0; k < SN_PPT; k++) {
+        const int p = (w.blk * SN_PPT + k) * 256 + (int)threadIdx.x;
+        if (p < w.HW) gx[base + p] = (h[k] - mean) / m;
+    }
+}
+
+// the table of a spatial-normalisation launch: SN_PPT pieces per workgroup, every sample below 2^31 elements, `need` slots set
+inline int sn_table(JobTab& t, const long* jobs, int njobs, int B, unsigned need) {
+    if (!jobs || njobs <= 0 || njobs > ccjobs::MAXJOBS || B <= 0) return -1;
+    long tot = 0;
+    for (int j = 0; j < njobs; j++) {
+        const long* q = jobs + (long)j * ccjobs::JOB_LONGS;
+        const long H = q[ccjobs::SLOTS], W = q[ccjobs::SLOTS + 1];
+        if (H <= 0 || W <= 0 || H * W >= (1l << 31) - 256 * SN_PPT) return -1;
+        for (int k = 0; k < ccjobs::SLOTS; k++)
+            if (((need >> k) & 1) && !q[k]) return -1;
+        tot += (long)B * ccjobs::pix_blocks_ppt<SN_PPT>((int)H, (int)W);
+        if (tot >= (1l << 31)) return -1;
+    }
+    return ccjobs::fill(t, jobs, njobs, B, ccjobs::pix_blocks_ppt<SN_PPT>);
+}
+
 }  // namespace
 
 extern "C" {
@@ -847,6 +999,34 @@ int cc_consensus_bce_fwd_bwd_jobs(const long* jobs, int njobs, int B, float* par
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(k_consensus_bce_jobs, dim3((unsigned)nblk), dim3(256), 0, s, t, thresh, wbce, 1.f - wbce, gscale);
     hipLaunchKernelGGL(k_reduce_add, dim3(1), dim3(256), 0, s, (const float*)partials, nblk, 1.0f, loss_accum);
+    CC_CHECK_LAUNCH();
+    return CC_OK;
+}
+
+/* ---- spatial normalisation of all pyramid levels (kernels above; rows carry (C*H, W): n = C*H*W elements per sample).
+ * A job's fp64 partial area holds B * cc_spatial_norm_pieces(n) values; it is written before it is read, by these launches only. */
+size_t cc_spatial_norm_pieces(long n) { return n > 0 ? (size_t)(((n + 255) / 256 + SN_PPT - 1) / SN_PPT) : 0; }
+
+int cc_spatial_norm_fwd_jobs(const long* jobs, int njobs, int B, void* stream) {
+    ccjobs::JobTab t;
+    const int nblk = sn_table(t, jobs, njobs, B, 0x19u);           // x, m, partials
+    if (nblk <= 0) return CC_ERR_ARG;
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_spatial_norm_sum_jobs, dim3((unsigned)nblk), dim3(256), 0, s, t);
+    hipLaunchKernelGGL(k_spatial_norm_apply_jobs, dim3((unsigned)nblk), dim3(256), 0, s, t);
+    CC_CHECK_LAUNCH();
+    return CC_OK;
+}
+
+int cc_spatial_norm_bwd_jobs(const long* jobs, int njobs, int B, void* stream) {
+    ccjobs::JobTab t;
+    const int nblk = sn_table(t, jobs, njobs, B, 0x7cu);           // dn, depth, m, gx, partials
+    if (nblk <= 0) return CC_ERR_ARG;
+    for (int j = 0; j < njobs; j++)
+        if (!t.slot[j][0] && !t.slot[j][1]) return CC_ERR_ARG;     // (a level without a gradient is left out by the caller)
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_spatial_norm_bwd_sum_jobs, dim3((unsigned)nblk), dim3(256), 0, s, t);
+    hipLaunchKernelGGL(k_spatial_norm_bwd_apply_jobs, dim3((unsigned)nblk), dim3(256), 0, s, t);
     CC_CHECK_LAUNCH();
     return CC_OK;
 }

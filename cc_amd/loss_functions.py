@@ -427,6 +427,70 @@ def reciprocal_levels(xs):
     return list(_RecipLevelsFn.apply(*xs))
 
 
+def _sn_partials(xs):
+    """-> (per-level device addresses, the buffer) of the fp64 partial areas of a cc_spatial_norm_*_jobs call over the maps xs."""
+    E = engine()
+    n = [x.shape[0] * E.call("cc_spatial_norm_pieces", x[0].numel()) for x in xs]
+    buf = torch.empty(max(sum(n), 1), device=xs[0].device, dtype=torch.float64)
+    base, addr, off = E._ptr(buf, "job", 0), [], 0
+    for k in n:
+        addr.append(base + 8 * off)
+        off += k
+    return addr, buf
+
+
+def _sn_hw(x):
+    return x.shape[1] * x.shape[2], x.shape[3]             # (a sample's C*H*W elements as (C*H, W))
+
+
+class _NormDepthLevelsFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, *xs):
+        xs = [_f32c(x) for x in xs]
+        dns, dps = [torch.empty_like(x) for x in xs], [torch.empty_like(x) for x in xs]
+        ms = [torch.empty(x.shape[0], device=x.device, dtype=torch.float32) for x in xs]
+        part, _buf = _sn_partials(xs)
+        jb = _Jobs()
+        for x, dn, dp, m, pa in zip(xs, dns, dps, ms, part):
+            jb.add([x, dn, dp, m, pa], *_sn_hw(x), key=x.shape[0])
+        _launch_jobs("cc_spatial_norm_fwd_jobs", jb, lambda j0, j1: (jb.rows[j0][3], STREAM))
+        ctx.save_for_backward(*(dns + dps + ms))
+        ctx.set_materialize_grads(False)
+        return tuple(dns) + tuple(dps)
+
+    @staticmethod
+    def backward(ctx, *gs):
+        n = len(gs) // 2
+        saved = ctx.saved_tensors
+        dns, dps, ms = saved[:n], saved[n:2 * n], saved[2 * n:]
+        out = [None] * n
+        live = [k for k in range(n) if gs[k] is not None or gs[n + k] is not None]
+        if live:
+            part, _buf = _sn_partials([dns[k] for k in live])
+            jb = _Jobs()
+            for k, pa in zip(live, part):
+                out[k] = torch.empty_like(dns[k])
+                g_dn, g_dp = gs[k], gs[n + k]
+                jb.add([None if g_dn is None else _f32c(g_dn), None if g_dp is None else _f32c(g_dp), dns[k], dps[k], ms[k], out[k], pa],
+                       *_sn_hw(dns[k]), key=dns[k].shape[0])
+            _launch_jobs("cc_spatial_norm_bwd_jobs", jb, lambda j0, j1: (jb.rows[j0][3], STREAM))
+        return tuple(out)
+
+
+def normalized_depth_levels(xs):
+    """([d / mean(d) per sample for d in xs], [1 / that ...]) (train.py:455-458 with --spatial-normalize: spatial_normalize, then
+    depth = 1 / disparity) for the maps of all scales: two launches, and two for the backward; the means are summed in fp64 in a fixed
+    order (bit-reproducible, whatever the other levels of the call are)."""
+    xs = list(xs)
+    res = _NormDepthLevelsFn.apply(*xs)
+    return list(res[:len(xs)]), list(res[len(xs):])
+
+
+def spatial_normalize_levels(xs):
+    """[spatial_normalize(d) for d in xs] on the kernels of normalized_depth_levels."""
+    return normalized_depth_levels(xs)[0]
+
+
 def abs_diff_levels(a_list, b_list):
     """[(a - b).abs() ...] WITHOUT gradient (train.py:475-476: the rigidity masks only ever enter `< THRESH` comparisons)."""
     with torch.no_grad():

@@ -38,6 +38,9 @@ class StepConfig:
         self.wssim, self.wrig, self.wbce = 0.997, 1.0, 0.5
         self.THRESH, self.qch, self.lambda_oob = 0.01, 0.5, 0.0
         self.smoothness_type = "edgeaware"
+        # --spatial-normalize (train.py:455-456: every disparity level divided by its per-sample mean before depth = 1 / disp) and
+        # --no-non-rigid-mask (train.py:483-488: the flow photometric loss without the 1 - exp_mask[:, 1:3] weighting)
+        self.spatial_normalize, self.no_non_rigid_mask = False, False
         self.lr, self.betas = 1e-4, (0.9, 0.999)
         self.weight_decay, self.eps = 0.0, 1e-8                                    # --weight-decay; torch.optim.Adam's default eps
         # gradient guard inside the step, per network (FlatAdam): None = off; a float > 0 = clip every network's gradient to that
@@ -154,7 +157,10 @@ def cc_forward(nets, batch, cfg, keep=False, cut=None, streams=None, after_fork=
                 for t in _tensors(outs):
                     t.record_stream(cur)
     disparities = _cut("dp", disp_out)
-    depth = LF.reciprocal_levels(disparities)                                          # :458  [1 / d for d in disparities]
+    if cfg.spatial_normalize:
+        disparities, depth = LF.normalized_depth_levels(disparities)                   # :455-458  d / mean(d), then 1 / that
+    else:
+        depth = LF.reciprocal_levels(disparities)                                      # :458  [1 / d for d in disparities]
     pose = _cut("dp", [pose_out])[0]
     out = {}
     if mask_net is None or flow_net is None:                                           # BASELINE config 2
@@ -169,7 +175,10 @@ def cc_forward(nets, batch, cfg, keep=False, cut=None, streams=None, after_fork=
     flow_fwd, flow_bwd, _ = flow_out
     flow_fwd, flow_bwd = _cut("mf", list(flow_fwd)), _cut("mf", list(flow_bwd))
     cam_fwd, cam_bwd = LF.rigid_flows_levels(depth, pose, (2, 1), K, Kinv)             # :470-471  pose2flow per scale
-    flow_exp_mask = LF.complement_slice_levels(exp_mask, 1, 3)                         # :488  1 - m[:, 1:3]
+    if cfg.no_non_rigid_mask:
+        flow_exp_mask = [None] * len(exp_mask)                                         # :483-484
+    else:
+        flow_exp_mask = LF.complement_slice_levels(exp_mask, 1, 3)                     # :488  1 - m[:, 1:3]
     # config.loss_stream: the loss phase is the one part of the step a single stream runs alone (every network's forward pass is done,
     # no backward pass can start: 1.2 ms of latency-bound kernels, tools/branch_timeline.py).  Its two independent halves -- the
     # consensus target + the flow photometric loss, and the rigid photometric loss + the mask / smoothness terms -- run side by side:
@@ -1148,6 +1157,20 @@ class CCTrainer:
             for a, b in zip(dst, src):
                 a.copy_(b)
 
+    def _capture_stream(self):
+        """The stream the warm-up and the capture run on: none of the networks' side streams.  torch hands its streams out of a pool
+        of 32 per priority, round-robin, and torch.cuda.graph's default capture stream is ONE of them for the whole process -- so the
+        side streams of the 10th or 20th trainer of a process can BE that stream.  The step's own stream and a network's stream are
+        then one: the per-stream weight-gradient queues (ops._PerStream, keyed by stream) merge, same-shaped layers of two networks
+        (PoseNetB6 conv3 with Back2Future conv3a-c) gather into one group launch with another split, and the captured step differs
+        from every other trainer's in the last bit of those gradients (and loses the overlap)."""
+        taken = {st.cuda_stream for st in (self.net_streams or ())} | {torch.cuda.current_stream().cuda_stream}
+        for _ in range(64):
+            s = torch.cuda.Stream()
+            if s.cuda_stream not in taken:
+                return s
+        raise RuntimeError("no HIP stream apart from the networks' side streams")
+
     def capture(self, batch, warmup=2):
         """Warm up eagerly on a side stream, then capture forward+backward of one step into a hipGraph."""
         assert not config.strict_nan_checks, "config.strict_nan_checks syncs the host per loss term: use use_graph=False with it"
@@ -1162,7 +1185,7 @@ class CCTrainer:
         opt_state = [(t, t.detach().clone()) for t in (self.opt.flat_p, self.opt.exp_avg, self.opt.exp_avg_sq, self.opt.step_dev) +
                      ((self.opt.guard_dev,) if self.opt.guard else ()) +      # (guard_dev: the skip counts)
                      ((self.ledger.state,) if self.ledger is not None else ())] if pipelined else []   # (a warm-up leaves no row)
-        s = torch.cuda.Stream()
+        s = self._capture_stream()
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s):
             for _ in range(warmup):
@@ -1187,15 +1210,15 @@ class CCTrainer:
             self.graph_b = torch.cuda.CUDAGraph()
             ok = False
             try:
-                with torch.cuda.graph(self.graph, capture_error_mode=mode):
+                with torch.cuda.graph(self.graph, stream=s, capture_error_mode=mode):
                     self.losses, mf = self._stage_a(self.static_batch)
-                with torch.cuda.graph(self.graph_b, pool=self.graph.pool(), capture_error_mode=mode):
+                with torch.cuda.graph(self.graph_b, pool=self.graph.pool(), stream=s, capture_error_mode=mode):
                     self._stage_b(mf)
                 ok = True
             finally:
                 self._stage_end(failed=not ok)
         else:
-            with torch.cuda.graph(self.graph, capture_error_mode=mode):
+            with torch.cuda.graph(self.graph, stream=s, capture_error_mode=mode):
                 self.losses = self._step_pipelined(self.static_batch) if pipelined else self._fwd_bwd(self.static_batch)
         # the NaN flags of the captured step live in the graph's private pool and are rewritten by every replay: keep them
         # as persistent handles (the reference asserts on NaN at every step, loss_functions.py:60,105,115)

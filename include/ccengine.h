@@ -472,6 +472,18 @@ int cc_edge_weights_jobs(const long* jobs, int njobs, int B, void* stream);
 int cc_bce_ones_fwd_bwd_jobs(const long* jobs, int njobs, int planes, float* partials, float* loss_accum, float gscale, void* stream);
 int cc_consensus_bce_fwd_bwd_jobs(const long* jobs, int njobs, int B, float* partials, float* loss_accum, float thresh, float wbce,
                                   float gscale, void* stream);
+/* --spatial-normalize of train.py:455-458 over all scales, with its backward: per level and sample b (n = C*H*W elements, fp32,
+ * contiguous; the job's (H, W) entries carry (C*H, W)):  m_b = mean(x_b), dn = x / m_b (loss_functions.py:13-16), depth = 1 / dn.
+ *   cc_spatial_norm_fwd_jobs  slots: x, dn (or 0), depth (or 0), m [B], partials
+ *   cc_spatial_norm_bwd_jobs  slots: g_dn (or 0), g_depth (or 0; not both), dn, depth, m, gx, partials:
+ *                             h = g_dn - g_depth * depth^2, gx = (h - mean(h * dn)) / m_b
+ * Two launches each for the whole table, no atomics, no host sync: every workgroup of the first stores the fp64 sum of its piece
+ * (fixed tree) into the job's partial area -- B * cc_spatial_norm_pieces(n) doubles the caller allocates, nothing to clear --, the
+ * second adds a sample's partials in index order, rounds the mean to fp32 once and writes the maps.  A piece's place depends on n
+ * alone: a level gives the same bits called alone and as one row of a table. */
+size_t cc_spatial_norm_pieces(long n);
+int cc_spatial_norm_fwd_jobs(const long* jobs, int njobs, int B, void* stream);
+int cc_spatial_norm_bwd_jobs(const long* jobs, int njobs, int B, void* stream);
 int cc_pose_proj_levels(const float* pose, const float* K, float* P_all, int L, int R, int B, const float* kdiv_host, void* stream);
 int cc_pose_grad_jobs(const long* jobs, int njobs, int L, int R, int B, const float* pose, const float* K, float* gpose,
                       const float* kdiv_host, void* stream);
