@@ -724,7 +724,9 @@ class _NetFn(torch.autograd.Function):
         for p in ctx.params:
             ent = tape.param_grads.get(id(p))
             gpar.append(ent[1] if ent is not None else None)
-        ctx.tape = None
+        # (the context refers to the node's own output tensors, which refer to the node: drop them with the tape, so that nothing of a
+        # finished backward pass waits for the cycle collector -- a captured step's activations would hold blocks of the graph's pool)
+        ctx.tape = ctx.ins = ctx.outs = None
         if NET_DONE is not None:
             NET_DONE(getattr(ctx.body, "__self__", None))
         return (None, None) + tuple(gin) + tuple(gpar)

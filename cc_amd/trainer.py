@@ -99,8 +99,16 @@ def _tensors(x):
             yield from _tensors(y)
 
 
+def _levels(x):
+    """a network output as the list of levels the losses take: an eval-mode network returns its full-resolution level as ONE tensor
+    (and `list(tensor)` would iterate over the batch) -- that is a one-level list; a list / tuple of levels is taken as it is"""
+    return [x] if torch.is_tensor(x) else list(x)
+
+
 def cc_forward(nets, batch, cfg, keep=False, cut=None, streams=None, after_fork=None):
     """train.py:454-509.  batch = (tgt, [4 refs], K, Kinv).
+    The networks may be in eval() mode (validate.validate_without_gt_from_store, under torch.no_grad()): their single full-resolution
+    outputs -- Back2Future's (flow_fwd, flow_bwd, occ) tensors included -- are one-level pyramids of the same terms.
     cut: optional dict; when given, the losses are computed on detached copies of the network outputs and
     cut['dp'] / cut['mf'] receive the (output, detached copy) pairs of DispResNet6 + PoseNetB6 / MaskNet6 + Back2Future, so
     that the backward pass can be run in stages (losses -> copies, then each network group from its outputs)."""
@@ -138,13 +146,13 @@ def cc_forward(nets, batch, cfg, keep=False, cut=None, streams=None, after_fork=
     # order the per-network pipeline issues the networks' gradient exchanges in -- one RCCL communicator executes its collectives in
     # issue order, and Back2Future, the longest backward, must not hold up DispResNet6's segment)
     flow_out = _on(s_flow, lambda: flow_net(tgt, refs[1:3])) if full else None         # :463
-    disp_out = _on(s_disp, lambda: list(disp_net(tgt)))                                # :454
+    disp_out = _on(s_disp, lambda: _levels(disp_net(tgt)))                                # :454
     # (behind the side streams' launches, on the step's stream: nothing of it is needed before the losses / the backward pass, and
     # in front of the forks it would hold up DispResNet6, whose chain is the step's critical path)
     if after_fork is not None:
         after_fork()
     LF.pyramid_cache.prefetch([tgt] + list(refs))        # the frames' scale pyramids (every loss pools them): one launch for all five
-    mask_out = _on(s_mask, lambda: list(mask_net(tgt, refs))) if full else None        # :460
+    mask_out = _on(s_mask, lambda: _levels(mask_net(tgt, refs))) if full else None        # :460
     pose_out = pose_net(tgt, refs)                                                     # :459
     _join(forked)
     if forked and not torch.cuda.is_current_stream_capturing():
@@ -173,7 +181,7 @@ def cc_forward(nets, batch, cfg, keep=False, cut=None, streams=None, after_fork=
         return out
     exp_mask = _cut("mf", mask_out)
     flow_fwd, flow_bwd, _ = flow_out
-    flow_fwd, flow_bwd = _cut("mf", list(flow_fwd)), _cut("mf", list(flow_bwd))
+    flow_fwd, flow_bwd = _cut("mf", _levels(flow_fwd)), _cut("mf", _levels(flow_bwd))
     cam_fwd, cam_bwd = LF.rigid_flows_levels(depth, pose, (2, 1), K, Kinv)             # :470-471  pose2flow per scale
     if cfg.no_non_rigid_mask:
         flow_exp_mask = [None] * len(exp_mask)                                         # :483-484

@@ -184,6 +184,56 @@ def _flow_batch(tgt_img, ref_imgs, intrinsics, intrinsics_inv, disp_net, pose_ne
     return flow_cam, flow_fwd, r
 
 
+def validate_without_gt_from_store(store, disp_net, pose_net, mask_net, flow_net, batch_size, cfg, normalize="global"):
+    """The validation signal that needs no labels: the training losses (train.py:490-509) of the four networks in eval() mode over a
+    `datasets.FrameStore` built with train=False -- the `SequenceFolder(train=False)` train.py:209-215 builds "to measure photometric
+    loss from warping" and no reference validator ever reads.  -> (values, names), names = ledger.LOSS_NAMES: the total and the five
+    terms, each the mean over the store's samples.
+    Batches: the samples in the store's (val.txt) order, not augmented -- ArrayToTensor + Normalize (train.py:187; normalize='local':
+    NormalizeLocally), frames read where they lie; every sample is scored, the last batch may be short and weighs by its size.
+    Per batch `trainer.cc_forward` under torch.no_grad(): the eval-mode outputs are one full-resolution level each, so every term
+    is its single-scale, forward-only form (no gradient is computed or stashed).  cfg: a trainer.StepConfig (weights, wssim, qch,
+    THRESH, smoothness_type, spatial_normalize, no_non_rigid_mask ..).  The values are folded into fp64 on the device by a Ledger of
+    this call's own and read back once, after the loop."""
+    import numpy as np
+    from .custom_transforms import DeviceTrainTransform
+    from .ledger import Ledger, LOSS_NAMES
+    from .trainer import cc_forward
+    if batch_size < 1 or len(store) < 1:
+        raise ValueError("validate_without_gt_from_store: batch size %d over %d samples" % (batch_size, len(store)))
+    nets = (disp_net, pose_net, mask_net, flow_net)
+    for net in nets:
+        net.eval()
+    dev = store.device
+    prep = DeviceTrainTransform(device=dev, normalize=normalize)          # (its frame converter and local normalisation; no draws)
+    meter = Ledger(dev, capacity=64)
+    S, nf = store.samples.shape
+    _, H, W, _ = store.frames.shape
+    one = 3 * H * W
+    with torch.no_grad():
+        for lo in range(0, S, batch_size):
+            ids = np.arange(lo, min(S, lo + batch_size))
+            b = ids.size
+            x = prep.frames.store_to_tensor(store, store.samples_np[ids].T.reshape(-1)).view(nf, b, 3, H, W)    # frame-major
+            if prep.local:
+                prep._local_norm(x, b, nf, one, b * one)
+            K = store.intrinsics_np[store.sample_scene_np[ids]]
+            KK = torch.from_numpy(np.stack([K, np.stack([np.linalg.inv(k) for k in K])])).to(dev)
+            LF.pyramid_cache.clear()
+            LF.step_nan_flags = flags = []
+            try:
+                out = cc_forward(nets, (x[0], [x[j] for j in range(1, nf)], KK[0], KK[1]), cfg)
+            finally:
+                LF.step_nan_flags = None
+                LF.pyramid_cache.clear()
+            LF.take_nan_flags()                                            # (they are sources of the meter's row instead)
+            meter.append({k: (v.reshape(1) if torch.is_tensor(v) else v) for k, v in out.items()}, b, nan_flags=flags)
+    avg = meter.average()                                                  # the loop's only host read-back
+    if avg["nan"]["avg"] > 0:
+        print('NaN encountered')
+    return [avg[k]["avg"] for k in LOSS_NAMES], list(LOSS_NAMES)
+
+
 def validate_depth_from_store(store, disp_net, batch_size, args=None):
     """validate_depth_with_gt over a `datasets.DepthValStore` -> (errors, error_names).  As there, every batch's mean counts once
     (AverageMeter.update(n=1), so a short last batch weighs as much as a full one); the six errors are summed in fp64 on the
