@@ -1810,7 +1810,10 @@ def check_single_call_equals_job_row(dev):
                                                                      plane borders), the table form piece by piece of each plane
     Where the layouts differ the layout is asserted: rows k % 4 != 0 of the WPPT / PPT = 4 forms' partial areas are exactly zero,
     every partial area is written over its whole documented extent and not beyond (NaN sentinels).  The values of the sums that are
-    added in another order are left to the float64 and golden tests.  (The SSIM family: check_ssim_single_call_equals_job_row.)"""
+    added in another order are left to the float64 tests (check_edge_smooth_float64, check_bce_ones_float64,
+    check_consensus_bce_float64) and the golden tests.  The table form of edge smoothness runs a second time with the levels' edge
+    weights (cc_edge_weights_jobs) in slot 5: the same bits in loss, partials and gpred.
+    (The SSIM family: check_ssim_single_call_equals_job_row.)"""
     from cc_amd._lib import engine, STREAM
     E = engine()
     B, C, R = 2, 3, 4
@@ -1953,6 +1956,18 @@ def check_single_call_equals_job_row(dev):
         jobs("cc_edge_smooth_fwd_bwd_jobs", lambda d: [d["img"], d["pred"], gj[rows.index(d)], LF._off(part, offs[rows.index(d)])] + extra(d),
              B, C if ppt == 1 else 0, part, loss_j, gscale, STREAM)
         assert bool(torch.isnan(part[-1])) and not bool(torch.isnan(part[:-1]).any()), (tag, "extent of the partial areas")
+        # slot 5 filled: the levels' edge weights from cc_edge_weights_jobs instead of exp() per pixel and plane -- the same bits
+        wts = [nan(B, 2, d["H"], d["W"]) for d in rows]
+        jobs("cc_edge_weights_jobs", lambda d: [d["img"], wts[rows.index(d)]], B, STREAM)
+        gw, _ = outs(BCHW)
+        part_w, loss_w = nan(offs[-1] + 1), torch.zeros(1, device=dev)
+        jobs("cc_edge_smooth_fwd_bwd_jobs", lambda d: [d["img"], d["pred"], gw[rows.index(d)], LF._off(part_w, offs[rows.index(d)]),
+                                                       None if ppt == 1 else C, wts[rows.index(d)]], B, C if ppt == 1 else 0, part_w, loss_w, gscale, STREAM)
+        assert bool(torch.isnan(part_w[-1]))
+        eq(tag + " partials with slot 5", part_w[:-1], part[:-1])
+        eq(tag + " loss with slot 5", loss_w, loss_j)
+        for i in range(len(rows)):
+            eq("%s gpred with slot 5 row %d" % (tag, i), gw[i], gj[i])
         ps = [nan(B * C, n) for n in nb]
         for i, d in enumerate(rows):
             E.call("cc_edge_smooth_fwd_bwd", d["img"], d["pred"], gs[i], ps[i], torch.zeros(1, device=dev), gscale, B, C, d["H"], d["W"], STREAM)
@@ -2409,3 +2424,613 @@ def check_ssim_nan_flag(dev):
     assert ref(zero) == float("inf")
     for o in (_photo_call(dev, zero, args, bwd=()), _photo_jobs(dev, rows[:-1] + [zero], args, 0)):
         assert float(o["flag"]) == 0 and float(o["loss"]) == float("inf"), (o["flag"], o["loss"])
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The rest of csrc/losses.hip against float64, per entry point, through the C ABI: the two smoothness kernels, the two BCE kernels,
+# the consensus target, the occlusion masks, the element-wise job kernel, k_reduce_add and the pyramid.
+# Bars: e_dev <= RIGID_MARGIN * e_32 + floor with e = max|x - f64| / max|f64|, the references are oracle.losses in fp32 and float64.
+# floor = 2^-23 for per-pixel tensors; for sums of non-negative terms (asserted on float64) k * 2^-24, k = the additions on the
+# longest path from a pixel to the result:
+#   block_sum_256       6   wave_sum: six __shfl_xor levels
+#                     + 2   (w0 + w1) + (w2 + w3)                                                                = LOSSK_K_BLOCK = 8
+#   partials, per kernel (LOSSK_K): the additions of a work-item into `part`, then block_sum_256
+#     edge1           2 + 8   edge_smooth_px: `part +=` the H-direction term, `part +=` the W-direction term (k_edge_smooth, jobs<1>)
+#     edge4           8 + 8   k_edge_smooth_jobs<4>: four pixels per work-item
+#     smooth2         3 + 8   k_smooth2: dx2, dy2, dxy
+#     bce_ones        0 + 8   one term per work-item
+#     consensus_bce   5 + 8   consensus_bce_px: w1 * .. + w0 * .. inside a channel's term, `part -=` for four channels
+#   loss_accum = the kernel's k + _k_reduce(n) for n partial sums:
+#     k_reduce_add    ceil(n / 256)   a work-item adds partials[tid], [tid + 256], ... in index order
+#                   + 8               block_sum_256
+#                   + 1               accum[0] += coef * v   (cc_reduce_add on its own, coef != 1: + 1 for the product)
+# Scalars of the ABI (thresh, wbce, wrig, gscale, weight, coef) are fp32 values on all three sides.
+# Decision outputs (the occlusion masks, the consensus target) are exactly the float64 decision wherever float64's margin
+# |lhs - rhs| / max(|lhs|, |rhs|) exceeds LOSSK_DELTA; the elements inside are left out on all sides (at most RIGID_MAX_EXCLUDED).
+# LOSSK_DELTA = 1e-5: either side of such a comparison is at most eight fp32 operations on values no larger than the larger side
+# (8 * 2^-24 = 5e-7 of it), twenty times less.
+LOSSK_SHAPES = ((8, 26), (20, 53), (3, 3), (2, 3), (2, 2))       # one ragged piece; five pieces, odd width; every pixel a border pixel
+LOSSK_B = 2
+LOSSK_GSCALE = float(np.float32(0.7))
+LOSSK_DELTA = 1e-5
+LOSSK_K_BLOCK = 8
+LOSSK_K = dict(edge1=2 + LOSSK_K_BLOCK, edge4=8 + LOSSK_K_BLOCK, smooth2=3 + LOSSK_K_BLOCK, bce_ones=0 + LOSSK_K_BLOCK,
+               consensus_bce=5 + LOSSK_K_BLOCK)
+# seeds at which the inputs meet the conditions the checks assert on the float64 reference (tie shares, class shares, zero second
+# differences); every other (check, H, W) takes seed 0
+LOSSK_SEEDS = {("smooth2", 3, 3): 3, ("smooth2", 2, 2): 2, ("decisions", 2, 2): 1}
+F32, F64 = torch.float32, torch.float64
+
+
+def _k_reduce(n):
+    return (n + 255) // 256 + LOSSK_K_BLOCK + 1
+
+
+def _lossk_gen(check, H, W, extra=0):
+    seed = LOSSK_SEEDS.get((check, H, W), 0)
+    return torch.Generator().manual_seed(100003 * seed + 1009 * H + 13 * W + extra)
+
+
+def _piece_sums(m):
+    """per-pixel terms [..., H, W] -> [planes, nb]: the sums over the 256-pixel pieces of every plane (leading dimensions flattened)"""
+    import torch.nn.functional as F
+    HW = m.shape[-2] * m.shape[-1]
+    nb = (HW + 255) // 256
+    return F.pad(m.reshape(-1, HW), (0, nb * 256 - HW)).view(-1, nb, 256).sum(2)
+
+
+def _group4(ps):
+    """[planes, nb] -> the layout of a four-pieces-per-workgroup kernel: piece 4k holds the sum of pieces 4k .. 4k + 3, the others 0"""
+    out = torch.zeros_like(ps)
+    for k in range(0, ps.shape[1], 4):
+        out[:, k] = ps[:, k:k + 4].sum(1)
+    return out
+
+
+def _guarded(tag, t):
+    """a NaN-filled area with one guard element behind it: written over its whole extent and not beyond -> the area"""
+    assert bool(torch.isnan(t[-1])), (tag, "a write behind the documented extent")
+    assert not bool(torch.isnan(t[:-1]).any()), (tag, "an element of the documented extent was not written")
+    return t[:-1]
+
+
+def _lossk_jobs(name, rows, *args):
+    """ONE launch of the *_jobs entry point `name`; rows: (slots, H, W)"""
+    from cc_amd._lib import engine
+    jb = LF._Jobs()
+    for slots, H, W in rows:
+        jb.add(slots, H, W)
+    engine().call(name, jb.pack(), len(jb), *args)
+
+
+def _offsets(sizes):
+    offs = [0]
+    for n in sizes:
+        offs.append(offs[-1] + n)
+    return offs
+
+
+# ------------------------------------------------------------------ edge-aware smoothness
+def _tied_pred(check, C, H, W, planted):
+    """randn [B,C,H,W]; planted: exact ties with the left neighbour and with the upper neighbour (a tenth of the pixels each, maps
+    wider / higher than 3) and at two corners (the corner pixel's two neighbours take its value)"""
+    g = _lossk_gen(check, H, W, extra=7 * C + (1 if planted else 0))
+    p = torch.randn(LOSSK_B, C, H, W, generator=g)
+    if planted:
+        mh, mv = torch.rand(LOSSK_B, C, H, W, generator=g) < 0.1, torch.rand(LOSSK_B, C, H, W, generator=g) < 0.1
+        if W > 3:
+            for x in range(1, W):
+                p[..., x] = torch.where(mh[..., x], p[..., x - 1], p[..., x])
+        if H > 3:
+            for y in range(1, H):
+                p[..., y, :] = torch.where(mv[..., y, :], p[..., y - 1, :], p[..., y, :])
+        p[..., 0, 1] = p[..., 0, 0]
+        p[..., 1, 0] = p[..., 0, 0]
+        p[..., H - 1, W - 2] = p[..., H - 1, W - 1]
+        p[..., H - 2, W - 1] = p[..., H - 1, W - 1]
+    return p.contiguous()
+
+
+def _tie_share(p):
+    dh, dw = L._grad_h(p), L._grad_w(p)
+    return float(((dh == 0).sum() + (dw == 0).sum()).double() / (dh.numel() + dw.numel()))
+
+
+def _edge_ref(img, pred, dt):
+    """L.edge_aware_smoothness_loss of one level in dtype dt (the image is the level's: its pooling is the identity) -> loss,
+    d loss / d pred * LOSSK_GSCALE, the per-pixel terms [B,C,H,W] (both directions, anchored at the pixel), the weights [B,2,H,W]"""
+    import torch.nn.functional as F
+    im, p = img.to(dt), _leaf_as(pred, dt)
+    loss = L.edge_aware_smoothness_loss(im, [p])
+    g = torch.autograd.grad(loss, p)[0] * LOSSK_GSCALE
+    with torch.no_grad():
+        wx = torch.exp(-torch.mean(torch.abs(L._grad_h(im)), 1, keepdim=True))
+        wy = torch.exp(-torch.mean(torch.abs(L._grad_w(im)), 1, keepdim=True))
+        tx, ty = torch.abs(L._grad_h(p)) * wx, torch.abs(L._grad_w(p)) * wy
+        terms = F.pad(tx / tx.numel(), (0, 0, 0, 1)) + F.pad(ty / ty.numel(), (0, 1, 0, 0))
+        wts = torch.cat((F.pad(wy, (0, 1, 0, 0)), F.pad(wx, (0, 0, 0, 1))), 1)
+    return dict(loss=loss.detach(), g=g, terms=terms, wts=wts)
+
+
+EDGE_C0_ROWS = (((8, 26), 1), ((20, 53), 2), ((3, 3), 4), ((2, 3), 1), ((2, 2), 2), ((20, 53), 4))      # (level, channels in slot 4)
+
+
+def check_edge_smooth_float64(dev, planted=True):
+    """cc_edge_smooth_fwd_bwd, cc_edge_smooth_fwd_bwd_jobs with C = 3 and with C = 0 (EDGE_C0_ROWS: 1 / 2 / 4 channels in slot 4, four
+    pieces per workgroup) and cc_edge_weights_jobs at LOSSK_SHAPES against L.edge_aware_smoothness_loss in fp32 and float64: the
+    loss, every partial area (NaN fill + guard element), gpred under gscale = 0.7, the weights (exactly 0 in the last column / row).
+    Either table form with the weights in slot 5 is torch.equal to slot 5 null; the single call refuses a level of one row or one
+    column (the table form takes it and returns a finite number where the reference's mean of an empty tensor is NaN).  planted: `pred` holds exact ties (more than 5 % of
+    the neighbour pairs, asserted), where sgn(0) = 0 is the reference's d|x|/dx; otherwise none (asserted)."""
+    from cc_amd._lib import engine, STREAM
+    E = engine()
+    B = LOSSK_B
+    check = "edge_ties" if planted else "edge_random"
+    T = _RigidTerms(check, "lossk")
+    nan = lambda *s: torch.full(s, float("nan"), device=dev)
+    g0 = {hw: _lossk_gen("edge_img", *hw) for hw in LOSSK_SHAPES}
+    imgs = {hw: torch.rand(B, 3, hw[0], hw[1], generator=g0[hw]) * 2 - 1 for hw in LOSSK_SHAPES}
+    img_d = {hw: im.to(dev) for hw, im in imgs.items()}
+    cache = {}
+
+    def case(hw, C):
+        if (hw, C) not in cache:
+            pred = _tied_pred(check, C, hw[0], hw[1], planted)
+            share = _tie_share(pred)
+            print("%s %dx%d C=%d: tie share %.3f" % (check, hw[0], hw[1], C, share))
+            assert (share > 0.05) if planted else (share == 0), (hw, C, share)
+            r32, r64 = _edge_ref(imgs[hw], pred, F32), _edge_ref(imgs[hw], pred, F64)
+            assert float(r64["terms"].min()) >= 0
+            cache[(hw, C)] = dict(pred=pred.to(dev), r32=r32, r64=r64)
+        return cache[(hw, C)]
+
+    # ---- the weights of every level in one launch
+    wt = {hw: nan(B * 2 * hw[0] * hw[1] + 1) for hw in LOSSK_SHAPES}
+    _lossk_jobs("cc_edge_weights_jobs", [([img_d[hw], wt[hw]], hw[0], hw[1]) for hw in LOSSK_SHAPES], B, STREAM)
+    for hw in LOSSK_SHAPES:
+        tag = "%dx%d" % hw
+        w = _guarded("weights " + tag, wt[hw]).view(B, 2, hw[0], hw[1]).cpu()
+        assert bool((w[:, 0, :, -1] == 0).all()) and bool((w[:, 1, -1, :] == 0).all()), (tag, "weights beyond the last column / row")
+        T.term("weights " + tag, w, case(hw, 3)["r32"]["wts"], case(hw, 3)["r64"]["wts"])
+
+    def compare(form, ppt, rows, part, offs, gp, loss):
+        ref = [case(hw, Cj) for hw, Cj in rows]
+        _guarded(form + " partials", part)
+        k = LOSSK_K["edge%d" % ppt]
+        T.term("loss_%s" % form, loss, sum(r["r32"]["loss"] for r in ref).reshape(1), sum(r["r64"]["loss"] for r in ref).reshape(1),
+               floor=(k + _k_reduce(offs[-1])) * 2.0 ** -24)
+        grp = _group4 if ppt == 4 else (lambda x: x)
+        for i, ((hw, Cj), r) in enumerate(zip(rows, ref)):
+            tag = "%dx%d C=%d" % (hw[0], hw[1], Cj)
+            pj = part[offs[i]:offs[i + 1]].view(B * Cj, -1)
+            T.term("partials_%s %s" % (form, tag), pj, grp(_piece_sums(r["r32"]["terms"])), grp(_piece_sums(r["r64"]["terms"])), floor=k * 2.0 ** -24)
+            T.term("gpred_%s %s" % (form, tag), gp[i], r["r32"]["g"], r["r64"]["g"])
+
+    def table(rows, C, with_weights):
+        offs = _offsets([B * Cj * ((hw[0] * hw[1] + 255) // 256) for hw, Cj in rows])
+        part, loss = nan(offs[-1] + 1), torch.zeros(1, device=dev)
+        gp = [nan(B, Cj, hw[0], hw[1]) for hw, Cj in rows]
+        _lossk_jobs("cc_edge_smooth_fwd_bwd_jobs",
+                    [([img_d[hw], case(hw, Cj)["pred"], gp[i], LF._off(part, offs[i]), None if C else Cj, wt[hw] if with_weights else None],
+                      hw[0], hw[1]) for i, (hw, Cj) in enumerate(rows)], B, C, part, loss, LOSSK_GSCALE, STREAM)
+        return part, offs, gp, loss
+
+    # ---- the single call per level
+    for hw in LOSSK_SHAPES:
+        nb = (hw[0] * hw[1] + 255) // 256
+        part, loss, gp = nan(B * 3 * nb + 1), torch.zeros(1, device=dev), nan(B, 3, hw[0], hw[1])
+        E.call("cc_edge_smooth_fwd_bwd", img_d[hw], case(hw, 3)["pred"], gp, part, loss, LOSSK_GSCALE, B, 3, hw[0], hw[1], STREAM)
+        compare("single", 1, [(hw, 3)], part, [0, B * 3 * nb], [gp], loss)
+    # a level of one row or one column (the reference's loss is NaN there: the mean of an empty tensor): the single call refuses it
+    for (H, W) in ((1, 5), (4, 1)):
+        g = torch.Generator().manual_seed(31)
+        img, pred = torch.rand(B, 3, H, W, generator=g) * 2 - 1, torch.randn(B, 3, H, W, generator=g)
+        assert bool(torch.isnan(L.edge_aware_smoothness_loss(img, [pred])))
+        with pytest.raises(RuntimeError):
+            E.call("cc_edge_smooth_fwd_bwd", img.to(dev), pred.to(dev), nan(B, 3, H, W), nan(B * 3 + 1), torch.zeros(1, device=dev), LOSSK_GSCALE, B, 3, H, W, STREAM)
+    # ---- the table forms, slot 5 null and filled
+    for form, ppt, rows, C in (("jobs1", 1, [(hw, 3) for hw in LOSSK_SHAPES], 3), ("jobs4", 4, list(EDGE_C0_ROWS), 0)):
+        part, offs, gp, loss = table(rows, C, False)
+        compare(form, ppt, rows, part, offs, gp, loss)
+        part_w, _, gp_w, loss_w = table(rows, C, True)
+        assert torch.equal(loss_w, loss) and torch.equal(_guarded(form + " partials (slot 5)", part_w), part[:-1]), (form, "slot 5: loss, partials")
+        for a, b in zip(gp_w, gp):
+            assert not bool(torch.isnan(a).any()) and torch.equal(a, b), (form, "slot 5: gpred")
+    T.done()
+
+
+# ------------------------------------------------------------------ second-order smoothness
+SMOOTH2_WEIGHTS = tuple(float(np.float32(v)) for v in (1.0, 1.0 / 2.3 ** 2))
+
+
+def check_smooth2_float64(dev):
+    """cc_smooth2_fwd_bwd (no table form) against weight * L.smooth_loss in fp32 and float64 at weight = 1 and 1 / 2.3^2, gscale =
+    0.7: loss and gpred, the extent of the partials.  pred is quantised to multiples of 1/4 so that more than 5 % of the second
+    differences of each stencil are exactly 0 (asserted): sgn(0) = 0 is the reference's gradient there.  H < 3 or W < 3: NaN on
+    both sides, the gradient of the non-empty stencils."""
+    from cc_amd._lib import engine, STREAM
+    E = engine()
+    B, C = LOSSK_B, 3
+    T = _RigidTerms("smooth2", "lossk")
+    nan = lambda *s: torch.full(s, float("nan"), device=dev)
+    for (H, W) in LOSSK_SHAPES:
+        pred = torch.round(torch.randn(B, C, H, W, generator=_lossk_gen("smooth2", H, W)) * 2) / 4
+        dx, dy = pred[..., 1:] - pred[..., :-1], pred[..., 1:, :] - pred[..., :-1, :]
+        for nm, d in (("dx2", dx[..., 1:] - dx[..., :-1]), ("dxdy", dx[..., 1:, :] - dx[..., :-1, :]), ("dy2", dy[..., 1:, :] - dy[..., :-1, :])):
+            if d.numel():
+                share = float((d == 0).double().mean())
+                print("smooth2 %dx%d: share of exact zeros in %s %.3f" % (H, W, nm, share))
+                assert share > 0.05, (H, W, nm, share)
+        degenerate = H < 3 or W < 3
+        nb = (H * W + 255) // 256
+        for weight in SMOOTH2_WEIGHTS:
+            tag = "%dx%d weight=%.3g" % (H, W, weight)
+            ref = {}
+            for dt in (F32, F64):
+                p = _leaf_as(pred, dt)
+                loss = L.smooth_loss([p]) * weight
+                ref[dt] = (loss.detach(), torch.autograd.grad(loss, p)[0] * LOSSK_GSCALE)
+                assert bool(torch.isnan(loss)) == degenerate and (degenerate or float(loss) >= 0), (tag, loss)
+            part, loss, gp = nan(B * C * nb + 1), torch.zeros(1, device=dev), nan(B, C, H, W)
+            E.call("cc_smooth2_fwd_bwd", pred.to(dev), gp, part, loss, weight, LOSSK_GSCALE, B * C, H, W, STREAM)
+            _guarded("partials " + tag, part)
+            if degenerate:
+                assert bool(torch.isnan(loss).all()), (tag, loss)
+            else:
+                T.term("loss " + tag, loss, ref[F32][0].reshape(1), ref[F64][0].reshape(1), floor=(LOSSK_K["smooth2"] + _k_reduce(B * C * nb)) * 2.0 ** -24)
+            T.term("gpred " + tag, gp, ref[F32][1], ref[F64][1])
+    T.done()
+
+
+# ------------------------------------------------------------------ BCE against ones
+BCE_PLANTED = (0.0, 1.0, 1e-45, 1e-30, 1e-13, 2.0 ** -24, 1.0 - 2.0 ** -24)       # the -100 clamp of the log, the 1e-12 clamp of the gradient
+
+
+def _bce_ones_ref(mask, dt):
+    """L.explainability_loss of one level in dtype dt -> loss, d loss / d mask * LOSSK_GSCALE, the per-element terms"""
+    import torch.nn.functional as F
+    m = _leaf_as(mask, dt)
+    loss = L.explainability_loss([m])
+    g = torch.autograd.grad(loss, m)[0] * LOSSK_GSCALE
+    with torch.no_grad():
+        terms = F.binary_cross_entropy(m, torch.ones_like(m), reduction="none") / m.numel()
+    return dict(loss=loss.detach(), g=g, terms=terms.detach())
+
+
+def check_bce_ones_float64(dev, planted=True):
+    """cc_bce_ones_fwd_bwd (flat over B C H W) and cc_bce_ones_fwd_bwd_jobs (piece by piece of each plane) at LOSSK_SHAPES, C = 4,
+    against L.explainability_loss (F.binary_cross_entropy) in fp32 and float64: loss, partials, gmask under gscale = 0.7.  planted:
+    BCE_PLANTED values among the sigmoid ones; each planted element of gmask is a term of its own, the ordinary elements another
+    (one planted gradient is -1e12 / n beside -1 / n)."""
+    from cc_amd._lib import engine, STREAM
+    E = engine()
+    B, C = LOSSK_B, 4
+    check = "bce_planted" if planted else "bce_plain"
+    T = _RigidTerms(check, "lossk")
+    nan = lambda *s: torch.full(s, float("nan"), device=dev)
+    rows = []
+    for (H, W) in LOSSK_SHAPES:
+        mask = torch.sigmoid(torch.randn(B, C, H, W, generator=_lossk_gen("bce", H, W)))
+        n = mask.numel()
+        where = [(k * n) // len(BCE_PLANTED) for k in range(len(BCE_PLANTED))] if planted else []
+        for i, v in zip(where, BCE_PLANTED):
+            mask.view(-1)[i] = v
+        if planted:
+            assert float(mask.view(-1)[where[2]]) > 0 and float(mask.view(-1)[where[6]]) < 1        # (1e-45 and 1 - 2^-24 are fp32 values)
+        r32, r64 = _bce_ones_ref(mask, F32), _bce_ones_ref(mask, F64)
+        assert float(r64["terms"].min()) >= 0
+        rows.append(dict(H=H, W=W, n=n, mask=mask.to(dev), where=where, r32=r32, r64=r64))
+
+    def gmask_terms(form, d, gm):
+        rest = torch.ones(d["n"], dtype=torch.bool)
+        for i, v in zip(d["where"], BCE_PLANTED):
+            rest[i] = False
+            one = torch.zeros(d["n"], dtype=torch.bool)
+            one[i] = True
+            T.term("gmask_%s_planted_%.3g %dx%d" % (form, v, d["H"], d["W"]), gm, d["r32"]["g"], d["r64"]["g"], keep=one.view(gm.shape))
+        T.term("gmask_%s_ordinary %dx%d" % (form, d["H"], d["W"]), gm, d["r32"]["g"], d["r64"]["g"], keep=rest.view(gm.shape))
+
+    for d in rows:
+        tag = "%dx%d" % (d["H"], d["W"])
+        nbl = (d["n"] + 255) // 256
+        part, loss, gm = nan(nbl + 1), torch.zeros(1, device=dev), nan(B, C, d["H"], d["W"])
+        E.call("cc_bce_ones_fwd_bwd", d["mask"], gm, part, loss, LOSSK_GSCALE, d["n"], STREAM)
+        T.term("loss_single " + tag, loss, d["r32"]["loss"].reshape(1), d["r64"]["loss"].reshape(1), floor=(LOSSK_K["bce_ones"] + _k_reduce(nbl)) * 2.0 ** -24)
+        flat = lambda t: _piece_sums(t.reshape(1, 1, 1, -1)).reshape(-1)
+        T.term("partials_single " + tag, _guarded("partials " + tag, part), flat(d["r32"]["terms"]), flat(d["r64"]["terms"]), floor=LOSSK_K["bce_ones"] * 2.0 ** -24)
+        gmask_terms("single", d, gm)
+    offs = _offsets([B * C * ((d["H"] * d["W"] + 255) // 256) for d in rows])
+    part, loss = nan(offs[-1] + 1), torch.zeros(1, device=dev)
+    gm = [nan(B, C, d["H"], d["W"]) for d in rows]
+    _lossk_jobs("cc_bce_ones_fwd_bwd_jobs", [([d["mask"], gm[i], LF._off(part, offs[i])], d["H"], d["W"]) for i, d in enumerate(rows)],
+                B * C, part, loss, LOSSK_GSCALE, STREAM)
+    _guarded("jobs partials", part)
+    T.term("loss_jobs", loss, sum(d["r32"]["loss"] for d in rows).reshape(1), sum(d["r64"]["loss"] for d in rows).reshape(1),
+           floor=(LOSSK_K["bce_ones"] + _k_reduce(offs[-1])) * 2.0 ** -24)
+    for i, d in enumerate(rows):
+        T.term("partials_jobs %dx%d" % (d["H"], d["W"]), part[offs[i]:offs[i + 1]].view(B * C, -1), _piece_sums(d["r32"]["terms"]),
+               _piece_sums(d["r64"]["terms"]), floor=LOSSK_K["bce_ones"] * 2.0 ** -24)
+        gmask_terms("jobs", d, gm[i])
+    T.done()
+
+
+# ------------------------------------------------------------------ consensus BCE
+CONSENSUS_ARGS = tuple(tuple(float(np.float32(v)) for v in a) for a in ((0.5, 0.5), (0.01, 0.2), (0.01, 0.9)))      # thresh, wbce
+CONSENSUS_PLANTED = (0.0, 1.0, 1e-9, 1.0 - 2.0 ** -24)
+
+
+def _consensus_inputs(H, W, thresh):
+    """exp_mask = sigmoid(3 randn) with CONSENSUS_PLANTED (each twice), census values U(0, 2 thresh) with some planted exactly at
+    float32(thresh) where the other channel is 0 and the target 0 (the pixel's class hangs on the strict <), targets of mean 0.3
+    (bwd) and 0.7 (fwd)"""
+    B, HW = LOSSK_B, H * W
+    g = _lossk_gen("consensus", H, W)
+    e = torch.sigmoid(3 * torch.randn(B, 4, H, W, generator=g))
+    n = e.numel()
+    where = [((2 * k + 1) * n) // (4 * len(CONSENSUS_PLANTED)) for k in range(2 * len(CONSENSUS_PLANTED))]
+    for k, i in enumerate(where):
+        e.view(-1)[i] = CONSENSUS_PLANTED[k // 2]
+    cb, cf = (torch.rand(B, 2, H, W, generator=g) * (2 * thresh) for _ in range(2))
+    tb, tf = (torch.rand(B, 1, H, W, generator=g) < 0.3).float(), (torch.rand(B, 1, H, W, generator=g) < 0.7).float()
+    below = float(((cb < thresh).double().mean() + (cf < thresh).double().mean()) / 2)
+    ties = 0
+    for (c, t, b, p) in ((cb, tb, 0, 0), (cf, tf, B - 1, HW - 1)) + (((cb, tb, B - 1, HW // 2), (cf, tf, 0, HW // 2 + 1)) if HW > 16 else ()):
+        y, x = p // W, p % W
+        c[b, 0, y, x], c[b, 1, y, x], t[b, 0, y, x] = thresh, 0.0, 0.0
+        ties += 1
+    assert float((cb == thresh).sum() + (cf == thresh).sum()) == ties
+    return dict(H=H, W=W, e=e, where=where, cb=cb, cf=cf, tb=tb, tf=tf, below=below)
+
+
+def _consensus_ref(d, thresh, wbce, dt):
+    """L.consensus_depth_flow_mask of one level in dtype dt -> loss, d loss / d exp_mask * LOSSK_GSCALE, the per-pixel terms (summed
+    over the four channels), the target"""
+    e = _leaf_as(d["e"], dt)
+    cb, cf, tb, tf = (d[k].to(dt) for k in ("cb", "cf", "tb", "tf"))
+    loss = L.consensus_depth_flow_mask([e], [cb], [cf], [tb], [tf], thresh, wbce)
+    g = torch.autograd.grad(loss, e)[0] * LOSSK_GSCALE
+    with torch.no_grad():
+        b = L.logical_or((cb < thresh).type_as(e).prod(dim=1, keepdim=True), tb)
+        f = L.logical_or((cf < thresh).type_as(e).prod(dim=1, keepdim=True), tf)
+        t = torch.cat((b, b, f, f), dim=1)
+        terms = -((1 - wbce) * (t * torch.log(e + L.EPS)) + wbce * ((1 - t) * torch.log(1 - e + L.EPS))) / e.numel()
+    return dict(loss=loss.detach(), g=g, terms=terms.sum(1), terms4=terms, t=t)
+
+
+def check_consensus_bce_float64(dev, args=CONSENSUS_ARGS):
+    """cc_consensus_bce_fwd_bwd and cc_consensus_bce_fwd_bwd_jobs at LOSSK_SHAPES against L.consensus_depth_flow_mask in fp32 and
+    float64 for (thresh, wbce) in CONSENSUS_ARGS (wbce != 1 - wbce is the point): loss, partials, gmask under gscale = 0.7; the planted
+    exp_mask elements one by one, the ordinary ones as another term.  census and thresh are fp32 values on all sides, so `<` is the
+    same decision in every precision, also at the planted equalities; 25-75 % of the census values lie below thresh and both target
+    classes are present (asserted).  The terms are non-negative but for log(1 + 1e-8) where exp_mask is exactly 0 or 1: at least
+    -1e-8 / n each (asserted), nothing against a loss of order 1."""
+    from cc_amd._lib import engine, STREAM
+    E = engine()
+    B = LOSSK_B
+    nan = lambda *s: torch.full(s, float("nan"), device=dev)
+    T = _RigidTerms("consensus_bce", "lossk")
+    for thresh, wbce in args:
+        rows = []
+        for (H, W) in LOSSK_SHAPES:
+            d = _consensus_inputs(H, W, thresh)
+            d["r32"], d["r64"] = _consensus_ref(d, thresh, wbce, F32), _consensus_ref(d, thresh, wbce, F64)
+            assert float(d["r64"]["terms4"].min()) >= -1.0001e-8 / d["e"].numel(), (H, W, float(d["r64"]["terms4"].min()))
+            assert torch.equal(d["r32"]["t"].double(), d["r64"]["t"])
+            ones = float(d["r64"]["t"].mean())
+            print("consensus_bce %dx%d thresh=%.3g: %.3f of the census values below thresh, target share %.3f" % (H, W, thresh, d["below"], ones))
+            assert 0.25 <= d["below"] <= 0.75 and 0.2 <= ones <= 0.8, (H, W, d["below"], ones)
+            d["dev"] = [d[k].to(dev) for k in ("e", "cb", "cf", "tb", "tf")]
+            rows.append(d)
+
+        def gmask_terms(form, d, gm):
+            tag = "%dx%d thresh=%.3g wbce=%.3g" % (d["H"], d["W"], thresh, wbce)
+            n = d["e"].numel()
+            rest = torch.ones(n, dtype=torch.bool)
+            for k, i in enumerate(d["where"]):
+                rest[i] = False
+                one = torch.zeros(n, dtype=torch.bool)
+                one[i] = True
+                T.term("gmask_%s_planted_%.3g_%d %s" % (form, CONSENSUS_PLANTED[k // 2], k % 2, tag), gm, d["r32"]["g"], d["r64"]["g"], keep=one.view(gm.shape))
+            T.term("gmask_%s_ordinary %s" % (form, tag), gm, d["r32"]["g"], d["r64"]["g"], keep=rest.view(gm.shape))
+
+        kp = LOSSK_K["consensus_bce"]
+        for d in rows:
+            tag = "%dx%d thresh=%.3g wbce=%.3g" % (d["H"], d["W"], thresh, wbce)
+            nb = (d["H"] * d["W"] + 255) // 256
+            part, loss, gm = nan(B * nb + 1), torch.zeros(1, device=dev), nan(B, 4, d["H"], d["W"])
+            E.call("cc_consensus_bce_fwd_bwd", *d["dev"], gm, part, loss, thresh, wbce, LOSSK_GSCALE, B, d["H"], d["W"], STREAM)
+            T.term("loss_single " + tag, loss, d["r32"]["loss"].reshape(1), d["r64"]["loss"].reshape(1), floor=(kp + _k_reduce(B * nb)) * 2.0 ** -24)
+            T.term("partials_single " + tag, _guarded("partials " + tag, part).view(B, nb), _piece_sums(d["r32"]["terms"]), _piece_sums(d["r64"]["terms"]),
+                   floor=kp * 2.0 ** -24)
+            gmask_terms("single", d, gm)
+        offs = _offsets([B * ((d["H"] * d["W"] + 255) // 256) for d in rows])
+        part, loss = nan(offs[-1] + 1), torch.zeros(1, device=dev)
+        gm = [nan(B, 4, d["H"], d["W"]) for d in rows]
+        _lossk_jobs("cc_consensus_bce_fwd_bwd_jobs", [(d["dev"] + [gm[i], LF._off(part, offs[i])], d["H"], d["W"]) for i, d in enumerate(rows)],
+                    B, part, loss, thresh, wbce, LOSSK_GSCALE, STREAM)
+        _guarded("jobs partials", part)
+        tag = "thresh=%.3g wbce=%.3g" % (thresh, wbce)
+        T.term("loss_jobs " + tag, loss, sum(d["r32"]["loss"] for d in rows).reshape(1), sum(d["r64"]["loss"] for d in rows).reshape(1),
+               floor=(kp + _k_reduce(offs[-1])) * 2.0 ** -24)
+        for i, d in enumerate(rows):
+            T.term("partials_jobs %dx%d %s" % (d["H"], d["W"], tag), part[offs[i]:offs[i + 1]].view(B, -1), _piece_sums(d["r32"]["terms"]),
+                   _piece_sums(d["r64"]["terms"]), floor=kp * 2.0 ** -24)
+            gmask_terms("jobs", d, gm[i])
+    T.done()
+
+
+# ------------------------------------------------------------------ decisions: occlusion masks, consensus target
+def _pinned_decision(tag, outs, dec32, dec64, lhs, rhs):
+    """outs: {form: device result}.  Every result (and the fp32 oracle's) equals the float64 decision dec64 wherever float64's margin
+    |lhs - rhs| / max(|lhs|, |rhs|) exceeds LOSSK_DELTA; at most RIGID_MAX_EXCLUDED inside it, 20-80 % ones."""
+    margin = (lhs - rhs).abs() / torch.maximum(lhs.abs(), rhs.abs()).clamp_min(1e-300)
+    keep = (margin > LOSSK_DELTA).reshape(dec64.shape) if margin.shape != dec64.shape else margin > LOSSK_DELTA
+    excl, ones = float((~keep).double().mean()), float(dec64.mean())
+    _note("lossk:decisions:excluded_share", excl)
+    print("%-64s excluded %.4f, share of ones %.3f" % (tag, excl, ones))
+    assert excl <= RIGID_MAX_EXCLUDED and 0.2 <= ones <= 0.8, (tag, excl, ones)
+    assert torch.equal(dec32.double()[keep], dec64[keep]), (tag, "the fp32 oracle")
+    for form, o in outs.items():
+        o = o.detach().cpu().double()
+        assert o.shape == dec64.shape and not bool(torch.isnan(o).any()), (tag, form)
+        assert torch.equal(o[keep], dec64[keep]), (tag, form, "%d decisions differ from float64's" % int((o[keep] != dec64[keep]).sum()))
+
+
+def _noocc_ref(bw, fw, dt):
+    """1 - L.occlusion_masks in dtype dt [B,1,H,W], and the two sides of its comparison"""
+    bw, fw = bw.to(dt), fw.to(dt)
+    occ_bw, occ_fw = L.occlusion_masks(bw, fw)
+    assert torch.equal(occ_bw, occ_fw)
+    return (1 - occ_bw).unsqueeze(1), (fw + bw).sum(dim=1, keepdim=True), (0.08 * (fw.pow(2).sum(dim=1, keepdim=True) + bw.pow(2).sum(dim=1, keepdim=True)) + 1.0)
+
+
+def check_decisions_float64(dev):
+    """cc_flow_noocc and cc_flow_noocc_jobs, cc_rigid_noocc, cc_consensus_target and cc_consensus_target_jobs (wrig = 0.7) at
+    LOSSK_SHAPES against L.occlusion_masks and the comparison of L.consensus_exp_masks in float64 (_pinned_decision).  Flows 1.5 randn
+    + 0.5: about half of the pixels are occluded."""
+    from cc_amd._lib import engine, STREAM
+    E = engine()
+    B = LOSSK_B
+    wrig = float(np.float32(0.7))
+    nan = lambda *s: torch.full(s, float("nan"), device=dev)
+    rows = []
+    for (H, W) in LOSSK_SHAPES:
+        g = _lossk_gen("decisions", H, W)
+        d = dict(H=H, W=W, flows=torch.randn(4, B, 2, H, W, generator=g) * 1.5 + 0.5,
+                 err_cf=torch.rand(B, 1, H, W, generator=g), err_cb=torch.rand(B, 1, H, W, generator=g), err_ff=torch.rand(B, 1, H, W, generator=g) * 0.5,
+                 v_cf=(torch.rand(B, 1, H, W, generator=g) < 0.5).float(), v_cb=(torch.rand(B, 1, H, W, generator=g) < 0.5).float())
+        d["dev"] = {k: v.to(dev) for k, v in d.items() if torch.is_tensor(v)}
+        d["out"] = dict(noocc_jobs=nan(B * H * W + 1), target_jobs=nan(B * H * W + 1))
+        rows.append(d)
+    _lossk_jobs("cc_flow_noocc_jobs", [([d["dev"]["flows"][0], d["dev"]["flows"][1], d["out"]["noocc_jobs"]], d["H"], d["W"]) for d in rows], B, STREAM)
+    _lossk_jobs("cc_consensus_target_jobs", [([d["dev"][k] for k in ("err_cf", "err_cb", "err_ff", "v_cf", "v_cb")] + [d["out"]["target_jobs"]], d["H"], d["W"])
+                                             for d in rows], B, wrig, STREAM)
+    for d in rows:
+        H, W, v = d["H"], d["W"], d["dev"]
+        tag = "%dx%d" % (H, W)
+        # occlusion_masks(flow_bw, flow_fw) of flows 0 and 1
+        single = nan(B * H * W + 1)
+        E.call("cc_flow_noocc", v["flows"][0], v["flows"][1], single, B, H, W, STREAM)
+        outs = {k: _guarded(k + " " + tag, t).view(B, 1, H, W) for k, t in (("single", single), ("jobs", d["out"]["noocc_jobs"]))}
+        r32, r64 = _noocc_ref(d["flows"][0], d["flows"][1], F32), _noocc_ref(d["flows"][0], d["flows"][1], F64)
+        _pinned_decision("flow_noocc " + tag, outs, r32[0], r64[0], r64[1], r64[2])
+        # depth_occlusion_masks' pairing of four flows: (m03, m12, m12, m03)
+        out4 = nan(B * 4 * H * W + 1)
+        E.call("cc_rigid_noocc", v["flows"], out4, B, H, W, STREAM)
+        ref = {}
+        for dt in (F32, F64):
+            m12, m03 = _noocc_ref(d["flows"][1], d["flows"][2], dt), _noocc_ref(d["flows"][0], d["flows"][3], dt)
+            ref[dt] = [torch.cat([m[k] for m in (m03, m12, m12, m03)], 1) for k in range(3)]
+        _pinned_decision("rigid_noocc " + tag, dict(single=_guarded("rigid_noocc " + tag, out4).view(B, 4, H, W)), ref[F32][0], ref[F64][0], ref[F64][1], ref[F64][2])
+        # the consensus target
+        single = nan(B * H * W + 1)
+        E.call("cc_consensus_target", v["err_cf"], v["err_cb"], v["err_ff"], v["v_cf"], v["v_cb"], single, wrig, B * H * W, STREAM)
+        outs = {k: _guarded(k + " " + tag, t).view(B, 1, H, W) for k, t in (("single", single), ("jobs", d["out"]["target_jobs"]))}
+        ref = {}
+        for dt in (F32, F64):
+            cam_err = torch.min(d["err_cf"].to(dt), d["err_cb"].to(dt)) * L.logical_or(d["v_cf"].to(dt), d["v_cb"].to(dt))
+            lhs, rhs = wrig * cam_err, d["err_ff"].to(dt) + L.EPS
+            ref[dt] = ((lhs <= rhs).to(dt), lhs, rhs)
+        _pinned_decision("consensus_target " + tag, outs, ref[F32][0], ref[F64][0], ref[F64][1], ref[F64][2])
+
+
+# ------------------------------------------------------------------ k_reduce_add
+REDUCE_NS = (1, 255, 256, 2048, 2049, 5000, 20000)         # one work-item's eight loads cover 2048 partials; 20000 > 8 * 2048
+
+
+def check_reduce_add_float64(dev):
+    """cc_reduce_add: accum (0.5 before the call) += coef * sum(partials[0..n)) with coef = float32(0.3), non-negative partials,
+    against float64 under the floor of the sums (k = _k_reduce(n) + 1 for the product); the NaN behind partials[n - 1] is not read."""
+    from cc_amd._lib import engine, STREAM
+    E = engine()
+    T = _RigidTerms("reduce_add", "lossk")
+    coef, acc0 = float(np.float32(0.3)), 0.5
+    for n in REDUCE_NS:
+        part = torch.full((n + 300,), float("nan"))
+        part[:n] = torch.rand(n, generator=torch.Generator().manual_seed(n))
+        acc = torch.full((1,), acc0, device=dev)
+        E.call("cc_reduce_add", part.to(dev), n, coef, acc, STREAM)
+        assert bool(torch.isfinite(acc).all()), (n, "read behind partials[n - 1]")
+        r32 = torch.full((1,), acc0) + torch.tensor(coef) * part[:n].sum()
+        r64 = acc0 + coef * part[:n].double().sum()
+        T.term("accum n=%d" % n, acc, r32, r64.reshape(1), floor=(_k_reduce(n) + 1) * 2.0 ** -24)
+    T.done()
+
+
+# ------------------------------------------------------------------ element-wise jobs
+def check_elementwise_jobs_float64(dev):
+    """cc_elementwise_jobs, two rows (8x26, 20x53) per launch: ops 0 (1 / a), 1 (-g y^2) and 5 (ImageNet normalisation) against
+    float64 under the per-pixel bar; ops 2 (|a - b|), 3 (1 - m[:, c0:c0 + nc]) and 4 (its backward: exactly 0 outside the slice, over
+    a sentinel-filled output; c0 = 1, nc = 2, MC = 4) exactly."""
+    from cc_amd._lib import STREAM
+    B = LOSSK_B
+    T = _RigidTerms("elementwise", "lossk")
+    hw = LOSSK_SHAPES[:2]
+    g = torch.Generator().manual_seed(17)
+
+    def run(op, planes, ins, out_planes, c0=0, nc=0, MC=0, fill=float("nan")):
+        """ins: per input a list with one tensor per row -> the rows' outputs [out_planes, H, W]"""
+        outs = [torch.full((out_planes * H * W + 1,), fill, device=dev) for H, W in hw]
+        _lossk_jobs("cc_elementwise_jobs", [([t[i].to(dev) for t in ins] + [outs[i]], H, W) for i, (H, W) in enumerate(hw)], planes, op, c0, nc, MC, STREAM)
+        res = []
+        for o, (H, W) in zip(outs, hw):
+            assert float(o[-1]) != float(o[-1]) or float(o[-1]) == fill, "a write behind the documented extent"
+            assert not bool(torch.isnan(o[:-1]).any()) and (fill != fill or not bool((o[:-1] == fill).any())), "an element was not written"
+            res.append(o[:-1].view(out_planes, H, W).cpu())
+        return res
+
+    P = B * 3
+    a = [torch.rand(P, H, W, generator=g) + 0.25 for H, W in hw]
+    gr = [torch.randn(P, H, W, generator=g) for H, W in hw]
+    y = run(0, P, [a], P)
+    ga = run(1, P, [gr, y], P)
+    im = [torch.rand(P, H, W, generator=g) * 2 - 1 for H, W in hw]
+    nrm = run(5, P, [im], P)
+    for i, (H, W) in enumerate(hw):
+        tag = "%dx%d" % (H, W)
+        T.term("op0 " + tag, y[i], 1.0 / a[i], 1.0 / a[i].double())
+        T.term("op1 " + tag, ga[i], -gr[i] * (y[i] * y[i]), -gr[i].double() * (y[i].double() * y[i].double()))
+        stat = lambda dt: [torch.tensor(s, dtype=dt).repeat(B).view(P, 1, 1) for s in ((0.485, 0.456, 0.406), (0.229, 0.224, 0.225))]
+        ref = {dt: ((im[i].to(dt) * 0.5 + 0.5) - stat(dt)[0]) / stat(dt)[1] for dt in (F32, F64)}
+        T.term("op5 " + tag, nrm[i], ref[F32], ref[F64])
+    b_ = [torch.rand(P, H, W, generator=g) for H, W in hw]
+    for i, o in enumerate(run(2, P, [a, b_], P)):
+        assert torch.equal(o, (a[i] - b_[i]).abs()), ("op 2", i)
+    c0, nc, MC = 1, 2, 4
+    m = [torch.rand(B, MC, H, W, generator=g) for H, W in hw]
+    for i, o in enumerate(run(3, B * nc, [m], B * nc, c0, nc, MC)):
+        assert torch.equal(o.view(B, nc, *hw[i]), 1.0 - m[i][:, c0:c0 + nc]), ("op 3", i)
+    gs = [torch.randn(B, nc, H, W, generator=g) for H, W in hw]
+    for i, o in enumerate(run(4, B * MC, [gs], B * MC, c0, nc, MC, fill=-77.0)):
+        o = o.view(B, MC, *hw[i])
+        assert torch.equal(o[:, c0:c0 + nc], -gs[i]), ("op 4: the slice", i)
+        assert bool((o[:, :c0] == 0).all()) and bool((o[:, c0 + nc:] == 0).all()), ("op 4: not exactly 0 outside the slice", i)
+    T.done()
+
+
+# ------------------------------------------------------------------ the pyramid's fallbacks
+def check_pyramid_fallbacks_float64(dev):
+    """cc_pyramid_build where the one-launch tile kernel does not apply: 48x80 (not a multiple of 32: one k_adaptive_pool launch per
+    level) and 64x96 from a pointer 4 bytes behind a 16-byte boundary (the alignment fallback; the aligned call beside it).  Every
+    level is torch.equal to cc_adaptive_avg_pool of that level and held to F.adaptive_avg_pool2d in float64 under the per-pixel bar."""
+    import torch.nn.functional as F
+    from cc_amd._lib import engine, STREAM
+    E = engine()
+    T = _RigidTerms("pyramid", "lossk")
+    B, nlevels = LOSSK_B, 6
+    for (H, W, off) in ((48, 80, 0), (64, 96, 1), (64, 96, 0)):
+        x = syn.frames(B, H, W, seed=11, n_frames=1)[0]
+        xd = _at_offset(x.to(dev), off)
+        sizes = [(H >> l, W >> l) for l in range(1, nlevels)]
+        packed = torch.full((sum(B * 3 * h * w for h, w in sizes) + 1,), float("nan"), device=dev)
+        E.call("cc_pyramid_build", xd, packed, nlevels, B * 3, H, W, STREAM)
+        body, o = _guarded("pyramid %dx%d" % (H, W), packed), 0
+        for (h, w) in sizes:
+            tag = "%dx%d+%d -> %dx%d" % (H, W, off, h, w)
+            lv = body[o:o + B * 3 * h * w].view(B, 3, h, w)
+            o += B * 3 * h * w
+            pool = torch.full((B, 3, h, w), float("nan"), device=dev)
+            E.call("cc_adaptive_avg_pool", xd, pool, B * 3, H, W, h, w, STREAM)
+            assert torch.equal(lv, pool), (tag, "differs from cc_adaptive_avg_pool")
+            T.term("level " + tag, lv, F.adaptive_avg_pool2d(x, (h, w)), F.adaptive_avg_pool2d(x.double(), (h, w)))
+    T.done()

@@ -288,6 +288,43 @@ def test_ssim_nan_flag_on_real_input():
     parity.check_ssim_nan_flag("cpu")
 
 
+# the smoothness, BCE and consensus kernels, the occlusion masks, the element-wise jobs, k_reduce_add and the pyramid against the
+# oracle in float64, per entry point (bars: parity.RIGID_MARGIN, parity.LOSSK_K, parity.LOSSK_DELTA)
+@pytest.mark.parametrize("planted", [True, False], ids=["ties", "random"])
+def test_edge_smooth_float64(planted):
+    parity.check_edge_smooth_float64("cpu", planted)
+
+
+def test_smooth2_float64():
+    parity.check_smooth2_float64("cpu")
+
+
+@pytest.mark.parametrize("planted", [True, False], ids=["planted", "plain"])
+def test_bce_ones_float64(planted):
+    parity.check_bce_ones_float64("cpu", planted)
+
+
+@pytest.mark.parametrize("args", parity.CONSENSUS_ARGS, ids=lambda a: "thresh%.3g-wbce%.3g" % a)
+def test_consensus_bce_float64(args):
+    parity.check_consensus_bce_float64("cpu", (args,))
+
+
+def test_occlusion_masks_and_consensus_target_match_float64_decisions():
+    parity.check_decisions_float64("cpu")
+
+
+def test_reduce_add_float64():
+    parity.check_reduce_add_float64("cpu")
+
+
+def test_elementwise_jobs_float64():
+    parity.check_elementwise_jobs_float64("cpu")
+
+
+def test_pyramid_fallbacks_float64():
+    parity.check_pyramid_fallbacks_float64("cpu")
+
+
 def test_bias_gradient_table():
     parity.check_bias_grad_table("cpu")
 
