@@ -63,6 +63,7 @@ class _Debug:
     pipe_extra = {}              # measurement: {network name: extra 256 MB fills (~50 us each) in its tail} -- how much slack has its stream?
     pipe_skip_tail = ()          # per-network pipeline, measurement only: names of the networks whose Adam segment + weight-image refresh are skipped
     reduce_trace = None          # a list: every weight-gradient reduce descriptor of the step is appended to it (tools/reduce_bytes.py)
+    corr_patch_gather = False    # ops.correlate_patch on the gather kernels (cc_corr_patch_*) where the plane-GEMM kernels would run
     library_path = None          # another build of libccengine.so (the tools build): picked up by _lib.engine() on first use
 
 

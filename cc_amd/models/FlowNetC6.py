@@ -61,6 +61,24 @@ class FlowNetC6(nn.Module):
         c2a = self.conv2(c1a)
         c3a = self.conv3(c2a)
         c3b = self.conv3(self.conv2(self.conv1(x2)))
+        return self._decode(c1a, c2a, c3a, c3b)
+
+    def forward_pair(self, tgt, refs):
+        """(self(tgt, refs[0]), self(tgt, refs[1])) -- train.py:465-466's two calls, flow_fwd then flow_bwd -- in ONE pass over the
+        two pairs stacked along the batch (rows [0, B): (tgt, refs[0]); [B, 2B): (tgt, refs[1])).  The network has no BatchNorm, so
+        every sample is computed exactly as in a call of its own; the target's encoder runs once and its features are shared."""
+        ref_fwd, ref_bwd = refs
+        B = tgt.shape[0]
+        c1a = self.conv1(tgt)
+        c2a = self.conv2(c1a)
+        c3a = self.conv3(c2a)
+        c3b = self.conv3(self.conv2(self.conv1(torch.cat((ref_fwd, ref_bwd), 0))))
+        out = self._decode(torch.cat((c1a, c1a), 0), torch.cat((c2a, c2a), 0), torch.cat((c3a, c3a), 0), c3b)
+        if self.training:
+            return tuple(o[:B] for o in out), tuple(o[B:] for o in out)
+        return out[:B], out[B:]
+
+    def _decode(self, c1a, c2a, c3a, c3b):
         corr = F.leaky_relu(self.corr(c3a, c3b), _S)                        # corr_activation
         c31 = self.conv3_1(torch.cat((self.conv_redir(c3a), corr), 1))
         c4 = self.conv4_1(self.conv4(c31))

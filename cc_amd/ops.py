@@ -973,13 +973,22 @@ class _CorrFn(torch.autograd.Function):
         return ga, gb
 
 
+def _corr_plane_ok(B, C, H, W, patch, dilation):
+    """The predicate of cc_corr_plane_{fwd,bwd} (corr_plane.hip: the residue planes of the dilated volume as GEMMs on the fp32 matrix
+    cores): FlowNetC6's 21 x 21 / dilation-2 volume on a map with even sides -- every frame whose sides are multiples of 16.  Every
+    other shape, and every shape under config.debug.corr_patch_gather, takes the gather kernels cc_corr_patch_{fwd,bwd}."""
+    return (not _dbg.corr_patch_gather and patch == 21 and dilation == 2 and H % 2 == 0 and W % 2 == 0
+            and 1 <= B <= 65535 and C >= 1 and H >= 2 and W >= 2)
+
+
 class _CorrPatchFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, a, b, patch, dilation):
         a, b = _c(a), _c(b)
         B, C, H, W = a.shape
         out = torch.empty(B, patch * patch, H, W, device=a.device, dtype=torch.float32)
-        engine().call("cc_corr_patch_fwd", a, b, out, B, C, H, W, patch, dilation, STREAM)
+        plane = _corr_plane_ok(B, C, H, W, patch, dilation)
+        engine().call("cc_corr_plane_fwd" if plane else "cc_corr_patch_fwd", a, b, out, B, C, H, W, patch, dilation, STREAM)
         ctx.save_for_backward(a, b)
         ctx.geom = (patch, dilation)
         return out
@@ -990,7 +999,9 @@ class _CorrPatchFn(torch.autograd.Function):
         B, C, H, W = a.shape
         ga = torch.empty_like(a) if ctx.needs_input_grad[0] else None
         gb = torch.empty_like(b) if ctx.needs_input_grad[1] else None
-        engine().call("cc_corr_patch_bwd", _c(g), a, b, ga, gb, B, C, H, W, ctx.geom[0], ctx.geom[1], STREAM)
+        plane = _corr_plane_ok(B, C, H, W, *ctx.geom)
+        engine().call("cc_corr_plane_bwd" if plane else "cc_corr_patch_bwd", _c(g), a, b, ga, gb, B, C, H, W, ctx.geom[0],
+                      ctx.geom[1], STREAM)
         return ga, gb, None, None
 
 

@@ -19,6 +19,7 @@ import collections
 import collections.abc
 import contextlib
 import ctypes
+import gc
 
 import torch
 import torch.distributed as dist
@@ -54,12 +55,14 @@ class StepConfig:
             setattr(self, k, v)
 
 
-def build_nets(device, flow=True, mask=True, init=True):
-    """disp, pose, mask, flow in the order train.py:245-255 creates (and :262-284 initialises) them."""
+def build_nets(device, flow=True, mask=True, init=True, flownet="Back2Future"):
+    """disp, pose, mask, flow in the order train.py:245-255 creates (and :262-284 initialises) them.
+    flownet: "Back2Future" (default) or "FlowNetC6" (train.py:90's --flownet; cc_forward makes its two-frame calls)."""
+    assert flownet in ("Back2Future", "FlowNetC6"), flownet
     disp = models.DispResNet6()
     pose = models.PoseNetB6(nb_ref_imgs=4)
     msk = models.MaskNet6(nb_ref_imgs=4, output_exp=True) if mask else None
-    flo = models.Back2Future(nlevels=6) if flow else None
+    flo = getattr(models, flownet)(nlevels=6) if flow else None
     nets = [disp, pose, msk, flo]
     for n in nets:
         if n is not None:
@@ -145,7 +148,12 @@ def cc_forward(nets, batch, cfg, keep=False, cut=None, streams=None, after_fork=
     # runs ready nodes latest-created first, so the backward passes are ENQUEUED pose, mask, disp, flow: shortest first, which is the
     # order the per-network pipeline issues the networks' gradient exchanges in -- one RCCL communicator executes its collectives in
     # issue order, and Back2Future, the longest backward, must not hold up DispResNet6's segment)
-    flow_out = _on(s_flow, lambda: flow_net(tgt, refs[1:3])) if full else None         # :463
+    if full and hasattr(flow_net, "forward_pair"):
+        # a two-frame flow network (FlowNetC6): train.py:465-466's  flow_fwd = flow_net(tgt, refs[2]); flow_bwd = flow_net(tgt, refs[1])
+        # as one pass over both pairs; no occlusion output
+        flow_out = _on(s_flow, lambda: tuple(flow_net.forward_pair(tgt, [refs[2], refs[1]])) + (None,))
+    else:
+        flow_out = _on(s_flow, lambda: flow_net(tgt, refs[1:3])) if full else None     # :463
     disp_out = _on(s_disp, lambda: _levels(disp_net(tgt)))                                # :454
     # (behind the side streams' launches, on the step's stream: nothing of it is needed before the losses / the backward pass, and
     # in front of the forks it would hold up DispResNet6, whose chain is the step's critical path)
@@ -802,6 +810,11 @@ class CCTrainer:
         if pipeline is None:
             pipeline = "per_network" if split_graphs is None else ("staged" if split_graphs else "post")
         assert pipeline in ("per_network", "post", "staged"), pipeline
+        if pipeline != "per_network" and nets[3] is not None and hasattr(nets[3], "forward_pair"):
+            raise ValueError("pipeline=%r with a two-frame flow network (%s): the legacy step forms cut the backward pass into the "
+                             "[DispResNet6 | PoseNetB6] and [MaskNet6 | Back2Future] stages of the taped networks and are kept for "
+                             "measurements against them only; a network that is not on the tape trains in the default "
+                             "'per_network' pipeline" % (pipeline, type(nets[3]).__name__))
         if getattr(cfg, "max_grad_norm", None) is not None:
             self._no_chunks_with_guard(pipeline == "per_network" and bool(config.grad_chunks))
         for n in nets:
@@ -1213,21 +1226,34 @@ class CCTrainer:
         # polling its events must not invalidate the capture
         mode = config.debug.capture_mode
         self.graph = torch.cuda.CUDAGraph()
-        if self.split_graphs:
-            # two graphs sharing one memory pool: the collective of the first gradient segment is issued between them
-            self.graph_b = torch.cuda.CUDAGraph()
-            ok = False
-            try:
+        # Python's cycle collector must not run inside the capture region.  A dead trainer of this process that sits in a reference
+        # cycle still owns its hipGraph and the graph's private memory pool; when the collector finds it, the pool is released with
+        # hipFree on the capturing thread, which the runtime refuses during a capture -- from a destructor, so the process aborts
+        # (seen as "Fatal Python error: Aborted ... Garbage-collecting" in the middle of a captured step, in processes that had
+        # captured other trainers before).  torch.cuda.graph collects on entry only with torch.compiler.config.force_cudagraph_gc:
+        # collect what is dead now, and keep the automatic collector off until the capture has ended.
+        gc.collect()
+        gc_was_on = gc.isenabled()
+        gc.disable()
+        try:
+            if self.split_graphs:
+                # two graphs sharing one memory pool: the collective of the first gradient segment is issued between them
+                self.graph_b = torch.cuda.CUDAGraph()
+                ok = False
+                try:
+                    with torch.cuda.graph(self.graph, stream=s, capture_error_mode=mode):
+                        self.losses, mf = self._stage_a(self.static_batch)
+                    with torch.cuda.graph(self.graph_b, pool=self.graph.pool(), stream=s, capture_error_mode=mode):
+                        self._stage_b(mf)
+                    ok = True
+                finally:
+                    self._stage_end(failed=not ok)
+            else:
                 with torch.cuda.graph(self.graph, stream=s, capture_error_mode=mode):
-                    self.losses, mf = self._stage_a(self.static_batch)
-                with torch.cuda.graph(self.graph_b, pool=self.graph.pool(), stream=s, capture_error_mode=mode):
-                    self._stage_b(mf)
-                ok = True
-            finally:
-                self._stage_end(failed=not ok)
-        else:
-            with torch.cuda.graph(self.graph, stream=s, capture_error_mode=mode):
-                self.losses = self._step_pipelined(self.static_batch) if pipelined else self._fwd_bwd(self.static_batch)
+                    self.losses = self._step_pipelined(self.static_batch) if pipelined else self._fwd_bwd(self.static_batch)
+        finally:
+            if gc_was_on:
+                gc.enable()
         # the NaN flags of the captured step live in the graph's private pool and are rewritten by every replay: keep them
         # as persistent handles (the reference asserts on NaN at every step, loss_functions.py:60,105,115)
         self.nan_flags = LF.take_nan_flags()

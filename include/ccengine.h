@@ -210,6 +210,13 @@ int cc_corr_patch_fwd(const float* f1, const float* f2, float* out, int B, int C
                       void* stream);
 int cc_corr_patch_bwd(const float* gout, const float* f1, const float* f2, float* g1_or_null, float* g2_or_null, int B, int C,
                       int H, int W, int patch, int dilation, void* stream);
+/* The same two operations as plane GEMMs on the fp32 matrix cores (corr_plane.hip): same arguments, same results bit for bit,
+ * out fully written.  Their predicate: patch == 21, dilation == 2, H and W even, 1 <= B <= 65535, any C >= 1.  For every other
+ * shape the two entries return CC_ERR_ARG -- those stay with cc_corr_patch_{fwd,bwd} (ops.correlate_patch chooses). */
+int cc_corr_plane_fwd(const float* f1, const float* f2, float* out, int B, int C, int H, int W, int patch, int dilation,
+                      void* stream);
+int cc_corr_plane_bwd(const float* gout, const float* f1, const float* f2, float* g1_or_null, float* g2_or_null, int B, int C,
+                      int H, int W, int patch, int dilation, void* stream);
 
 /* ---------------------------------------------------------------- convolutions (nn.Conv2d / nn.ConvTranspose2d of models/ *.py)
  * fp32 implicit GEMM on v_mfma_f32_32x32x2_f32.  act: 0 none, 1 ReLU, 2 LeakyReLU(0.2), 3 act_a*sigmoid+act_b.
