@@ -150,7 +150,7 @@ def take_nan_flags():
     return out
 
 
-step_nan_flags = None     # a list while a CCTrainer step with the ledger on runs: the flags that step registers (cc_amd/ledger.py)
+step_nan_flags = None     # a list while a step with the ledger on runs (step_scope.StepScope): the flags it registers (cc_amd/ledger.py)
 
 
 def _register_nan_flag(flag):
@@ -239,13 +239,7 @@ class _PyramidCache:
         H, W = img.shape[2], img.shape[3]
         if (h, w) == (H, W):
             return _f32c(img)
-        key = id(img)
-        ent = self.items.get(key)
-        if ent is None or ent[0] is not img or ent[1] != img._version:
-            ent = (img, img._version, {})
-            self.items[key] = ent
-            while len(self.items) > self.cap:
-                self.items.pop(next(iter(self.items)))
+        ent = self._entry(img)
         lv = ent[2].get((h, w))
         if lv is None:
             src = _f32c(img.detach())
@@ -273,7 +267,7 @@ pyramid_cache = _PyramidCache()
 class _HeadGrads:
     """Per-step gradient accumulators of the network outputs the loss terms share (train.py:509,567: a disparity / flow / mask
     level feeds two to four loss terms and the autograd engine adds their gradients pairwise -- ~44 launches per step).  While
-    the trainer has this active (CCTrainer._stage_a: ONE backward pass per forward pass), every fused loss scales its stashed
+    a step has this active (step_scope.StepScope.loss_phase: ONE backward pass per forward pass), every fused loss scales its stashed
     gradients straight INTO the tensor's accumulator (cc_scale_acc_jobs: first writer =, later writers +=, in the engine's own
     execution order); the term that registered the tensor first hands the accumulator to autograd, the others return None.  The
     engine runs a tensor's consumer only after every term that has an edge to it has executed, so the sum is complete by then.
@@ -303,7 +297,7 @@ class _HeadGrads:
 head_grads = _HeadGrads()
 
 # The stream the fused loss terms below issue their FORWARD launches on (None: the current one).  Set by cc_amd.trainer.cc_forward
-# around the calls it wants beside -- not behind -- the rigid photometric loss (warps, SSIM, adjoints: a fused term computes its
+# (through step_scope.forward_stream) around the calls it wants beside -- not behind -- the rigid photometric loss (warps, SSIM, adjoints: a fused term computes its
 # gradients in the forward call).  The switch sits INSIDE forward on purpose: the call returns on the caller's stream, so autograd binds
 # the node -- and with it the backward call, which adds into the step's shared gradient accumulators (_HeadGrads) in the engine's
 # execution order -- to the caller's stream; a `with torch.cuda.stream(..)` AROUND the call would move the backward call to the side

@@ -262,6 +262,13 @@ class PackRegistry:
             if e:
                 e["ok"] = False
 
+    def rebuild(self):
+        """every image again with one launch, outside a step: the weights were restored or edited and the next (captured) step of
+        the per-network pipeline starts from its images without a refresh of its own"""
+        self.mark_stale()
+        self.prepack_all()
+        self.end_step()
+
     def end_step(self):
         """per-network pipeline: the images stay (they match the updated weights); conv calls outside a step repack for themselves"""
         self.valid = False

@@ -84,9 +84,10 @@ class BnCounters:
 
 BN_COUNTERS = None
 
-# Set by CCTrainer for the duration of a pipelined step: called with the network module at the END of that network's backward
-# pass (inside its autograd node, i.e. on the network's stream, behind its last gradient launch) -- the trainer then runs the
-# network's gradient exchange, Adam segment and weight-image refresh right there instead of behind the whole backward pass.
+# Set by CCTrainer (step_scope.StepScope.network_hooks) around the backward call of a pipelined step: called with the network
+# module at the END of that network's backward pass (inside its autograd node, i.e. on the network's stream, behind its last
+# gradient launch) -- the trainer then runs the network's gradient exchange, Adam segment and weight-image refresh right there
+# instead of behind the whole backward pass.
 NET_DONE = None
 # ... and with (module, tag) when the backward pass comes back to a point the network's forward marked (Tape.mark): every parameter
 # used AFTER that point has its complete gradient (parked weight-gradient launches aside: the callee flushes them), so the trainer

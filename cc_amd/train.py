@@ -346,34 +346,6 @@ def build_networks(args, dev):
     return [disp_net, pose_net, mask_net, flow_net]
 
 
-def drop_trainer(tr, nets, dev):
-    """a phase boundary: the trainer with its graph goes, and nothing of it stays on the device -- the captured graph is reset (its
-    private pool with it), every parameter moves back to a storage of its own and loses its gradient (the views into the flat
-    buckets would keep both buckets alive), the weight images registered against the buckets are forgotten"""
-    import torch
-    from . import ops
-    if dev.type == "cuda":
-        torch.cuda.synchronize()
-    for name in ("graph", "graph_b"):
-        g = getattr(tr, name, None)
-        if g is not None:
-            g.reset()
-        setattr(tr, name, None)
-    tr.static_batch = tr.losses = None
-    tr.nan_flags = []
-    # (torch keeps one BLAS workspace per (handle, stream) for the life of the process -- 128 MB each on this stack, taken by the
-    # step's one torch.dot (LF.weighted_total) on every trainer's capture stream, out of the captured graph's pool; no graph is
-    # alive at this point, so they can all go)
-    clear = getattr(torch._C, "_cuda_clearCublasWorkspaces", None)
-    if dev.type == "cuda" and clear is not None:
-        clear()
-    for n in nets:
-        for q in n.parameters():
-            q.data = q.data.clone()
-            q.grad = None
-    ops.packs.reset()
-
-
 def make_trainer(args, nets, trained, dev):
     """requires_grad for the phase's set BEFORE the trainer exists (a network is frozen for good by it), then the trainer in its
     default form: captured on a HIP device, eager on the emulation"""
@@ -475,10 +447,9 @@ def main(argv=None, world_size=None):
         if end <= start:
             continue
         # ---- a phase: its own trainer, loader and decisive error
-        if tr is not None:
-            old, tr = tr, None
-            drop_trainer(old, nets, dev)
-            del old
+        if tr is not None:                      # a phase boundary: the trainer with its graph goes, nothing of it stays on the device
+            tr.close()
+            tr = None
             gc.collect()
             if dev.type == "cuda":
                 torch.cuda.empty_cache()

@@ -24,7 +24,7 @@ import gc
 import torch
 import torch.distributed as dist
 
-from . import config, models, ops, tape
+from . import config, models, ops, step_scope, tape
 from . import loss_functions as LF
 from ._lib import engine, header_constant, STREAM
 from .inverse_warp import pose2flow
@@ -211,8 +211,7 @@ def cc_forward(nets, batch, cfg, keep=False, cut=None, streams=None, after_fork=
         rig_bwd = LF.abs_diff_levels(cam_bwd, flow_bwd)                                # :476
     l1 = LF.photometric_reconstruction_loss(tgt, refs, K, Kinv, depth, exp_mask, pose,
                                             lambda_oob=cfg.lambda_oob, qch=cfg.qch, wssim=cfg.wssim)   # :490
-    LF.forward_stream = side         # (the forward launches of the terms below: on the side stream, behind the consensus target)
-    try:
+    with step_scope.forward_stream(side):    # (the forward launches of the terms below: on the side stream, behind the consensus target)
         l2 = LF.explainability_loss(exp_mask) if cfg.w2 > 0 else 0                     # :492-495
         if cfg.smoothness_type == "regular":                                           # :497-501
             l3s = [LF.smooth_loss(depth), LF.smooth_loss(flow_fwd), LF.smooth_loss(flow_bwd), LF.smooth_loss(exp_mask)]
@@ -220,8 +219,6 @@ def cc_forward(nets, batch, cfg, keep=False, cut=None, streams=None, after_fork=
             l3s = [LF.edge_aware_smoothness_sum(tgt, [depth, flow_fwd, flow_bwd, exp_mask])]  # the four terms, one job table
         l4 = LF.photometric_flow_loss(tgt, refs[1:3], [flow_bwd, flow_fwd], flow_exp_mask,
                                       lambda_oob=cfg.lambda_oob, qch=cfg.qch, wssim=cfg.wssim)         # :503
-    finally:
-        LF.forward_stream = None
     if side is not None:
         origin.wait_stream(side)
         if not torch.cuda.is_current_stream_capturing():      # (eager mode: allocated on the side stream, read on this one)
@@ -357,6 +354,7 @@ class FlatAdam:
         per_net = [([p for p in n.parameters() if p.requires_grad] if n is not None else []) for n in nets]
         params = [p for ps in per_net for p in ps]
         self.params = params
+        self.nets = [n for n in nets if n is not None]
         # "<net>.<parameter name>" per entry of `params` (param_stats)
         self.param_names = ["%s.%s" % (NET_NAMES[i] if i < len(NET_NAMES) else i, name) for i, n in enumerate(nets) if n is not None
                             for name, p in n.named_parameters() if p.requires_grad]
@@ -431,6 +429,17 @@ class FlatAdam:
         self._rccl = None
         self.n_comms = 1            # RCCL communicators of the captured form: one per issuing stream (rccl())
         self._pstats = None         # param_stats(): chunk table, partials and outputs, built on first use
+
+    def release(self):
+        """The parameters leave the buckets: every parameter of the networks gets a storage of its own with the same values and
+        loses its gradient (the views would keep flat_p and flat_g alive), the gradient sinks are emptied and the weight images
+        registered against the buckets forgotten.  Afterwards nothing but this object refers to the four buckets."""
+        for n in self.nets:
+            for p in n.parameters():
+                p.data = p.data.clone()
+                p.grad = None
+        self.sinks.clear()
+        ops.packs.reset()
 
     def zero_grad(self):
         engine().call("cc_fill", self.flat_g, self.flat_g.numel(), 0.0, STREAM)
@@ -881,6 +890,8 @@ class CCTrainer:
         self.static_batch = None
         self.losses = None
         self.nan_flags = []
+        self._scr = None                 # _scratch(): measurement only
+        self._closed = False
         self.opt.n_comms = 1 + (len(self.net_streams) if self.net_streams else 0)
         # step ledger (StepConfig.ledger): its device state is allocated here, before any capture; survives switch_pipeline / a re-capture
         cap = getattr(cfg, "ledger", None)
@@ -891,6 +902,31 @@ class CCTrainer:
                 self.opt.rccl()          # the communicators must exist before any capture
             except Exception as e:       # noqa: BLE001 -- librccl not bindable / communicator set-up refused: keep training, say so
                 self._fall_back("the direct RCCL communicators could not be created (%r)" % (e,))
+
+    def close(self):
+        """The end of this trainer's life (a phase boundary of the driver, a test that builds the next one): nothing of it stays on
+        the device -- the captured graphs are reset (their private pool with them), the static batch, the captured losses and NaN
+        flags and the measurement scratch are dropped, and the networks' parameters move out of the optimizer's buckets
+        (FlatAdam.release).  The networks keep their weights; a step() after this raises.  Harmless when called again."""
+        if self._closed:
+            return
+        self._closed = True
+        on_device = self.opt.flat_p.is_cuda
+        if on_device:
+            torch.cuda.synchronize()
+        for g in (self.graph, self.graph_b):
+            if g is not None:
+                g.reset()
+        self.graph = self.graph_b = None
+        self.static_batch = self.losses = self._scr = None
+        self.nan_flags = []
+        # (torch keeps one BLAS workspace per (handle, stream) for the life of the process -- 128 MB each on this stack, taken by the
+        # step's one torch.dot (LF.weighted_total) on every trainer's capture stream, out of the captured graph's pool; no graph is
+        # alive at this point, so they can all go)
+        clear = getattr(torch._C, "_cuda_clearCublasWorkspaces", None)
+        if on_device and clear is not None:
+            clear()
+        self.opt.release()
 
     def switch_pipeline(self, pipeline):
         """Change the step form of a live trainer (same bucket, same optimizer state): the captured graphs are dropped and the next
@@ -933,39 +969,34 @@ class CCTrainer:
         self._chunk_lo = {}
 
     # ------------------------------------------------------------------------------------------------ the step's pieces
-    def _begin(self, batch):
-        tape.BN_COUNTERS = self.bn_counters
-        self.bn_counters.begin()
-        LF.pyramid_cache.clear()
+    def _scope(self, batch):
+        """the scope of one step (cc_amd/step_scope.py): entered before the step's first launch -- it brings the weight images up to
+        date, per-network: fresh from the previous step's tails, no launch -- and left behind its last one"""
+        if self.ledger is not None:
+            self._step_flags = []
+            self._ledger_n = int(batch[0].shape[0])
+        return step_scope.StepScope(batch[0].device, sinks=self.opt.sinks, bn_counters=self.bn_counters,
+                                    nan_flags=self._step_flags if self.ledger is not None else None,
+                                    images="per_network" if self.pipeline == "per_network" else "legacy")
+
+    def _loss_grads(self, scope, batch):
+        """counter tick, zero grads, forward of the four nets + losses (train.py:454-509) and d loss / d (network outputs)
+        -> (losses, dp pairs, mf pairs)"""
         if self.pipeline == "per_network":
-            ops.packs.begin_step()         # fresh from the previous step's per-network refresh: no launch
             self.opt.tick()                # the networks' Adam segments of this step all read the advanced counter
-        else:
-            ops.packs.prepack_all()        # every conv layer's [tap][c][m] weight images, one launch (weights changed in Adam)
         if not self.net_streams:
             self.opt.zero_grad()                                            # :566  (with side streams: behind their forks, cc_forward)
-        ops.grad_sinks = self.opt.sinks
-        LF.scalar_pool.begin(batch[0].device)
-        if self.ledger is not None:
-            LF.step_nan_flags = self._step_flags = []
-            self._ledger_n = int(batch[0].shape[0])
-
-    def _loss_grads(self, batch):
-        """forward of the four nets + losses (train.py:454-509) and d loss / d (network outputs) -> (losses, dp pairs, mf pairs)"""
         cut = {}
-        LF.head_grads.begin()              # the loss terms' gradients of a shared network output meet in one accumulator
-        try:
+        with scope.loss_phase():
             out = cc_forward(self.nets, batch, self.cfg, cut=cut, streams=self.net_streams,
                              after_fork=self.opt.zero_grad if self.net_streams else None)
             self.bn_counters.commit()
             pairs = cut.get("dp", []) + cut.get("mf", [])
             g = torch.autograd.grad(out["loss"], [d for _, d in pairs], allow_unused=True) if pairs else ()   # :567, losses only
-        finally:
-            LF.head_grads.end()
         ndp = len(cut.get("dp", []))
         dp = [(t, gt) for (t, _), gt in zip(pairs[:ndp], g[:ndp]) if gt is not None]
         mf = [(t, gt) for (t, _), gt in zip(pairs[ndp:], g[ndp:]) if gt is not None]
-        ops.wgrad_queue.enabled = not config.debug.no_wgrad_queue
+        scope.park_weight_gradients()
         losses = {k: v.detach() for k, v in out.items() if torch.is_tensor(v) and k.startswith("loss")}
         return losses, dp, mf
 
@@ -990,9 +1021,8 @@ class CCTrainer:
     #      backward of DispResNet6 + PoseNetB6                                   -> all-reduce(flat_g[:n_dp]) starts
     #   B: backward of MaskNet6 + Back2Future                                    -> all-reduce(flat_g[n_dp:]) (exposed)
     # The nets only meet in the losses, so the two backward stages are independent given the output gradients.
-    def _stage_a(self, batch, fuse_b=False):
-        self._begin(batch)
-        losses, dp, mf = self._loss_grads(batch)
+    def _stage_a(self, scope, batch, fuse_b=False):
+        losses, dp, mf = self._loss_grads(scope, batch)
         if fuse_b and self.net_streams:
             self._backward(dp + mf)
             self._sync_streams(bool(dp + mf))
@@ -1018,36 +1048,13 @@ class CCTrainer:
         self._backward(mf)
         self._sync_streams(bool(mf))
 
-    def _stage_end(self, failed=False):
-        tape.BN_COUNTERS = None
-        tape.NET_DONE = tape.NET_MARK = None
-        LF.step_nan_flags = None
-        if failed:
-            # a stage raised part-way: the parked launches' operands belong to the failed step and no fork / join is in place for
-            # the side streams -- drop them instead of launching
-            ops.wgrad_queue.drop()
-            ops.wgrad_reduces.drop()
-        else:
-            ops.wgrad_queue.flush()
-        ops.wgrad_queue.enabled = False
-        LF.scalar_pool.end()
-        ops.grad_sinks = {}
-        if self.pipeline == "per_network" and not failed:
-            ops.packs.end_step()
-        else:
-            ops.packs.invalidate()
-
     def _fwd_bwd(self, batch, between=None):
         """(legacy forms) forward + backward of one mini-batch; `between()` runs between the two backward stages."""
-        ok = False
-        try:
-            losses, mf = self._stage_a(batch, fuse_b=between is None)      # (no collective between the stages: one backward call)
+        with self._scope(batch) as scope:
+            losses, mf = self._stage_a(scope, batch, fuse_b=between is None)   # (no collective between the stages: one backward call)
             if between is not None:
                 between()
             self._stage_b(mf)
-            ok = True
-        finally:
-            self._stage_end(failed=not ok)
         return losses
 
     # ------------------------------------------------------------------------------------------------ per-network pipeline
@@ -1106,7 +1113,7 @@ class CCTrainer:
         return 0
 
     def _scratch(self):
-        if getattr(self, "_scr", None) is None:
+        if self._scr is None:
             self._scr = torch.empty(64 << 20, device=self.opt.flat_p.device, dtype=torch.float32)      # 256 MB: ~50 us per fill
         return self._scr
 
@@ -1120,17 +1127,14 @@ class CCTrainer:
 
     def _step_pipelined(self, batch):
         """train.py:445-568 with every network's exchange + update behind ITS backward pass (see the class docstring)"""
-        ok = False
         self._done = set()
         self._open_hi = {}
         self.segment_calls = []
-        try:
-            self._begin(batch)
-            losses, dp, mf = self._loss_grads(batch)
-            tape.NET_DONE, tape.NET_MARK = self._net_done, (self._net_mark if self._chunk_lo else None)
+        with self._scope(batch) as scope:
+            losses, dp, mf = self._loss_grads(scope, batch)
             both = dp + mf
-            self._backward(both)
-            tape.NET_DONE = tape.NET_MARK = None
+            with scope.network_hooks(self._net_done, self._net_mark if self._chunk_lo else None):
+                self._backward(both)
             self._sync_streams(bool(both))
             for i in range(len(self.nets)):     # networks that are not on the tape (alternative architectures) or received no gradient
                 if i not in self._done:
@@ -1138,9 +1142,6 @@ class CCTrainer:
             # (the side streams were joined above, every tail is ordered in front of this point of the step's own stream: the guard
             # rows and the counter the row reads are final)
             self._ledger_append(losses)
-            ok = True
-        finally:
-            self._stage_end(failed=not ok)
         return losses
 
     def _ledger_append(self, losses):
@@ -1216,9 +1217,7 @@ class CCTrainer:
         for b, saved in bn_state + opt_state:
             b.copy_(saved)
         if pipelined:
-            ops.packs.mark_stale()
-            ops.packs.prepack_all()         # the images of the restored weights: the captured step starts from them
-            ops.packs.end_step()
+            ops.packs.rebuild()             # the images of the restored weights: the captured step starts from them
             self._packed_version = None
             self._weights_touched()
         LF.check_finite()                   # the warm-up's own flags (and drop them: the captured step registers its own)
@@ -1237,17 +1236,15 @@ class CCTrainer:
         gc.disable()
         try:
             if self.split_graphs:
-                # two graphs sharing one memory pool: the collective of the first gradient segment is issued between them
+                # two graphs sharing one memory pool: the collective of the first gradient segment is issued between them.  ONE scope
+                # spans both: entered inside the first graph (its weight-image refresh is a node of it), left behind the second
                 self.graph_b = torch.cuda.CUDAGraph()
-                ok = False
-                try:
+                with contextlib.ExitStack() as whole_step:
                     with torch.cuda.graph(self.graph, stream=s, capture_error_mode=mode):
-                        self.losses, mf = self._stage_a(self.static_batch)
+                        scope = whole_step.enter_context(self._scope(self.static_batch))
+                        self.losses, mf = self._stage_a(scope, self.static_batch)
                     with torch.cuda.graph(self.graph_b, pool=self.graph.pool(), stream=s, capture_error_mode=mode):
                         self._stage_b(mf)
-                    ok = True
-                finally:
-                    self._stage_end(failed=not ok)
             else:
                 with torch.cuda.graph(self.graph, stream=s, capture_error_mode=mode):
                     self.losses = self._step_pipelined(self.static_batch) if pipelined else self._fwd_bwd(self.static_batch)
@@ -1386,13 +1383,15 @@ class CCTrainer:
 
     def step(self, batch):
         """train.py:445-568 for one mini-batch: returns the (device) loss tensors of this step."""
+        if self._closed:
+            raise RuntimeError("this CCTrainer is closed (close()): its graphs and its buckets are gone; build a new one")
         self.opt.flush_hyper()              # pending lr / betas / eps / weight-decay writes: in front of the replay, on this stream
         if self.pipeline == "per_network":
             if self._weights_touched():
-                ops.packs.mark_stale()
                 if self.graph is not None:
-                    ops.packs.prepack_all()     # (the captured step contains no start-of-step refresh)
-                    ops.packs.end_step()
+                    ops.packs.rebuild()         # (the captured step contains no start-of-step refresh)
+                else:
+                    ops.packs.mark_stale()
             if self.use_graph:
                 if self.graph is None:
                     try:

@@ -198,6 +198,7 @@ def validate_without_gt_from_store(store, disp_net, pose_net, mask_net, flow_net
     import numpy as np
     from .custom_transforms import DeviceTrainTransform
     from .ledger import Ledger, LOSS_NAMES
+    from .step_scope import StepScope
     from .trainer import cc_forward
     if batch_size < 1 or len(store) < 1:
         raise ValueError("validate_without_gt_from_store: batch size %d over %d samples" % (batch_size, len(store)))
@@ -219,13 +220,10 @@ def validate_without_gt_from_store(store, disp_net, pose_net, mask_net, flow_net
                 prep._local_norm(x, b, nf, one, b * one)
             K = store.intrinsics_np[store.sample_scene_np[ids]]
             KK = torch.from_numpy(np.stack([K, np.stack([np.linalg.inv(k) for k in K])])).to(dev)
-            LF.pyramid_cache.clear()
-            LF.step_nan_flags = flags = []
-            try:
+            flags = []
+            with StepScope(nan_flags=flags):
                 out = cc_forward(nets, (x[0], [x[j] for j in range(1, nf)], KK[0], KK[1]), cfg)
-            finally:
-                LF.step_nan_flags = None
-                LF.pyramid_cache.clear()
+            LF.pyramid_cache.clear()
             LF.take_nan_flags()                                            # (they are sources of the meter's row instead)
             meter.append({k: (v.reshape(1) if torch.is_tensor(v) else v) for k, v in out.items()}, b, nan_flags=flags)
     avg = meter.average()                                                  # the loop's only host read-back

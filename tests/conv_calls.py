@@ -17,6 +17,7 @@ import torch
 
 from cc_amd import loss_functions as LF, models, ops, synthetic as syn, trainer as T
 from cc_amd._lib import engine
+from cc_amd.step_scope import StepScope
 from loss_calls import ArgLog
 from oracle.make_golden import ALT_NETS, AB, AH, AW, SB, SH, SW, alt_net_args
 
@@ -158,23 +159,18 @@ def trace_config1(dev):
     opt = T.FlatAdam([dn, pn], T.StepConfig())
     opt.zero_grad()
     tgt, refs, K, Kinv = tgt.to(dev), [r.to(dev) for r in refs], K.to(dev), Kinv.to(dev)
-    ops.grad_sinks = opt.sinks
     try:
-        with ConvLog() as log:
+        with StepScope(sinks=opt.sinks) as scope, ConvLog() as log:
             disp = dn(tgt)
             exp, pose = pn(tgt, refs)
             depth = 1 / disp[0]
             l1 = LF.photometric_reconstruction_loss(tgt, refs, K, Kinv, depth, None, pose, wssim=0)
             l3 = LF.smooth_loss(depth)
-            ops.wgrad_queue.enabled = True
+            scope.park_weight_gradients()
             (l1 + 0.1 * l3).backward()
             ops.wgrad_queue.flush()
             ops.wgrad_reduces.flush()
     finally:
-        ops.wgrad_queue.drop()
-        ops.wgrad_reduces.drop()
-        ops.wgrad_queue.enabled = False
-        ops.grad_sinks = {}
         ops.packs.reset()
     LF.check_finite()
     return [t.detach().clone() for t in list(disp) + [pose, l1, l3, opt.flat_g]], log.calls

@@ -10,6 +10,7 @@ import torch
 
 from cc_amd import loss_functions as LF, synthetic as syn, trainer as T
 from cc_amd._lib import engine, STREAM
+from cc_amd.step_scope import StepScope
 from oracle.make_golden import pyramid_inputs
 
 FIXTURE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "loss_calls.json")
@@ -71,17 +72,12 @@ def loss_phase(dev, B=LB, H=LH, W=LW):
     nets = (lambda t: disp, lambda t, r: pose, lambda t, r: mask, lambda t, r: (ffw, fbw, None))
     batch = (tgt.to(dev), [r.to(dev) for r in refs], K.to(dev), Kinv.to(dev))
     cut = {}
-    LF.pyramid_cache.clear()
-    LF.scalar_pool.begin(batch[0].device)
-    LF.head_grads.begin()
     try:
-        with ArgLog() as log:
+        with StepScope(batch[0].device) as scope, scope.loss_phase(), ArgLog() as log:
             out = T.cc_forward(nets, batch, T.StepConfig(), cut=cut)
             pairs = cut["dp"] + cut["mf"]
             grads = torch.autograd.grad(out["loss"], [d for _, d in pairs], allow_unused=True)
     finally:
-        LF.head_grads.end()
-        LF.scalar_pool.end()
         LF.pyramid_cache.clear()
         LF.take_nan_flags()
     losses = {k: v.detach().clone() for k, v in out.items() if torch.is_tensor(v) and k.startswith("loss")}

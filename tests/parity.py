@@ -6,6 +6,7 @@ import pytest
 import torch
 
 from cc_amd import synthetic as syn, inverse_warp as IW, loss_functions as LF, ssim as SS
+from cc_amd.step_scope import StepScope
 from oracle import geometry as G, losses as L
 from oracle.make_golden import pyramid_inputs
 
@@ -1245,12 +1246,10 @@ def check_wgrad_list(dev, tol=2e-5, shapes=None, groups=None):
     x2, gy2 = rn(B, Cin, H, W), rn(*items[0][0][0].shape)
     want[0] = want[0] + ref_grad(x2, gy2, (Cout, Cin, k, k), k, st, pad)
     items.append(([gy2.to(dev).contiguous()], [x2.to(dev).contiguous()], [bufs[0]], items[0][3]))
-    ops.wgrad_queue.enabled = True
-    try:
+    with StepScope() as scope:
+        scope.park_weight_gradients()
         ops._wgrad_list(items)
         ops.wgrad_reduces.flush()
-    finally:
-        ops.wgrad_queue.enabled = False
     if dev != "cpu":
         torch.cuda.synchronize()
     for i, (b, w_) in enumerate(zip(bufs, want)):

@@ -72,21 +72,18 @@ def test_parked_bias_sum_is_reduced_before_its_target_is_parked_again_emulated()
     the B * H * W <= 32768 bound under which the kernel writes the bias gradient itself and nothing is parked."""
     import torch
     from cc_amd import ops
+    from cc_amd.step_scope import StepScope
     from hipemu.emu import emulated_engine
     gen = torch.Generator().manual_seed(7)
     gy, y = torch.randn(2, 2, 128, 160, generator=gen), torch.randn(2, 2, 128, 160, generator=gen)
     gb = torch.zeros(2)
     ge = [torch.empty_like(gy) for _ in range(2)]
     with emulated_engine():
-        ops.wgrad_queue.enabled = True
-        try:
-            with CC.ConvLog() as log:
-                for k in range(2):
-                    ops._act_bwd_bias([gy], [y], [ge[k]], [gb], 1, 1.0, 0.0, True)
-                ops.wgrad_reduces.flush()
-        finally:
-            ops.wgrad_reduces.drop()
-            ops.wgrad_queue.enabled = False
+        with StepScope() as scope, CC.ConvLog() as log:
+            scope.park_weight_gradients()
+            for k in range(2):
+                ops._act_bwd_bias([gy], [y], [ge[k]], [gb], 1, 1.0, 0.0, True)
+            ops.wgrad_reduces.flush()
     got = [(c[0], c[1][1]) if c[0] == "cc_wgrad_reduce_table" else c[0] for c in log.calls if not c[0].endswith("_ws_bytes")]
     assert got == ["cc_act_bwd_bias_group_defer", ("cc_wgrad_reduce_table", 1)] * 2, got
     # both calls added sum over (n, h, w) of gy * relu'(y): fp32 sums of 81920 terms per channel, summed in lanes, trees and chunks,

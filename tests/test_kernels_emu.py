@@ -170,6 +170,7 @@ def test_head_gradient_accumulators_match_the_engine_sums():
     # engine sums up from the terms' separate tensors
     import torch
     from cc_amd import loss_functions as LF
+    from cc_amd.step_scope import StepScope
     g = torch.Generator().manual_seed(5)
     img = torch.rand(2, 3, 24, 40, generator=g) * 2 - 1
     masks = [torch.sigmoid(torch.randn(2, 4, 24 >> s, 40 >> s, generator=g)).requires_grad_(True) for s in range(3)]
@@ -183,24 +184,18 @@ def test_head_gradient_accumulators_match_the_engine_sums():
     # repeated: the duplicate position used to share ONE launch with the first one ('=' and '+=' of unordered jobs: a race that lost
     # a contribution in most, not all, runs); now it goes into a launch of its own
     for _ in range(12):
-        LF.head_grads.begin()
-        try:
+        with StepScope() as scope, scope.loss_phase():
             assert LF.head_grads.active
             got = torch.autograd.grad(total(), masks)
-        finally:
-            LF.head_grads.end()
         for a, b in zip(got, want):
             assert float((a - b).abs().max()) <= 1e-6 * max(float(b.abs().max()), 1e-30), float((a - b).abs().max())
     # a second backward through the same term would add into the accumulators twice: refused, not silently doubled
-    LF.head_grads.begin()
-    try:
+    with StepScope() as scope, scope.loss_phase():
         t = total()
         torch.autograd.grad(t, masks, retain_graph=True)
         import pytest
         with pytest.raises(RuntimeError):
             torch.autograd.grad(t, masks)
-    finally:
-        LF.head_grads.end()
 
 
 def test_cost_volume():

@@ -172,3 +172,43 @@ def test_no_write_while_a_capture_is_in_progress(monkeypatch):
         opt.lr = 2e-4
         opt.flush_hyper()
         assert float(opt.hyper_dev[0, 0]) == pytest.approx(2e-4) and float(opt.hyper_dev[3, 0]) == pytest.approx(2e-4)
+
+
+def test_release_moves_the_parameters_out_of_the_buckets(monkeypatch):
+    """FlatAdam.release(): same values in storages of their own, no gradients, no sinks, the weight images forgotten -- and the
+    modules are as good as new ones: a second FlatAdam over them takes the same first step, bit for bit, as one over a fresh copy
+    of the weights"""
+    from cc_amd import ops
+    torch.manual_seed(0)
+
+    def grad(n, seed):
+        return 0.05 * torch.randn(n, generator=torch.Generator().manual_seed(seed))
+    with emulated_engine():
+        nets = C._two_nets()
+        opt = T.FlatAdam(nets, T.StepConfig())
+        opt.flat_g.copy_(grad(opt.flat_g.numel(), 2))
+        opt.step(0.5)                                   # (the weights are not the initial ones any more)
+        params = [p for n in nets for p in n.parameters()]
+        want = [p.detach().clone() for p in params]
+        resets = []
+        monkeypatch.setattr(ops.packs, "reset", lambda: resets.append(1))
+        opt.release()
+        monkeypatch.undo()
+        assert resets == [1]
+        for bucket in (opt.flat_p, opt.flat_g):
+            lo, hi = bucket.data_ptr(), bucket.data_ptr() + 4 * bucket.numel()
+            assert not any(lo <= p.data_ptr() < hi for p in params)
+        assert all(torch.equal(p.detach(), w) for p, w in zip(params, want))
+        assert all(p.grad is None for p in params) and opt.sinks == {}
+        assert len({p.data_ptr() for p in params}) == len(params)
+        fresh = C._two_nets()
+        for n, m in zip(fresh, nets):
+            n.load_state_dict({k: v.clone() for k, v in m.state_dict().items()})
+        steps = []
+        for mods in (nets, fresh):
+            o = T.FlatAdam(mods, T.StepConfig(weight_decay=1e-2))
+            o.flat_g.copy_(grad(o.flat_g.numel(), 3))
+            o.step(0.5)
+            steps.append((o.flat_p, o.exp_avg, o.exp_avg_sq, o.step_dev))
+        assert all(torch.equal(a, b) for a, b in zip(*steps))
+        assert not torch.equal(steps[0][0], opt.flat_p)       # (the released buckets are nobody's weights any more)

@@ -58,3 +58,44 @@ def test_launcher_entries_are_spelled_once():
     for name in LAUNCHER_ENTRIES:
         assert sites.get(name) == ["cc_amd/ops.py"], (name, sites.get(name))
     assert not any("_Conv2dFn" in text for text in src.values())
+
+
+# the process-wide state of a training step (cc_amd/step_scope.py): assigned, begun and ended in that module only
+STEP_STATE_ASSIGNED = ["tape.BN_COUNTERS", "tape.NET_DONE", "tape.NET_MARK", "ops.grad_sinks", "wgrad_queue.enabled",
+                       "LF.step_nan_flags", "LF.forward_stream"]
+STEP_STATE_CALLS = ["scalar_pool.begin", "scalar_pool.end", "head_grads.begin", "head_grads.end", "packs.begin_step", "packs.end_step",
+                    "packs.invalidate"]
+# diagnosis: tools/branch_timeline.py wraps the installed tape.NET_DONE for the length of one network's backward call and puts
+# it back (stamps around the network's tail inside a captured step)
+STEP_STATE_EXCEPTIONS = {("tools/branch_timeline.py", "tape.NET_DONE")}
+
+
+def _step_state_sites(root):
+    """{(file, name)}: assignments (plain, augmented, chained, tuple targets) to the names above and calls of the methods above,
+    matched on the dotted spelling's end (`ops.wgrad_queue.enabled = ..` is an assignment to wgrad_queue.enabled)"""
+    def targets(t):
+        if isinstance(t, (ast.Tuple, ast.List)):
+            for e in t.elts:
+                yield from targets(e)
+        else:
+            yield t
+    sites = set()
+    for f in glob.glob(os.path.join(root, "cc_amd", "*.py")) + glob.glob(os.path.join(root, "tools", "*.py")):
+        rel = os.path.relpath(f, root)
+        for n in ast.walk(ast.parse(open(f).read())):
+            if isinstance(n, (ast.Assign, ast.AugAssign, ast.AnnAssign)):
+                spelled = [ast.unparse(x) for t in (n.targets if isinstance(n, ast.Assign) else [n.target]) for x in targets(t)]
+                names = STEP_STATE_ASSIGNED
+            elif isinstance(n, ast.Call):
+                spelled, names = [ast.unparse(n.func)], STEP_STATE_CALLS
+            else:
+                continue
+            sites.update((rel, name) for sp in spelled for name in names if sp == name or sp.endswith("." + name))
+    return sites
+
+
+def test_step_state_is_switched_in_one_module():
+    sites = _step_state_sites(ROOT)
+    outside = {s for s in sites if s[0] != "cc_amd/step_scope.py"}
+    assert outside == STEP_STATE_EXCEPTIONS, sorted(outside ^ STEP_STATE_EXCEPTIONS)
+    assert {name for f, name in sites if f == "cc_amd/step_scope.py"} == set(STEP_STATE_ASSIGNED + STEP_STATE_CALLS)

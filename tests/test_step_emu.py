@@ -283,3 +283,85 @@ def test_per_network_pipeline_falls_back_loudly_without_direct_rccl(monkeypatch,
         assert "falling back to pipeline='post'" in capsys.readouterr().err
     finally:
         dist.destroy_process_group()
+
+
+def _assert_step_state_idle():
+    """every idle value cc_amd/step_scope.py documents"""
+    from cc_amd import loss_functions as LF, ops, tape
+    assert tape.BN_COUNTERS is None and tape.NET_DONE is None and tape.NET_MARK is None
+    assert ops.grad_sinks == {}
+    assert ops.wgrad_queue.enabled is False
+    for parked in (ops.wgrad_queue, ops.wgrad_reduces):
+        assert not any(inst.busy() for inst, _ in parked._inst.values())
+    assert not any(inst.keep or inst.targets for inst, _ in ops.wgrad_reduces._inst.values())
+    assert ops.packs.valid is False and ops.packs.recording is False
+    assert LF.scalar_pool.buf is None
+    assert LF.head_grads.active is False and LF.head_grads.acc == {}
+    assert LF.step_nan_flags is None and LF.forward_stream is None
+
+
+def _config2_trainer(pipeline="per_network"):
+    """DispResNet6 + PoseNetB6 (photometric + smoothness loss), seeded weights, eager, the ledger on (a step registers its NaN
+    flags); 64 x 64 is the smallest frame the networks' six levels accept, and a batch of 2 the smallest the training-mode
+    BatchNorm of DispResNet6's 1 x 1 level does (one value per channel is refused, as torch refuses it)"""
+    nets = T.build_nets("cpu", flow=False, mask=False, init=False)
+    for n in nets:
+        if n is not None:
+            n.load_state_dict(syn.seeded_state_dict(n, 0))
+    return T.CCTrainer(nets, T.StepConfig(ledger=4), use_graph=False, pipeline=pipeline), syn.sample(2, 64, 64, seed=1)
+
+
+@pytest.mark.slow
+@pytest.mark.parametrize("pipeline", ["per_network", "post", "staged"])
+def test_step_state_is_idle_after_a_step(pipeline):
+    with emulated_engine():
+        tr, batch = _config2_trainer(pipeline)
+        losses = tr.step(batch)
+        _assert_step_state_idle()
+        assert all(bool(torch.isfinite(v).all()) for v in losses.values())
+        tr.close()
+
+
+def _assert_next_step_succeeds(tr, batch):
+    losses = tr.step(batch)
+    assert losses and all(bool(torch.isfinite(v).all()) for v in losses.values())
+    _assert_step_state_idle()
+    tr.close()
+
+
+@pytest.mark.slow
+def test_step_state_is_idle_after_a_loss_term_raises(monkeypatch):
+    from cc_amd import loss_functions as LF
+
+    def boom(*a, **k):
+        raise ZeroDivisionError("loss term")
+    with emulated_engine():
+        tr, batch = _config2_trainer()
+        monkeypatch.setattr(LF, "edge_aware_smoothness_loss", boom)
+        with pytest.raises(ZeroDivisionError):
+            tr.step(batch)
+        _assert_step_state_idle()
+        monkeypatch.undo()
+        _assert_next_step_succeeds(tr, batch)
+
+
+@pytest.mark.slow
+def test_step_state_is_idle_after_the_backward_pass_raises_with_work_parked(monkeypatch):
+    from cc_amd import ops
+    group, seen = ops._wgrad_group, {"calls": 0}
+
+    def third_call_raises(*a, **k):
+        seen["calls"] += 1
+        if seen["calls"] == 3:
+            seen["parked"] = ops.wgrad_queue.busy() or ops.wgrad_reduces.busy()
+            raise ZeroDivisionError("weight-gradient group")
+        return group(*a, **k)
+    with emulated_engine():
+        tr, batch = _config2_trainer()
+        monkeypatch.setattr(ops, "_wgrad_group", third_call_raises)
+        with pytest.raises(ZeroDivisionError):
+            tr.step(batch)
+        assert seen["calls"] == 3 and seen["parked"], seen         # (the premise: in the middle of the backward pass, work parked)
+        _assert_step_state_idle()
+        monkeypatch.undo()
+        _assert_next_step_succeeds(tr, batch)

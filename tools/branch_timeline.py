@@ -59,12 +59,12 @@ def bwd(ctx, *g):
 
 
 tape._NetFn.backward = staticmethod(bwd)
-_begin, _lg, _sync = tr._begin, tr._loss_grads, tr._sync_streams
-tr._begin = lambda bt: (stamp(0, "step starts"), _begin(bt))[1]
+_scope, _lg, _sync = tr._scope, tr._loss_grads, tr._sync_streams
+tr._scope = lambda bt: (stamp(0, "step starts"), _scope(bt))[1]
 
 
-def lg(bt):
-    r = _lg(bt)
+def lg(scope, bt):
+    r = _lg(scope, bt)
     stamp(30, "losses + their gradients done (backward passes are enqueued next)")
     return r
 

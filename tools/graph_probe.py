@@ -30,7 +30,7 @@ def main():
     ap.add_argument("--steps", type=int, default=30)
     args = ap.parse_args()
     ab_env.apply()
-    from cc_amd import config, ops, synthetic as syn, tape, trainer as T, loss_functions as LF
+    from cc_amd import config, synthetic as syn, trainer as T
     dev = torch.device("cuda", 0)
     torch.manual_seed(0)
     nets = T.build_nets(dev)
@@ -42,24 +42,12 @@ def main():
         """the step without its backward pass: weight images, zero grads, four forward passes, losses (then Adam on zero gradients)"""
 
         def _fwd_bwd(self, batch, between=None):
-            try:
-                tape.BN_COUNTERS = self.bn_counters
-                self.bn_counters.begin()
-                LF.pyramid_cache.clear()
-                ops.packs.prepack_all()
+            with self._scope(batch) as scope:
                 self.opt.zero_grad()
-                ops.grad_sinks = self.opt.sinks
-                LF.scalar_pool.begin(batch[0].device)
-                LF.head_grads.begin()
-                try:
-                    with torch.no_grad():
-                        out = T.cc_forward(self.nets, batch, self.cfg, streams=self.net_streams)
-                    self.bn_counters.commit()
-                finally:
-                    LF.head_grads.end()
+                with scope.loss_phase(), torch.no_grad():
+                    out = T.cc_forward(self.nets, batch, self.cfg, streams=self.net_streams)
+                self.bn_counters.commit()
                 return {k: v.detach() for k, v in out.items() if torch.is_tensor(v) and k.startswith("loss")}
-            finally:
-                self._stage_end()
 
     def steady(tr, n):
         for _ in range(4):

@@ -75,7 +75,7 @@ def run(eng, G, B, Cin, H, W, Cout, iters, wino):
         step()
     torch.cuda.synchronize()
     recs = collect(eng)
-    ops.packs.invalidate()
+    ops.packs.reset()
     return recs, out, call_ms
 
 

@@ -38,7 +38,7 @@ def main():
             for ln in buf.raw[:n].decode().splitlines():
                 nm, cnt, ms, gf = ln.split("\t")
                 rows.append((Cin, nm, float(ms) / int(cnt) * 1e3))
-            ops.packs.invalidate()
+            ops.packs.reset()
         for r in rows:
             print("C %4d  %-22s %8.2f us" % r)
         us = {c: t for c, n, t in rows if n.startswith("k_wino")}

@@ -80,7 +80,7 @@ def run(G, B, Cin, H, W, Cout, iters, env):
     torch.cuda.synchronize()
     ms = e0.elapsed_time(e1) / (4 * iters)
     res = [t.detach().clone() for t in out[0]] + [t.detach().clone() for t in out[1]]
-    ops.packs.invalidate()
+    ops.packs.reset()
     del gr
     return ms, res
 
