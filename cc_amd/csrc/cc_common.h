@@ -179,4 +179,44 @@ __device__ __forceinline__ void block_sum_256(float (&v)[N], float* scratch) {
     __syncthreads();
 }
 
+// The strided LDS tree over a workgroup of THREADS work-items (a power of two): red[t] = v, then for s = THREADS/2, THREADS/4, .. 1
+// red[t] = OP(red[t], red[t + s]) for t < s -- ONE association order, so a sum's bits depend on the values alone.  Every work-item
+// gets the result; `red` (THREADS elements of LDS) is free again on return.  T: double, unsigned; OP: Sum, Max.
+struct Sum {
+    template <typename T> __device__ static __forceinline__ T apply(T a, T b) { return a + b; }
+};
+struct Max {    // (b NaN: a stays)
+    template <typename T> __device__ static __forceinline__ T apply(T a, T b) { return b > a ? b : a; }
+};
+template <int THREADS, typename OP, typename T>
+__device__ __forceinline__ T block_tree(T v, T* red) {
+    const int t = threadIdx.x;
+    red[t] = v;
+    __syncthreads();
+    for (int s = THREADS / 2; s > 0; s >>= 1) {
+        if (t < s) {
+            const T b = red[t + s];
+            red[t] = OP::apply(red[t], b);
+        }
+        __syncthreads();
+    }
+    const T r = red[0];
+    __syncthreads();
+    return r;
+}
+
+// Sum of one double over a 256-thread workgroup in ANOTHER order than block_tree's: xor shuffles inside a wave, then
+// (w0 + w1) + (w2 + w3) -- the spatial-normalisation partials (losses.hip) are defined by it.  red: 4 doubles; every work-item
+// gets the total.
+__device__ __forceinline__ double block_sum_f64(double v, double* red) {
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
+    if (lane == 0) red[wid] = v;
+    __syncthreads();
+    const double r = (red[0] + red[1]) + (red[2] + red[3]);
+    __syncthreads();
+    return r;
+}
+
 }  // namespace cc

@@ -6,10 +6,11 @@
 //                  finite sum) and every workgroup stores ONE fp64 partial, unconditionally;
 //   k_guard_finish one workgroup sums the partials in a fixed order and writes the network's guard row
 //                  {norm, coef, finite, skipped, 0, 0, 0, 0} (skipped is a running count: += 1 per non-finite step);
-//   k_adam_guard   k_adam_hyper's update (optim.hip) of one row with the gradient multiplied by coef, the bias corrections taken
-//                  at t = step - skipped (a skipped step does not count for this network) and NO store at all when finite == 0.
+//   k_adam_guard   k_adam_hyper's update of one row -- the one body of adam_update.h -- with the gradient multiplied by coef, the
+//                  bias corrections taken at t = step - skipped (a skipped step does not count for this network) and NO store at
+//                  all when finite == 0.
 // With coef == 1 and skipped == 0 the update is k_adam_hyper's bit for bit (x * 1.0f and t - 0.0f are exact, -ffp-contract=off).
-#include "cc_common.h"
+#include "adam_update.h"
 #include "../../include/ccengine.h"
 
 namespace {
@@ -17,19 +18,6 @@ namespace {
 constexpr int kThreads = 256;
 constexpr int kLoads = 4;               // independent 16-byte loads a work-item issues before it consumes the first one
 constexpr int kMaxBlocks = CC_GRAD_GUARD_MAX_BLOCKS;      // 4 workgroups (16 waves, 64 KB of loads in flight) per CU on 256 CUs
-
-__device__ __forceinline__ double block_sum(double v, double* red) {
-    const int t = threadIdx.x;
-    red[t] = v;
-    __syncthreads();
-    for (int s = kThreads / 2; s > 0; s >>= 1) {
-        if (t < s) red[t] += red[t + s];
-        __syncthreads();
-    }
-    const double r = red[0];
-    __syncthreads();
-    return r;
-}
 
 __device__ __forceinline__ double sumsq4(double acc, const float4 x) {
     acc += (double)x.x * (double)x.x;
@@ -57,7 +45,7 @@ __global__ __launch_bounds__(kThreads) void k_grad_sumsq(const float* __restrict
     for (; i < n4; i += T) acc = sumsq4(acc, g4[i]);
     if (blockIdx.x == 0 && threadIdx.x == 0)
         for (long j = n4 << 2; j < n; j++) acc += (double)g[j] * (double)g[j];
-    const double s = block_sum(acc, red);
+    const double s = cc::block_tree<kThreads, cc::Sum>(acc, red);
     if (threadIdx.x == 0) partials[blockIdx.x] = s;
 }
 
@@ -67,7 +55,7 @@ __global__ __launch_bounds__(kThreads) void k_guard_finish(const double* __restr
     __shared__ double red[kThreads];
     double acc = 0.0;
     for (int b = threadIdx.x; b < nblocks; b += kThreads) acc += partials[b];
-    const double sumsq = block_sum(acc, red);
+    const double sumsq = cc::block_tree<kThreads, cc::Sum>(acc, red);
     if (threadIdx.x != 0) return;
     const bool finite = sumsq <= 1.7976931348623157e308;          // (a sum of squares: >= 0, +Inf or NaN)
     const float norm = (float)((double)grad_scale * sqrt(sumsq));
@@ -92,40 +80,10 @@ __global__ __launch_bounds__(kThreads) void k_adam_guard(float* __restrict__ p, 
     if (i4 >= n) return;
     if (guard[2] == 0.f) return;            // a NaN / Inf in this network's gradient: p, m, v keep their bits
     const bool full = i4 + 3 < n;
-    float4 pp, gg, mm, vv;
-    if (full) {
-        pp = *reinterpret_cast<float4*>(p + i4);
-        gg = *reinterpret_cast<const float4*>(g + i4);
-        mm = *reinterpret_cast<float4*>(m + i4);
-        vv = *reinterpret_cast<float4*>(v + i4);
-    }
-    const float lr = h[0], b1 = h[1], b2 = h[2], eps = h[3], wd = h[4];
-    const float coef = guard[1];
-    const float t = step[0] - guard[3];
-    const float bc1 = 1.f - powf(b1, t), bc2 = 1.f - powf(b2, t);
-    const float step_size = lr / bc1, rs2 = 1.f / sqrtf(bc2);
-    if (full) {
-        float* P = &pp.x; const float* G = &gg.x; float* M = &mm.x; float* V = &vv.x;
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            float gr = (G[k] * grad_scale) * coef;
-            if (wd != 0.f) gr = gr + wd * P[k];
-            M[k] = b1 * M[k] + (1.f - b1) * gr;
-            V[k] = b2 * V[k] + (1.f - b2) * gr * gr;
-            P[k] -= step_size * (M[k] / (sqrtf(V[k]) * rs2 + eps));
-        }
-        *reinterpret_cast<float4*>(p + i4) = pp;
-        *reinterpret_cast<float4*>(m + i4) = mm;
-        *reinterpret_cast<float4*>(v + i4) = vv;
-    } else {
-        for (long i = i4; i < n; i++) {
-            float gr = (g[i] * grad_scale) * coef;
-            if (wd != 0.f) gr = gr + wd * p[i];
-            m[i] = b1 * m[i] + (1.f - b1) * gr;
-            v[i] = b2 * v[i] + (1.f - b2) * gr * gr;
-            p[i] -= step_size * (m[i] / (sqrtf(v[i]) * rs2 + eps));
-        }
-    }
+    ccadam::Quad q;
+    if (full) ccadam::load4(q, p, g, m, v, i4);
+    const ccadam::Coefs c = ccadam::coefs(h[0], h[1], h[2], h[3], h[4], step[0] - guard[3], grad_scale, guard[1]);
+    ccadam::update4<true, true>(p, g, m, v, i4, n, full, q, c);
 }
 
 int sumsq_blocks(long n) {

@@ -9,12 +9,13 @@
 #include <hip/hip_runtime.h>
 #include "cc_common.h"
 #include "pose_mat.h"
+#include "radix_select.h"
 #include "../../include/ccengine.h"
 
 namespace {
 
 constexpr int kThreads = 256;
-constexpr int kBins = 256;              // radix-select digit: 8 bits, 4 passes over the fp32 key
+using ccradix::kBins;
 constexpr int kSel = 4;                 // selections: gt lower, gt upper, pred lower, pred upper middle element
 constexpr int kEigenSums = 7;           // per row: |d|/gt, d^2/gt, d^2, (log gt - log p)^2, thresh < 1.25, 1.25^2, 1.25^3
 constexpr int kMaxEigenBlocks = 64;
@@ -215,13 +216,11 @@ __device__ __forceinline__ bool eigen_valid(const EigenArgs& a, long i, long bw,
     return (double)g > a.lo && (double)g < a.hi;          // generate_mask (:194-206) inside the Garg crop
 }
 
-// radix-select pass `pass` of the four middle elements (np.median averages the two middle values of an even count):
+// radix-select pass `pass` (radix_select.h) of the four middle elements (np.median averages the two middle values of an even count):
 // selections 0/1 over the valid gt, 2/3 over the prediction at the same pixels.  Valid keys are positive fp32.
 __global__ __launch_bounds__(kThreads) void k_eigen_hist(EigenArgs a, unsigned* hist, const unsigned* state, int pass) {
     __shared__ unsigned h[kSel * kBins];
-    for (int j = threadIdx.x; j < kSel * kBins; j += kThreads) h[j] = 0u;
-    __syncthreads();
-    const int shift = 24 - 8 * pass;
+    ccradix::clear<kThreads>(h, kSel * kBins);
     unsigned pre[kSel];
     for (int s = 0; s < kSel; s++) pre[s] = state[4 * s];
     const long bw = a.x2 - a.x1, n = (long)(a.y2 - a.y1) * bw;
@@ -229,41 +228,16 @@ __global__ __launch_bounds__(kThreads) void k_eigen_hist(EigenArgs a, unsigned* 
         float g, p;
         if (!eigen_valid(a, i, bw, g, p)) continue;
         const unsigned key[2] = {__float_as_uint(g), __float_as_uint(p)};
-        for (int s = 0; s < kSel; s++) {
-            const unsigned k = key[s >> 1];
-            if (pass == 0 || (k >> (shift + 8)) == (pre[s] >> (shift + 8))) atomicAdd(&h[s * kBins + ((k >> shift) & (kBins - 1))], 1u);
-        }
+        for (int s = 0; s < kSel; s++) ccradix::count_key(h + s * kBins, key[s >> 1], pre[s], pass);
     }
-    __syncthreads();
-    for (int j = threadIdx.x; j < kSel * kBins; j += kThreads)
-        if (h[j]) atomicAdd(&hist[j], h[j]);
+    ccradix::flush<kThreads>(h, hist, kSel * kBins);
 }
 
-// one work-item per selection: pick the bin that holds the remaining rank, extend the prefix, clear the histogram
+// one work-item per selection: even selections the lower, odd ones the upper middle element
 __global__ __launch_bounds__(64) void k_eigen_select(unsigned* hist, unsigned* state, int pass) {
     const int s = threadIdx.x;
     if (s >= kSel) return;
-    unsigned* hs = hist + s * kBins;
-    unsigned* st = state + 4 * s;
-    if (pass == 0) {
-        unsigned c = 0;
-        for (int j = 0; j < kBins; j++) c += hs[j];
-        st[2] = c;
-        st[1] = c > 0 ? ((s & 1) ? c / 2 : (c - 1) / 2) : 0;
-    }
-    const int shift = 24 - 8 * pass;
-    unsigned cum = 0;
-    const unsigned rank = st[1];
-    for (int j = 0; j < kBins; j++) {
-        const unsigned c = hs[j];
-        if (c > 0 && rank < cum + c) {
-            st[0] |= (unsigned)j << shift;
-            st[1] = rank - cum;
-            break;
-        }
-        cum += c;
-    }
-    for (int j = 0; j < kBins; j++) hs[j] = 0u;
+    ccradix::select(hist + s * kBins, state + 4 * s, pass, (s & 1) != 0);
 }
 
 // the two scale factors: row 0 the PoseNet one (test_disp.py:130-136; 0 without displacements > 0), row 1 the median ratio
@@ -320,14 +294,8 @@ __global__ __launch_bounds__(kThreads) void k_eigen_terms(EigenArgs a, const uns
         }
     }
     for (int j = 0; j < 2 * kEigenSums; j++) {
-        red[threadIdx.x] = acc[j];
-        __syncthreads();
-        for (int st = kThreads / 2; st > 0; st >>= 1) {
-            if ((int)threadIdx.x < st) red[threadIdx.x] += red[threadIdx.x + st];
-            __syncthreads();
-        }
-        if (threadIdx.x == 0) partial[(long)blockIdx.x * 2 * kEigenSums + j] = red[0];
-        __syncthreads();
+        const double t = cc::block_tree<kThreads, cc::Sum>(acc[j], red);
+        if (threadIdx.x == 0) partial[(long)blockIdx.x * 2 * kEigenSums + j] = t;
     }
 }
 

@@ -130,13 +130,8 @@ __global__ __launch_bounds__(kThreads) void k_census_max(const float* __restrict
         const unsigned key = __float_as_uint(du * du + dv * dv) & 0x7fffffffu;
         m = key > m ? key : m;
     }
-    red[threadIdx.x] = m;
-    __syncthreads();
-    for (int st = kThreads / 2; st > 0; st >>= 1) {
-        if ((int)threadIdx.x < st) red[threadIdx.x] = red[threadIdx.x + st] > red[threadIdx.x] ? red[threadIdx.x + st] : red[threadIdx.x];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) atomicMax(&smax[b], red[0]);
+    m = cc::block_tree<kThreads, cc::Max>(m, red);
+    if (threadIdx.x == 0) atomicMax(&smax[b], m);
 }
 
 struct NormOut {

@@ -566,22 +566,11 @@ __global__ __launch_bounds__(256) void k_elementwise_jobs(JobTab t, int op, int 
 // reference's rounding order.  A job's "image" is the N = C*H*W elements of one sample (rows carry (C*H, W)), cut into pieces of
 // SN_PPT * 256 elements, one workgroup each.  Two launches per direction for all levels:
 //   *_sum_jobs    every workgroup adds its piece in fp64 -- a work-item its SN_PPT elements in index order, the work-items in the
-//                 fixed tree of block_sum_f64 -- and stores ONE fp64 partial, unconditionally (nothing is cleared beforehand);
+//                 fixed tree of cc::block_sum_f64 (cc_common.h) -- and stores ONE fp64 partial, unconditionally (nothing is cleared beforehand);
 //   *_apply_jobs  every workgroup adds the partials of ITS sample in index order (each arrives at the same bits), rounds the mean
 //                 to fp32 once and writes its piece.
 // No atomics, no host sync; a piece's place depends on N alone, so a level gives the same bits alone and as one row of a table.
 constexpr int SN_PPT = 16;
-
-__device__ __forceinline__ double block_sum_f64(double v, double* red) {        // red: 4 doubles; every work-item gets the total
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
-    if (lane == 0) red[wid] = v;
-    __syncthreads();
-    const double r = (red[0] + red[1]) + (red[2] + red[3]);
-    __syncthreads();
-    return r;
-}
 
 // part[0] + part[1] + ... + part[np - 1], in that order, in every work-item (staged through LDS 256 at a time: broadcast reads)
 __device__ __forceinline__ double sn_total(const double* __restrict__ part, int np, double* stage) {
@@ -611,7 +600,7 @@ __global__ __launch_bounds__(256) void k_spatial_norm_sum_jobs(JobTab t) {
     double acc = 0.0;
 #pragma unroll
     for (int k = 0; k < SN_PPT; k++) acc += (double)v[k];
-    const double s = block_sum_f64(acc, red);
+    const double s = cc::block_sum_f64(acc, red);
     if (threadIdx.x == 0) ccjobs::ptr<double>(t, w.j, 4)[(size_t)w.b * per + w.blk] = s;
 }
 
@@ -669,7 +658,7 @@ __global__ __launch_bounds__(256) void k_spatial_norm_bwd_sum_jobs(JobTab t) {
     double acc = 0.0;
 #pragma unroll
     for (int k = 0; k < SN_PPT; k++) acc += (double)v[k];
-    const double s = block_sum_f64(acc, red);
+    const double s = cc::block_sum_f64(acc, red);
     if (threadIdx.x == 0) ccjobs::ptr<double>(t, w.j, 6)[(size_t)w.b * per + w.blk] = s;
 }
 

@@ -2,11 +2,12 @@
 // errors / Fl outliers (flow_diff, compute_epe, outlier_err, compute_all_epes) and the Eigen depth errors (compute_errors) on the
 // device, without a host synchronisation, so that a validation pass can be captured into a hipGraph.
 //
-// Determinism: float sums are fp64 per-thread accumulators, a fixed LDS tree per workgroup, a per-workgroup slab in the caller's
+// Determinism: float sums are fp64 per-thread accumulators, a fixed LDS tree per workgroup (cc::block_tree), a per-workgroup slab in the caller's
 // workspace and a fixed-order final reduce; only the integer radix histograms of the exact depth medians use global atomics.
 // The bilinear resizes follow F.interpolate(mode='bilinear', align_corners=False) tap for tap (the build keeps -ffp-contract=off).
 #include <hip/hip_runtime.h>
 #include "cc_common.h"
+#include "radix_select.h"
 #include "../../include/ccengine.h"
 
 namespace {
@@ -17,7 +18,7 @@ constexpr int kMaxMasks = 2;
 constexpr int kMaxFlowBlocks = 512;
 constexpr int kDepthSums = 6;       // per sample: sum |d|, sum |d|/gt, sum d^2/gt, counts of thresh < 1.25, 1.25^2, 1.25^3
 constexpr int kMaxDepthBlocks = 64; // per sample
-constexpr int kBins = 256;          // radix-select digit: 8 bits, 4 passes over the fp32 key
+using ccradix::kBins;
 
 // upsample_bilinear2d, align_corners=False: src = max(scale*(dst+0.5)-0.5, 0), i1 = i0+1 only while i0 < in-1
 struct Tap {
@@ -73,20 +74,6 @@ struct FlowArgs {
 __device__ __forceinline__ float epe_of(float ug, float vg, float up, float vp) {
     const float du = ug - up, dv = vg - vp;
     return sqrtf(du * du + dv * dv);
-}
-
-// fixed-shape LDS tree over the workgroup -> thread 0 holds the sum (same order every run)
-__device__ __forceinline__ double block_sum(double v, double* red) {
-    const int t = threadIdx.x;
-    red[t] = v;
-    __syncthreads();
-    for (int s = kThreads / 2; s > 0; s >>= 1) {
-        if (t < s) red[t] += red[t + s];
-        __syncthreads();
-    }
-    const double r = red[0];
-    __syncthreads();
-    return r;
 }
 
 __host__ __device__ inline int flow_blocks(int B, int Hg, int Wg) {
@@ -222,7 +209,7 @@ __global__ __launch_bounds__(kThreads) void k_flow_metrics(FlowArgs a, FlowTable
     }
 #pragma unroll
     for (int j = 0; j < NV * kFlowSums; j++) {
-        const double t = block_sum(acc[j], red);
+        const double t = cc::block_tree<kThreads, cc::Sum>(acc[j], red);
         if (threadIdx.x == 0) partial[(long)blockIdx.x * NV * kFlowSums + j] = t;
     }
 }
@@ -297,14 +284,12 @@ __device__ __forceinline__ float clamp_depth(float p) {       // torch.clamp(p, 
     return p != p ? p : (p < 1e-3f ? 1e-3f : (p > 80.f ? 80.f : p));
 }
 
-// radix-select pass `pass` (digit = bits [24-8*pass, 32-8*pass)) of the lower medians of valid gt and valid clamped pred:
-// histogram of the keys that match the digits selected so far.  Valid keys are positive fp32, so their bits order as integers.
+// radix-select pass `pass` (radix_select.h) of the lower medians of valid gt and valid clamped pred: histogram of the keys that
+// match the digits selected so far.  Valid keys are positive fp32, so their bits order as integers.
 __global__ __launch_bounds__(kThreads) void k_depth_hist(DepthArgs a, unsigned* hist, unsigned* state, int pass) {
     __shared__ unsigned h[2 * kBins];
-    for (int j = threadIdx.x; j < 2 * kBins; j += kThreads) h[j] = 0u;
-    __syncthreads();
+    ccradix::clear<kThreads>(h, 2 * kBins);
     const int b = blockIdx.y;
-    const int shift = 24 - 8 * pass;
     unsigned* st = state + (long)b * 8;
     const unsigned pre_g = st[0], pre_p = st[4];
     const int bw = a.x2 - a.x1;
@@ -316,57 +301,29 @@ __global__ __launch_bounds__(kThreads) void k_depth_hist(DepthArgs a, unsigned* 
         const float g = a.gt[o];
         if (!(g > 0.f && g < 80.f)) continue;
         const float p = clamp_depth(a.pred[o]);
-        const unsigned kg = __float_as_uint(g);
-        if (pass == 0 || (kg >> (shift + 8)) == (pre_g >> (shift + 8))) atomicAdd(&h[(kg >> shift) & (kBins - 1)], 1u);
+        ccradix::count_key(h, __float_as_uint(g), pre_g, pass);
         if (p != p) {
             nan_p++;
             continue;
         }
-        const unsigned kp = __float_as_uint(p);
-        if (pass == 0 || (kp >> (shift + 8)) == (pre_p >> (shift + 8))) atomicAdd(&h[kBins + ((kp >> shift) & (kBins - 1))], 1u);
+        ccradix::count_key(h + kBins, __float_as_uint(p), pre_p, pass);
     }
     if (pass == 0 && nan_p) atomicAdd(&st[7], nan_p);
-    __syncthreads();
-    unsigned* gh = hist + (long)b * 2 * kBins;
-    for (int j = threadIdx.x; j < 2 * kBins; j += kThreads)
-        if (h[j]) atomicAdd(&gh[j], h[j]);
+    ccradix::flush<kThreads>(h, hist + (long)b * 2 * kBins, 2 * kBins);
 }
 
-// one thread per (sample, array): pick the bin that holds the remaining rank, extend the prefix, clear the histogram
+// one thread per (sample, array): torch.median's lower median
 __global__ __launch_bounds__(64) void k_depth_select(unsigned* hist, unsigned* state, int B, int pass) {
     const int t = threadIdx.x + blockIdx.x * 64;
     if (t >= 2 * B) return;
-    unsigned* h = hist + (long)t * kBins;
-    unsigned* st = state + (long)t * 4;
-    if (pass == 0) {
-        unsigned c = 0;
-        for (int j = 0; j < kBins; j++) c += h[j];
-        st[2] = c;
-        st[1] = c > 0 ? (c - 1) / 2 : 0;       // torch.median: the lower median
-    }
-    const int shift = 24 - 8 * pass;
-    unsigned cum = 0, rank = st[1];
-    for (int j = 0; j < kBins; j++) {
-        const unsigned c = h[j];
-        if (c > 0 && rank < cum + c) {
-            st[0] |= (unsigned)j << shift;
-            st[1] = rank - cum;
-            break;
-        }
-        cum += c;
-    }
-    for (int j = 0; j < kBins; j++) h[j] = 0u;
-}
-
-__device__ __forceinline__ float median_of(const unsigned* st) {
-    return (st[2] == 0 || st[3] != 0) ? __int_as_float(0x7fc00000) : __uint_as_float(st[0]);
+    ccradix::select(hist + (long)t * kBins, state + (long)t * 4, pass, false);
 }
 
 // compute_errors, loss_functions.py:446-465: per-pixel terms of the median-scaled prediction -> per-workgroup fp64 partials
 __global__ __launch_bounds__(kThreads) void k_depth_terms(DepthArgs a, const unsigned* state, double* partial) {
     __shared__ double red[kThreads];
     const int b = blockIdx.y;
-    const float mg = median_of(state + (long)b * 8), mp = median_of(state + (long)b * 8 + 4);
+    const float mg = ccradix::median_of(state + (long)b * 8), mp = ccradix::median_of(state + (long)b * 8 + 4);
     const int bw = a.x2 - a.x1;
     const long n = (long)(a.y2 - a.y1) * bw;
     double acc[kDepthSums] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
@@ -387,7 +344,7 @@ __global__ __launch_bounds__(kThreads) void k_depth_terms(DepthArgs a, const uns
         acc[5] += th < 1.953125f ? 1.0 : 0.0;
     }
     for (int j = 0; j < kDepthSums; j++) {
-        const double t = block_sum(acc[j], red);
+        const double t = cc::block_tree<kThreads, cc::Sum>(acc[j], red);
         if (threadIdx.x == 0) partial[((long)b * gridDim.x + blockIdx.x) * kDepthSums + j] = t;
     }
 }

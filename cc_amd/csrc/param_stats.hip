@@ -3,7 +3,7 @@
 // "which layer blew up" (the gradient guard, grad_guard.hip, reports per NETWORK).  One sweep over flat_g and flat_p, two launches,
 // no host sync, no atomics, nothing cleared beforehand, the same bits on every call:
 //   k_param_chunk   one workgroup per chunk (<= CC_PARAM_STATS_CHUNK floats of ONE parameter, host-built table): fp64 accumulation,
-//                   a fixed assignment of elements to work-items and a fixed reduction tree; every workgroup stores its four
+//                   a fixed assignment of elements to work-items and a fixed reduction tree (cc::block_tree); every workgroup stores its four
 //                   partials unconditionally.  A parameter starts at any offset of the bucket (only a network's start is 256-byte
 //                   aligned): 16-byte loads on the aligned interior, scalar loads on the <= 3 elements in front of and behind it.
 //                   HBM-bound (2 x 297 MB for the four networks): like k_grad_sumsq, a work-item has kLoads independent 16-byte
@@ -39,23 +39,6 @@ __device__ __forceinline__ void add4(Acc& a, const float4 g, const float4 p) {
     add1(a, g.w, p.w);
 }
 
-template <bool MAX>
-__device__ __forceinline__ double block_reduce(double v, double* red) {
-    const int t = threadIdx.x;
-    red[t] = v;
-    __syncthreads();
-    for (int s = kThreads / 2; s > 0; s >>= 1) {
-        if (t < s) {
-            if (MAX) red[t] = red[t + s] > red[t] ? red[t + s] : red[t];
-            else red[t] += red[t + s];
-        }
-        __syncthreads();
-    }
-    const double r = red[0];
-    __syncthreads();
-    return r;
-}
-
 __global__ __launch_bounds__(kThreads) void k_param_chunk(const float* __restrict__ g, const float* __restrict__ p, long n,
                                                           const long* __restrict__ chunks, double* __restrict__ partials) {
     __shared__ double red[kThreads];
@@ -87,10 +70,10 @@ __global__ __launch_bounds__(kThreads) void k_param_chunk(const float* __restric
         for (int k = 0; k < kLoads; k++) add4(a, x[k], y[k]);
     }
     for (; i < n4; i += kThreads) add4(a, g4[i], p4[i]);
-    const double gs = block_reduce<false>(a.gs, red);
-    const double ps = block_reduce<false>(a.ps, red);
-    const double mx = block_reduce<true>((double)a.mx, red);
-    const double nf = block_reduce<false>((double)a.nf, red);
+    const double gs = cc::block_tree<kThreads, cc::Sum>(a.gs, red);
+    const double ps = cc::block_tree<kThreads, cc::Sum>(a.ps, red);
+    const double mx = cc::block_tree<kThreads, cc::Max>((double)a.mx, red);
+    const double nf = cc::block_tree<kThreads, cc::Sum>((double)a.nf, red);
     if (t == 0) {
         out[0] = gs;
         out[1] = ps;

@@ -760,13 +760,8 @@ __global__ __launch_bounds__(256) void k_fx_absmax(const float* __restrict__ x, 
             if (b < 0x7f800000u && b > m) m = b;             // finite values only
         }
     }
-    red[threadIdx.x] = m;
-    __syncthreads();
-    for (int st = 128; st > 0; st >>= 1) {
-        if ((int)threadIdx.x < st && red[threadIdx.x + st] > red[threadIdx.x]) red[threadIdx.x] = red[threadIdx.x + st];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0 && red[0]) atomicMax(out, red[0]);
+    m = cc::block_tree<256, cc::Max>(m, red);
+    if (threadIdx.x == 0 && m) atomicMax(out, m);
 }
 
 __global__ __launch_bounds__(256) void k_fx_to_float(const unsigned long long* __restrict__ fx, const unsigned* __restrict__ mx,

@@ -634,7 +634,9 @@ int cc_adam_tick(float* step_dev, void* stream);
  * row: equal bounds); bounds[0] = 0, ascending, every bound a multiple of 4 floats but the last one (= n). */
 int cc_adam_step_hyper(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, float* step_dev, long n,
                        const float* hyper, const long* bounds, int rows, float grad_scale, void* stream);
-/* ... on a sub-range that lies inside ONE row (base pointers of the range, hyper_row = hyper + 8 * row); tick as above. */
+/* ... on a sub-range that lies inside ONE row (base pointers of the range, hyper_row = hyper + 8 * row); tick as above.
+ * The four entries above and cc_adam_step_segment_guard run ONE update body (cc_amd/csrc/adam_update.h); with weight_decay == 0
+ * and the same values the table-driven entries give the bits of cc_adam_step / cc_adam_step_segment. */
 int cc_adam_step_segment_hyper(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, float* step_dev, long n,
                                const float* hyper_row, float grad_scale, int tick, void* stream);
 int cc_fill(float* p, long n, float value, void* stream);
@@ -656,7 +658,8 @@ int cc_grad_guard_finish(const double* partials, int nblocks, const float* hyper
                          void* stream);
 /* cc_adam_step_segment_hyper's update of a range inside one row, with the gradient (g * grad_scale) * coef (weight decay is added
  * after the clipping, as in torch), the bias corrections at t = step_dev[0] - skipped, and no store at all when finite == 0.
- * Never advances the counter (cc_adam_tick does).  coef == 1 and skipped == 0: the bits of cc_adam_step_segment_hyper. */
+ * Never advances the counter (cc_adam_tick does).  coef == 1 and skipped == 0: the bits of cc_adam_step_segment_hyper (the
+ * same body, cc_amd/csrc/adam_update.h, with the coef multiply compiled in). */
 int cc_adam_step_segment_guard(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, const float* step_dev, long n,
                                const float* hyper_row, const float* guard_row, float grad_scale, void* stream);
 

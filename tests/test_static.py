@@ -99,3 +99,35 @@ def test_step_state_is_switched_in_one_module():
     outside = {s for s in sites if s[0] != "cc_amd/step_scope.py"}
     assert outside == STEP_STATE_EXCEPTIONS, sorted(outside ^ STEP_STATE_EXCEPTIONS)
     assert {name for f, name in sites if f == "cc_amd/step_scope.py"} == set(STEP_STATE_ASSIGNED + STEP_STATE_CALLS)
+
+
+# hand-rolled LDS trees deliberately left outside cc::block_tree (cc_common.h): (file, kernel) -> why
+TREE_ALLOWED = {
+    ("prep.hip", "k_frames_minmax_partial"): "min and max of one value in ONE barrier sequence, fminf / fmaxf (NaN-dropping) on float",
+    ("prep.hip", "k_frames_minmax_final"): "the same pair over MMB = 64 partials",
+    ("prep.hip", "k_store_minmax"): "min and max of one byte value in one barrier sequence, over unsigned",
+    ("prep.hip", "k_local_norm_partial"): "sum and sum of squares in one barrier sequence; block_tree's order, left as it is: prep.hip is outside the consolidated kernels",
+    ("prep.hip", "k_local_norm_final"): "the same pair over LNB = 64 partials",
+}
+
+
+def test_small_kernel_bodies_are_written_once():
+    """the Adam update, the strided LDS tree and the radix-select pick each have ONE text under cc_amd/csrc/ (adam_update.h,
+    cc_common.h, radix_select.h): the bit-identities between the entries that share them do not rest on copies kept alike"""
+    import re
+    csrc = os.path.join(ROOT, "cc_amd", "csrc")
+    src = {os.path.basename(f): open(f).read() for f in glob.glob(os.path.join(csrc, "*.hip")) + glob.glob(os.path.join(csrc, "*.h"))}
+    assert [f for f, t in src.items() if "(1.f - b1) *" in t] == ["adam_update.h"]
+    assert [f for f, t in src.items() if "st[0] |= (unsigned)j << shift" in t] == ["radix_select.h"]
+    tree = re.compile(r"for\s*\(\s*(?:const\s+)?(?:int|unsigned|long|size_t)[\w\s]*?\b(\w+)\s*=[^;]+;\s*\1\s*>\s*0\s*;\s*\1\s*(?:>>=\s*1|/=\s*2)\s*\)")
+    kernel = re.compile(r"__global__[^;{]*?\bvoid\s+(\w+)\s*\(")
+    found = set()
+    for f, t in src.items():
+        if f == "cc_common.h":
+            assert len(tree.findall(t)) == 1 and "block_tree" in t and "block_sum_f64" in t
+            continue
+        assert not re.search(r"^[^/\n]*\b\w*(block_sum|block_reduce)\w*\s*\([^;{]*\)\s*\{", t, re.M), f + " defines a block reduction of its own"
+        for m in tree.finditer(t):
+            owner = [k.group(1) for k in kernel.finditer(t, 0, m.start())]
+            found.add((f, owner[-1] if owner else None))
+    assert found == set(TREE_ALLOWED), sorted(found ^ set(TREE_ALLOWED))
