@@ -47,6 +47,20 @@ class _Uploader(object):
             torch.cuda.current_stream().synchronize()        # the staging buffers are released with this object
 
 
+def frame_tables(found):
+    """crawl's samples -> (paths: each distinct frame once, in order of first use; samples int32 [S,1+R] of ids into paths;
+    sample_scene int32 [S]) -- the store's frame order, shared with the stores `datasets.prepare` writes directly"""
+    ids, paths = {}, []
+    for _, ps in found:
+        for p in ps:
+            if p not in ids:
+                ids[p] = len(paths)
+                paths.append(p)
+    samples = np.array([[ids[p] for p in ps] for _, ps in found], dtype=np.int32)
+    sample_scene = np.array([s for s, _ in found], dtype=np.int32)
+    return paths, samples, sample_scene
+
+
 class FrameStore(object):
     """frames: uint8 [F,H,W,3] on the device, each distinct frame once; minmax: fp32 [F,2] on the device.  On the host (the batch
     tables are drawn there): intrinsics float32 [scenes,3,3]; samples int32 [S,1+R], frame ids with the target first and the
@@ -85,14 +99,7 @@ class FrameStore(object):
         scenes, intrinsics, found = crawl(root, train, sequence_length)
         if not found:
             raise ValueError("%s: no scene with %d or more frames" % (root, sequence_length))
-        ids, paths = {}, []
-        for _, ps in found:
-            for p in ps:
-                if p not in ids:
-                    ids[p] = len(paths)
-                    paths.append(p)
-        samples = np.array([[ids[p] for p in ps] for _, ps in found], dtype=np.int32)
-        sample_scene = np.array([s for s, _ in found], dtype=np.int32)
+        paths, samples, sample_scene = frame_tables(found)
         first = load_as_uint8(paths[0])
         H, W, F = first.shape[0], first.shape[1], len(paths)
         total = F * H * W * 3 + 8 * F

@@ -403,6 +403,18 @@ int cc_store_rotate(const void* frames, const float* minmax_or_null, int F, cons
 size_t cc_sample_local_norm_ws_bytes(int B);
 int cc_sample_local_norm(float* x, void* ws, int B, int nf, int h, int w, long sample_stride, long frame_stride, void* stream);
 
+/* ---- data preparation (data/prepare_train_data.py with kitti_raw_loader.py:107-115 and cityscapes_loader.py:111-119;
+ * cc_amd/datasets/prepare.py): scipy.misc.imresize of a uint8 frame = Pillow's 8-bit bilinear resample, NO byte-scaling, and the
+ * result stays uint8.  src: uint8 [N,H,W,3]; dst: uint8 [N,h_keep,w,3] = rows 0 .. h_keep-1 of the resample to h x w
+ * (h_keep <= h; Cityscapes keeps int(h * 0.75) rows).  Horizontal pass to uint8, then the vertical pass, each with its own table:
+ * htab: int32 [w * (1 + KH)] = first[w] followed by weights[w][KH]; vtab: int32 [h * (1 + KV)] likewise (Pillow's 22-bit
+ * coefficients, zero padded to the axis' tap count; cc_amd/custom_transforms.py resample_table); accumulate from 1 << 21, shift,
+ * clip.  Bit-exact with Image.resize((w, h), BILINEAR), any ratio, the same size included.  Frame offsets are 64-bit.
+ * 1 <= N <= 65535, H * w and h_keep * w below 2^31.  ws: cc_frames_resize_u8_ws(N, H, w) bytes (the uint8 [N,H,w,3] intermediate). */
+size_t cc_frames_resize_u8_ws(int N, int H, int w);
+int cc_frames_resize_u8(const void* src, void* dst, const int* htab, int KH, const int* vtab, int KV, void* ws, int N, int H, int W,
+                        int h, int w, int h_keep, void* stream);
+
 /* ---------------------------------------------------------------- BatchNorm2d, training mode
  * (models/DispResNet6.py:53-56: the Conv1x1 + BatchNorm2d shortcut of every ResNet stage; 13 per forward)
  * y = (x - mean_c) / sqrt(var_c + eps) * w_c + b_c with batch statistics over (B,H,W); running stats updated with
